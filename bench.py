@@ -2,7 +2,15 @@
 """Benchmark of the hot path (BASELINE.json metric: GCUPS, 10k x 10k Smith-Waterman).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4|c3|c5|ref] [--ref-len L]
-                    [--ref-pair a,b]
+                    [--ref-pair a,b] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs
+(--dump-outputs) and prints ONE JSON line (rank 0) with value = whole-job GCUPS
+and ms_per_step; the only check it makes is that the plan's sticky error word is
+0 (every timed step completed its waits).  Everything else described below (the
+comparisons with the CPU oracle and the fixtures, the DP kernel's own time and
+roofline, the same-run C4 strong-scaling record, the CPU baseline, the boundary
+call of `ref`) runs only with --full and adds its fields to the same line.
 
 One process per GPU (torch.distributed, backend "nccl" = RCCL over xGMI when
 launched by torch.distributed.run).  A "step" is one pass of the DP fill over
@@ -27,9 +35,15 @@ one batch of input already resident in HBM:
   in, printed text out: PCIe, plan set-up, node list and print_seq included)
   is timed separately and reported as boundary_call_ms, never as the value.
 
-After the timed steps (outside the timed region) the run is checked: the
-plan's sticky error word must be 0 (every timed step completed its waits), the
-score must equal the CPU oracle's, for c2 the checksum of the whole H matrix
+--dump-outputs DIR writes what a caller of the timed path holds after the last
+timed step as DIR/<name>.npy (float64): `scores` (one per pair; c4: the gathered
+vector), `cells_sample` (c2 / c3 / c5 / ref: the H or direction cells at a fixed,
+seeded sample of in-range (i, j), listed in `cells_sample_ij`) and, for c5 / ref,
+`traceback_ops` with `traceback_info` (op count, begin cell, status).  The inputs
+and the sample depend on the arguments alone, so two builds compare file by file.
+
+With --full, after the timed steps (outside the timed region) the run is checked:
+the score must equal the CPU oracle's, for c2 the checksum of the whole H matrix
 the timed steps wrote must equal the oracle's, for c4 the gathered scores must
 equal the committed fixture.  Prints ONE JSON line (rank 0) with value =
 whole-job GCUPS, the roofline of the DP kernel (HIP events around that kernel
@@ -70,9 +84,14 @@ def parse():
     ap.add_argument("--ref-pair", default="0,1", help="ref workload: dataset indices a,b of the pair")
     ap.add_argument("--pairs", type=int, default=0,
                     help="c4: run only the first PAIRS of the 1024 pairs (e.g. 128 = one rank's share at N=8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the outputs against the CPU oracle / fixtures and measure the DP kernel's "
+                         "time and roofline, the C4 strong-scaling record (c2) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-c4-strong", action="store_true",
-                    help="c2: skip the same-run C4 strong-scaling sub-record (config.c4_strong)")
+                    help="--full, c2: skip the same-run C4 strong-scaling sub-record (config.c4_strong)")
     ap.add_argument("--synthetic", action="store_true", help="i.i.d. ACGT (splitmix seed) instead of the dataset")
     return ap.parse_args()
 
@@ -241,6 +260,58 @@ def c4_strong(rank: int, world: int, dev, steps: int, warmup: int, syn: bool):
                      "one RCCL all-gather of the scores per step")
 
 
+DUMP_SAMPLE_CELLS = 1 << 20  # 3 float64 per sampled cell: 24 MiB, within --dump-outputs' 64 MB
+DUMP_SEED = 0x5EEDD0D0
+
+
+def sample_cells(plan, pair: int = 0, count: int = DUMP_SAMPLE_CELLS, seed: int = DUMP_SEED):
+    """A fixed sample of a pair's cells: (ij, idx), ij[k] = (i, j) with 1 <= i <= m and j in 1..n (banded
+    plans: inside the band), idx[k] = that cell's element in the plan's skewed cell output (plan.py's
+    layout; the stripe's first column comes from the stripe meta of the last run).  The same plan shape,
+    count and seed give the same sample in every run."""
+    from cse305_parallel_sequence_alignment_amd import _lib as LB
+
+    g = plan.geom[pair]
+    meta = plan.stripe_meta()
+    rng = np.random.default_rng(seed)
+    i = rng.integers(1, g.m + 1, size=count, dtype=np.int64)
+    if plan.band >= 0:
+        j = rng.integers(np.maximum(1, i - plan.band), np.minimum(g.n, i + plan.band) + 1, dtype=np.int64)
+    else:
+        j = rng.integers(1, g.n + 1, size=count, dtype=np.int64)
+    R = g.rows_per_lane
+    s, r, rho = (i - 1) // (64 * R), (i - 1) % (64 * R) // R, (i - 1) % R
+    t = j - meta[g.stripe0 + s, 0].astype(np.int64) + r
+    if t.min() < 0 or t.max() >= g.pmax * 16:
+        raise RuntimeError("sample_cells: a sampled cell lies outside its stripe's steps")
+    w = 16 if plan.cells == LB.CELLS_DIR else 4  # elements of one lane per block: 16 direction bytes, 4 int32 cells
+    idx = g.out_off + (((s * (g.pmax * 16 // w) + t // w) * R + rho) * 64 + r) * w + t % w
+    return np.stack([i, j], axis=1), idx
+
+
+def dump_outputs(dirname, plan, res, out, gathered=None, tb_ops=None, tb_info=None):
+    """--dump-outputs: what the last timed step left with its caller, as float64 .npy files."""
+    import torch
+
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    arrs = {}
+    if gathered is not None:
+        arrs["scores"] = gathered.cpu().numpy()
+    else:
+        arrs["scores"] = np.array([r["score"] for r in res])
+    if out is not None:
+        ij, idx = sample_cells(plan)
+        arrs["cells_sample_ij"] = ij
+        arrs["cells_sample"] = out[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    if tb_info is not None:
+        inf = tb_info.cpu().numpy()[:4]  # n_ops, begin cell, status (the rest are the walk's own counters)
+        arrs["traceback_info"] = inf
+        arrs["traceback_ops"] = tb_ops[:int(inf[0])].cpu().numpy()
+    for name, a in arrs.items():
+        np.save(d / f"{name}.npy", np.asarray(a, dtype=np.float64))
+
+
 def launch_ranks(gpus: int) -> int:
     """``bench.py --gpus N`` started without a launcher: run the same command under torch.distributed.run
     (N ranks, one per GPU) as a CHILD process -- nothing in this process has touched the GPU, and it never
@@ -403,11 +474,45 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- checks of what the timed steps produced (outside the timed region) ----
     err = plan.error()
     if err:
         raise SystemExit(f"rank {rank}: a kernel wait hit its spin limit (site {err}) during the timed steps")
     res = plan.results()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, plan, res, out, gathered=gathered if wl == "c4" else None,
+                     tb_ops=tb_ops if wl in ("c5", "ref") else None,
+                     tb_info=tb_info if wl in ("c5", "ref") else None)
+
+    total_cells = cells_per_step * args.steps * world
+    gcups = total_cells / elapsed / 1e9
+    line = {
+        "metric": "GCUPS (DP cell updates/s) + max-score match vs CPU, 10k×10k SW",
+        "value": round(gcups, 3),
+        "unit": "GCUPS",
+        "n_gpus": dist.get_world_size() if world > 1 else 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "strong" if wl == "c4" else "weak",  # c4: a fixed 1024-pair batch split over ranks
+        "vs_baseline": None,
+        "dtype": "int32",
+        "data": "synthetic i.i.d. ACGT" if syn else "gene_sequences_test (reference's bundled FASTA)",
+        "config": dict(workload=wl + ": " + desc, cells_per_step_per_gpu=int(cells_per_step),
+                       parallelism=(f"dp{world} (pairs sharded over GPUs; RCCL bcast of the reference, "
+                                    f"all-gather of scores every step)" if wl == "c4" else
+                                    f"dp{world} (one independent pair per GPU; RCCL bcast of the reference "
+                                    f"once; no collective in the step)"),
+                       score_rank0=int(res[0]["score"]), kernel_errors=0),
+    }
+    if not args.full:  # a plain run: the headline figure alone
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: checks of what the timed steps produced (outside the timed region) ----
     from oracle import oracle as O  # CPU checker
 
     checks = {}
@@ -522,8 +627,6 @@ def main():
     if strong is not None and not strong["scores_match_fixture"]:  # (all-reduced: every rank agrees)
         raise SystemExit(f"rank {rank}: c4_strong: gathered scores differ from tests/golden/c4_scores.json")
 
-    total_cells = cells_per_step * args.steps * world
-    gcups = total_cells / elapsed / 1e9
     if rank == 0:
         kern_gcups = cells_per_step / (kern_ms * 1e-3) / 1e9
         shape = f"pairs={len(qs)}" if wl == "c4" else f"{m},{n}"
@@ -553,40 +656,20 @@ def main():
                                    pairs=qs if wl == "c4" else None)
             except Exception as e:  # pragma: no cover
                 cpu = dict(value=None, unit="GCUPS", cores=1, kind="port", sample=f"failed: {e}")
-        line = {
-            "metric": "GCUPS (DP cell updates/s) + max-score match vs CPU, 10k×10k SW",
-            "value": round(gcups, 3),
-            "unit": "GCUPS",
-            "n_gpus": dist.get_world_size() if world > 1 else 1,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if wl == "c4" else "weak",  # c4: a fixed 1024-pair batch split over ranks
-            "vs_baseline": None,
-            "dtype": "int32",
-            "data": "synthetic i.i.d. ACGT" if syn else "gene_sequences_test (reference's bundled FASTA)",
-            "config": dict(workload=wl + ": " + desc, cells_per_step_per_gpu=int(cells_per_step),
-                           parallelism=(f"dp{world} (pairs sharded over GPUs; RCCL bcast of the reference, "
-                                        f"all-gather of scores every step)" if wl == "c4" else
-                                        f"dp{world} (one independent pair per GPU; RCCL bcast of the reference "
-                                        f"once; no collective in the step)"),
-                           score_rank0=int(res[0]["score"]), checks_all_ranks=bool(ok.item()), **checks,
-                           kernel_errors=0, dp_kernel_ms=round(kern_ms, 4),
-                           **({"traceback_ms": round(tb_ms, 4), "traceback_walk": tb_walk} if tb_ms is not None
-                              else {}),
-                           **({"dp_launch": dp_launch} if dp_launch is not None else {}),
-                           **({"c4_strong": strong} if strong is not None else {}),
-                           **({"score_allgather_ms": round(gather_ms, 4),
-                               "score_allgather_share": round(gather_ms / (elapsed / args.steps * 1e3), 4)}
-                              if gather_ms is not None else {}),
-                           **({"boundary_call_ms": round(boundary_ms, 3),
-                               "boundary_note": "msa_main_alignment with host buffers (plan set-up, H2D codes, fill, "
-                                                "device walk, D2H ops, node list, print_seq text): PCIe-inclusive, "
-                                                "not the value"} if wl == "ref" else {})),
-            "roofline": roof,
-            "cpu_baseline": cpu,
-        }
+        line["config"].update(
+            checks_all_ranks=bool(ok.item()), **checks, dp_kernel_ms=round(kern_ms, 4),
+            **({"traceback_ms": round(tb_ms, 4), "traceback_walk": tb_walk} if tb_ms is not None else {}),
+            **({"dp_launch": dp_launch} if dp_launch is not None else {}),
+            **({"c4_strong": strong} if strong is not None else {}),
+            **({"score_allgather_ms": round(gather_ms, 4),
+                "score_allgather_share": round(gather_ms / (elapsed / args.steps * 1e3), 4)}
+               if gather_ms is not None else {}),
+            **({"boundary_call_ms": round(boundary_ms, 3),
+                "boundary_note": "msa_main_alignment with host buffers (plan set-up, H2D codes, fill, "
+                                 "device walk, D2H ops, node list, print_seq text): PCIe-inclusive, "
+                                 "not the value"} if wl == "ref" else {}))
+        line["roofline"] = roof
+        line["cpu_baseline"] = cpu
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
