@@ -193,10 +193,17 @@ int msa_partition_tables(const int32_t* T1, const int32_t* T2, const int32_t* T3
                          msa_node* out, size_t cap, size_t* n_out);
 
 /* ---- device-resident plans (configs C2-C5) --------------------------------
- * A plan owns the device scratch for one shape of work; running it launches
- * the stripe kernel + a tiny per-pair reduction on `stream` (no allocation,
- * no host sync inside msa_plan_run).  Inputs are uint8 codes in [0,8) already
- * in device memory (see msa_encode_pair for the host-side code map); the
+ * A plan owns the device scratch for one shape of work.  msa_plan_create
+ * picks the kernel family from the description (msa_plan_launch_info reports
+ * it): the stripe kernel (a batch, a small batch split into items, or one
+ * pair), the flow kernels (one SW-linear pair; SW-affine / Gotoh with
+ * direction bytes; pass 2 inside the launch or as a launch behind it), cflow
+ * (packed score-only couples) or the band kernel (one banded pair, exact or
+ * in chunks with the exact launch as fallback).  Running the plan stages the
+ * column codes, launches that family and a tiny per-pair reduction on
+ * `stream` (no allocation, no host sync inside msa_plan_run).  Inputs are
+ * uint8 codes in [0,8) already in device memory (see msa_encode_pair for the
+ * host-side code map); the
  * Smith-Waterman algorithms reserve code 7 (out-of-matrix sentinel), so their
  * inputs use codes 0..6. */
 typedef enum msa_alg_e {
