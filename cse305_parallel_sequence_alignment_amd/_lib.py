@@ -104,6 +104,7 @@ def lib() -> C.CDLL:
     L.msa_plan_error.argtypes = [P, C.POINTER(C.c_int), P]
     L.msa_plan_run_info.argtypes = [P, P, P]
     L.msa_plan_launch_info.argtypes = [P, P]
+    L.msa_plan_format_info.argtypes = [P, P]
     L.msa_plan_clear_error.argtypes = [P, P]
     L.msa_plan_scores.argtypes = [P, P, P]
     L.msa_plan_stripe_meta.argtypes = [P, P, i64, P]
@@ -140,6 +141,7 @@ EXPORTED = [
     "msa_partial_partition", "msa_partial_tables", "msa_partition_tables", "msa_plan_create", "msa_plan_destroy", "msa_plan_cells_size",
     "msa_plan_run", "msa_plan_results", "msa_plan_error", "msa_plan_run_info", "msa_plan_clear_error", "msa_plan_scores",
     "msa_plan_stripe_meta", "msa_plan_stripes", "msa_plan_pair_layout", "msa_plan_launch_info",
+    "msa_plan_format_info",
     "msa_plan_checksum", "msa_plan_traceback", "msa_plan_traceback_gotoh",
     "msa_plan_last_kernel_ms", "msa_plan_set_timing", "msa_encode_pair", "msa_sw_align",
 ]

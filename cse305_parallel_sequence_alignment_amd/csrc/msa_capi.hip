@@ -771,6 +771,16 @@ int msa_plan_launch_info(const msa_plan* P, int32_t* out8) {
   return MSA_OK;
 }
 
+int msa_plan_format_info(const msa_plan* P, int32_t* out4) {
+  if (!P || !out4) return MSA_ERR_ARG;
+  const int alg = P->main.kp.alg;
+  out4[0] = alg == MSA_ALG_SWLP ? 1 : (alg == MSA_ALG_REF1 ? 2 : 0);
+  out4[1] = P->tp;
+  out4[2] = P->h16 ? 1 : 0;
+  out4[3] = 0;
+  return MSA_OK;
+}
+
 int msa_plan_error(msa_plan* P, int* code, void* stream) {
   if (!P || !code) return MSA_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;

@@ -772,8 +772,16 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
       int cD[2] = {0, 0};
       bool cok[2] = {false, false};
       if constexpr (LDSCODE) {
-        // prologue: everything phases 0 and 1 read, synchronously
-        const int lo0 = s0.cs - 63 - 4;
+        // prologue: everything phases 0 and 1 read, synchronously -- and, below that, the virtual columns a later
+        // stripe of the item starts on: its lane 63 reads column cs - 63 at step 0, and its cs lies up to 15 below the
+        // first stripe's (stripe_geom's lead).  The phases after the prologue only stage upwards, so columns left
+        // unstaged here were read as whatever the ring held: a stale code equal to the row's scored a match in a
+        // virtual cell, which reached column 1 whenever match > ~68 gaps (SW kernels: their head phases rely on
+        // the virtual score, not on a mask).  The slots stay valid until the window has moved MSA_CRING columns on,
+        // long after the item's last stripe has started.
+        int cs_min = s0.cs;
+        for (int k = 1; k < ns; ++k) cs_min = min(cs_min, sched[k].cs);
+        const int lo0 = uni(cs_min) - 63 - 4;
         const int hi1 = max(need_hi(0), need_hi(1));
         int dlo, dhi;
         drange(lo0 - 1, hi1, dlo, dhi);

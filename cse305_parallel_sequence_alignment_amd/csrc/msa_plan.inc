@@ -72,6 +72,7 @@ struct msa_plan {
                  // once unless a chunk failed to converge (rank convergence, msa_kernels.hip)
   Launch fill;   // flow, long pairs: pass 2 as a launch of its own behind pass 1 (flow_fill_kernel)
   int nc = 1;
+  int tp = 0;  // end-cell tracking (choose_algorithm): 0 none, 1 compare-select, 2 packed (value, step) key
   int KS = MSA_KS_BATCH;    // DP steps per phase
   std::vector<msa_pair_desc> pairs;
   int64_t total_stripes = 0, cells_elems = 0;
@@ -286,9 +287,18 @@ PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp) {
     // Gotoh: profile bytes 4 (f + 2g) <= 127; the shifted tagged values 4 (T + g(i+j)) stay far
     // inside int32 (REF1's own bound covers the shift: |T| + g(i+j) <= (g+h+1) span)
     const bool got_ok = kalg == MSA_ALG_REF1 && out_mode == MSA_OUT_DIR && 4 * (1 + 2 * desc->gap_extend) <= 127;
+    // SW linear with a negative score (MSA_ALG_SWL) runs the flow kernels in X-space (X = H - g under the zero floor,
+    // msa_flow.hip): fl_profile's bytes are score + g there, not the score + 2g of G-space that check_ranges admits
+    // down to -128.  The top is covered (score + g <= score + 2g <= 127, g >= 0); the bottom needs min(match,
+    // mismatch) + g >= -128 of its own.  One below it the byte wraps: mismatch -130 with g = 1 (-129) ran as +127 and
+    // an all-mismatch 65 x 70 pair scored 8,190 instead of 0.  Such a pair runs the stripe kernel, whose G-space byte
+    // (-128) fits.  Scores >= 0 (MSA_ALG_SWL0) run in G-space in both kernels.
+    const bool lin_ok = kalg == MSA_ALG_SWL0 ||
+                        (kalg == MSA_ALG_SWL && std::min(desc->match, desc->mismatch) + desc->gap_extend >= -128);
     bool whole;
-    if (((kalg == MSA_ALG_SWL || kalg == MSA_ALG_SWL0) ? (out_mode == MSA_OUT_H || (out_mode == MSA_OUT_NONE && !tp))
-                                                       : (aff_ok || got_ok)) &&
+    if (((kalg == MSA_ALG_SWL || kalg == MSA_ALG_SWL0)
+             ? (lin_ok && (out_mode == MSA_OUT_H || (out_mode == MSA_OUT_NONE && !tp)))
+             : (aff_ok || got_ok)) &&
         flow_lds_bytes(desc, is_affine_flow(kalg), &whole) <= device_lds_max())
       return PM_FLOW;
     // A banded pair has only ~(2*band+64)/(64*lag) stripes in flight at once: band_kernel's chains of
@@ -699,6 +709,7 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** out) {
   P->d.single = desc->single ? 1 : 0;
   int kalg, tp;
   if ((rc = choose_algorithm(desc, kalg, tp)) != MSA_OK) return rc;
+  P->tp = tp;
   if (desc->single && desc->n_pairs != 1) return MSA_ERR_ARG;
   // (alg, cells, tracking) combinations no kernel computes: every family takes a subset of the stripe kernel's
   if (!pick_kernel(kalg, desc->cells, tp, desc->single != 0)) return MSA_ERR_UNSUPPORTED;

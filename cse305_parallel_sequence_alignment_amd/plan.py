@@ -146,6 +146,15 @@ class Plan:
         return dict(mode=modes[v[0]], grid=int(v[1]), threads=int(v[2]), lds_bytes=int(v[3]), nflow=int(v[4]),
                     fill_grid=int(v[5]), rows_per_lane=int(v[6]), items=int(v[7]))
 
+    def format_info(self) -> dict:
+        """The number formats the plan chose (msa_plan_format_info): values ("int32", "packed16" couples or
+        "tagged4" Gotoh), end-cell tracking ("none", "select" or the packed "key"), and whether the chunks of a
+        chunked banded plan write int16 cells."""
+        v = (C.c_int32 * 4)()
+        LB.check(LB.lib().msa_plan_format_info(self._h, v), "msa_plan_format_info")
+        return dict(values={0: "int32", 1: "packed16", 2: "tagged4"}[v[0]],
+                    tracking={0: "none", 1: "select", 2: "key"}[v[1]], int16_cells=int(v[2]))
+
     def clear_error(self, stream=None) -> None:
         LB.check(LB.lib().msa_plan_clear_error(self._h, _stream_ptr(stream)), "msa_plan_clear_error")
 

@@ -271,6 +271,12 @@ int msa_plan_run_info(msa_plan* plan, int32_t* out4, void* stream);
  * launch (flow_fill_kernel, long pairs; 0 = pass 2 runs inside the main launch); rows per lane;
  * items}. */
 int msa_plan_launch_info(const msa_plan* plan, int32_t* out8);
+/* The number formats the plan chose (read-only; for tests and tools): out4 = {value format: 0 int32, 1 packed
+ * int16 couples (two score-only SW-linear pairs per lane), 2 the x4 tagged values of the reference's Gotoh
+ * (start type -1); end-cell tracking: 0 none, 1 compare-select on (value, position), 2 the first maximum's
+ * step packed with the value into one int; 1 if the chunks of a chunked banded plan write int16 cells;
+ * 0 (reserved)}. */
+int msa_plan_format_info(const msa_plan* plan, int32_t* out4);
 /* The sticky error word (0 = no error; else the kernel site code), synchronizes. */
 int msa_plan_error(msa_plan* plan, int* code, void* stream);
 /* Reset the sticky error word (stream-ordered). */
