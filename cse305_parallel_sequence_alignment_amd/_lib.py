@@ -24,7 +24,7 @@ STATUS = {
 }
 
 # msa_alg_e / msa_out_e
-SW_LINEAR, SW_AFFINE, NW_BANDED, REF_GOTOH, PARTIAL = 0, 1, 2, 3, 4
+SW_LINEAR, SW_AFFINE, NW_BANDED, REF_GOTOH, PARTIAL, NW_ALIGN = 0, 1, 2, 3, 4, 5
 CELLS_NONE, CELLS_H, CELLS_DIR, CELLS_TAB = 0, 1, 2, 3
 
 
@@ -114,11 +114,13 @@ def lib() -> C.CDLL:
     L.msa_plan_checksum.argtypes = [P, P, i64, C.POINTER(u64), P]
     L.msa_plan_traceback.argtypes = [P, i64, P, P, i64, P, P]
     L.msa_plan_traceback_gotoh.argtypes = [P, i64, C.c_int, P, P, i64, P, P]
+    L.msa_plan_traceback_nw.argtypes = [P, i64, P, P, i64, P, P]
     L.msa_plan_last_kernel_ms.argtypes = [P, C.POINTER(C.c_float)]
     L.msa_plan_set_timing.argtypes = [P, i32]
     L.msa_encode_pair.argtypes = [P, sz, P, sz, P, P]
     L.msa_sw_align.argtypes = [P, sz, P, sz, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64),
                                C.POINTER(i64), C.POINTER(i64), P, sz]
+    L.msa_nw_align.argtypes = [P, sz, P, sz, i32, i32, i64, C.POINTER(i32), P, sz]
     _lib = L.lib
     return _lib
 
@@ -142,6 +144,6 @@ EXPORTED = [
     "msa_plan_run", "msa_plan_results", "msa_plan_error", "msa_plan_run_info", "msa_plan_clear_error", "msa_plan_scores",
     "msa_plan_stripe_meta", "msa_plan_stripes", "msa_plan_pair_layout", "msa_plan_launch_info",
     "msa_plan_format_info",
-    "msa_plan_checksum", "msa_plan_traceback", "msa_plan_traceback_gotoh",
-    "msa_plan_last_kernel_ms", "msa_plan_set_timing", "msa_encode_pair", "msa_sw_align",
+    "msa_plan_checksum", "msa_plan_traceback", "msa_plan_traceback_gotoh", "msa_plan_traceback_nw",
+    "msa_plan_last_kernel_ms", "msa_plan_set_timing", "msa_encode_pair", "msa_sw_align", "msa_nw_align",
 ]

@@ -280,3 +280,22 @@ def sw_align(A, B, match=1, mismatch=0, gap_open=1, gap_extend=1, traceback=True
         r["beg"] = (bi.value, bj.value)
         r["cigar"] = cig.value.decode()
     return r
+
+
+def nw_align(A, B, gap_open=3, gap_extend=1, band=-1, traceback=True):
+    """Global (Gotoh) alignment (build extension) -> dict(score, cigar).
+
+    +1 on equal symbols, 0 otherwise; a gap of L costs (gap_open - gap_extend) + gap_extend * L.  ``band`` >= 0
+    restricts the alignment to |i - j| <= band (-1: none).  The fill writes one direction byte per in-band cell,
+    the walk runs on the device, and the CIGAR (start -> end, I consumes A, D consumes B) consumes all of A and
+    B.  ``traceback=False`` returns the score only."""
+    A, B = _buf(A), _buf(B)
+    sc = C.c_int32()
+    cap = 4 * (len(A) + len(B)) + 16
+    cig = C.create_string_buffer(cap) if traceback else None
+    LB.check(LB.lib().msa_nw_align(A, len(A), B, len(B), gap_open, gap_extend, band, C.byref(sc), cig,
+                                   cap if traceback else 0), "msa_nw_align")
+    r = dict(score=sc.value)
+    if traceback:
+        r["cigar"] = cig.value.decode()
+    return r

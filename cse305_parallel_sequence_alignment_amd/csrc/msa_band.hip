@@ -31,6 +31,12 @@
 // from a guessed row; its items (kp.groups slots) chain through granules, its warm-up stripes
 // write no cells, and the io wave saves the warm-up's last row and the chunk's last row into the
 // checkpoint buffer for chunk_check_kernel / chunk_add_kernel.
+// band_kernel<true> (MSA_NW_ALIGN plans) writes one direction byte per cell instead of H, in the SW-affine
+// format msa_traceback.hip walks: bits 0-1 = 1 / 2 / 3 for H from the diagonal / E / F (first of them equal to
+// H), bit 2 = E opened from H(i, j-1), bit 3 = F opened from H(i-1, j) (a tie with the extension opens).  The
+// shift g(i+j) is the same on both sides of each comparison, so the ties are the unshifted recurrence's; a chunk's
+// constant does not change them either, so chunked mode needs no add pass.  A lane's 16 bytes of a phase are one
+// 16-byte store: a wave's phase is one 1 KiB block of the DIR layout.
 #pragma once
 
 namespace msa {
@@ -78,6 +84,7 @@ __host__ __device__ inline size_t bk_lds_bytes(int code_bytes) {
   return (size_t)(FL_FLAGS + BK_LINKS * 512) * 4 + (size_t)BK_NCOPY * code_bytes;
 }
 
+template <bool DIRK>  // cells: false int32 / int16 H (or none), true direction bytes
 __global__ __launch_bounds__((BK_W + 1) * 64) void band_kernel(KArgs a) {
   extern __shared__ __attribute__((aligned(16))) int smem[];
   const msa_kparams& kp = a.kp;
@@ -301,7 +308,7 @@ __global__ __launch_bounds__((BK_W + 1) * 64) void band_kernel(KArgs a) {
       const unsigned a_cons = lds_addr(last ? flags + 64 : flags + 33 + w + 1);
       int* const prog_me = flags + 33 + w;
       const unsigned a_prog_me = lds_addr(prog_me);
-      const bool outp = (k >= ks0) && (a.outH != nullptr);
+      const bool outp = (k >= ks0) && (DIRK ? a.outDir != nullptr : a.outH != nullptr);
       int32_t* const orow = a.outH + pd.out_off + (size_t)k * pd.pmax * MSA_K * 64 + 4 * lane;
       // chunked, chunk >= 1, int16 chunk cells (msa_plan_create): H relative to the guessed row, 2 B per
       // cell, widened by chunk_add_kernel
@@ -309,6 +316,9 @@ __global__ __launch_bounds__((BK_W + 1) * 64) void band_kernel(KArgs a) {
       // (MSA_H16_PAIRED: a lane's cells of u-blocks 2h and 2h+1 side by side, one 16-B store per two
       // u-blocks; chunk_add_kernel undoes the pairing)
       int16_t* const orow16 = a.outH16 + (size_t)(k - C) * pd.pmax * MSA_K * 64 + (MSA_H16_PAIRED ? 8 : 4) * lane;
+      // direction bytes: block q of the stripe is the phase's 1 KiB, 16 B per lane
+      uint8_t* odir = nullptr;
+      if constexpr (DIRK) odir = a.outDir + pd.out_off + (size_t)k * pd.pmax * MSA_K * 64 + 16 * lane;
       unsigned plo, phi;
       {
         const int sm = 1 + 2 * g + hh, sx = 2 * g + hh;  // f + 2g + h, f = 1 on a match
@@ -409,7 +419,8 @@ __global__ __launch_bounds__((BK_W + 1) * 64) void band_kernel(KArgs a) {
       auto run_phase = [&](const int q, fl_v4i (&Zi)[4], fl_v4i (&Fi)[4], fl_v2u& Cl, fl_v2u& Ch, fl_v4i (&Zn)[4],
                            fl_v4i (&Fn)[4], fl_v2u& Cln, fl_v2u& Chn, auto MODE_, auto OUT_) __attribute__((always_inline)) {
         constexpr int MODE = decltype(MODE_)::value;
-        constexpr int OUT = decltype(OUT_)::value;  // 0: no cells (warm-up), 1: int32 cells, 2: int16 chunk cells
+        // 0: no cells (warm-up), 1: int32 cells, 2: int16 chunk cells, 3: direction bytes
+        constexpr int OUT = decltype(OUT_)::value;
         const int need = Bin < 0 ? 0 : min(q + 1, Bin + 1) + dq_in;
         if (pubv < need) {
           wait_flag(need);
@@ -420,12 +431,14 @@ __global__ __launch_bounds__((BK_W + 1) * 64) void band_kernel(KArgs a) {
         }
         int xz[16], xf[16], ho[16];
         fl_v2u h16lo = {0u, 0u};
+        unsigned dirw[4] = {0u, 0u, 0u, 0u};
         int pubn = 0;
         const int ctq = ct0 - 16 * g * q;
         const unsigned cw[4] = {Cl.x, Cl.y, Ch.x, Ch.y};
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
+          unsigned dacc = 0;  // the u-block's four direction bytes, the first cell's in the top byte
 #pragma unroll
           for (int kk = 0; kk < 4; ++kk) {
             const int kx = 4 * u + kk;
@@ -437,6 +450,15 @@ __global__ __launch_bounds__((BK_W + 1) * 64) void band_kernel(KArgs a) {
             int en = imax(Z, E);
             int h = imax3(U + sc, en, fn);
             asm("" : "+v"(h));
+            if constexpr (OUT == 3) {
+              // byte = 3 + 8 [F opened] + 4 [E opened] - [H is the diagonal or E] - [H is the diagonal]: four
+              // compares into scalar masks; two selects (3 / 11, 0 / 4) joined with the shifted word by one
+              // v_or3, the two "H is ..." masks taken off by a select and a v_subb (ten VALU per cell, scheduled
+              // behind the phase's DP chain)
+              const int m1 = (h == U + sc) ? 1 : 0;
+              const int m2 = (h == en) ? 1 : m1;
+              dacc = (dacc << 8) + (zu >= fu ? 11u : 3u) + (Z >= E ? 4u : 0u) - (unsigned)m2 - (unsigned)m1;
+            }
             int zn = h - hh;
             if constexpr ((MODE & 1) != 0) {
               const bool fl = (16 * q + kx == tmin - 1);  // the left neighbour of the row's first cell
@@ -464,8 +486,14 @@ __global__ __launch_bounds__((BK_W + 1) * 64) void band_kernel(KArgs a) {
             xf[kx] = fn;
             ho[kx] = zn + (ctq - g * kx);
           }
+          if constexpr (OUT == 3) dirw[u] = __builtin_amdgcn_perm(0u, dacc, 0x00010203u);  // first cell -> byte 0
 #ifndef BK_NOSTORE
-          if constexpr (OUT != 0) {
+          if constexpr (OUT == 3) {
+            if (u == 3) {
+              const fl_v4u dv = {dirw[0], dirw[1], dirw[2], dirw[3]};
+              __builtin_nontemporal_store(dv, reinterpret_cast<fl_v4u*>(odir + (size_t)q * 1024));
+            }
+          } else if constexpr (OUT != 0) {
             if constexpr (OUT == 2) {
               const fl_v2u hv = {__builtin_amdgcn_perm((unsigned)ho[4 * u + 1], (unsigned)ho[4 * u], 0x05040100u),
                                  __builtin_amdgcn_perm((unsigned)ho[4 * u + 3], (unsigned)ho[4 * u + 2], 0x05040100u)};
@@ -538,9 +566,14 @@ __global__ __launch_bounds__((BK_W + 1) * 64) void band_kernel(KArgs a) {
         run_range(qc, Pe, M2_{}, O_);
         if (P & 1) run_phase(P - 1, ZA, FA, CAl, CAh, ZB, FB, CBl, CBh, M3_{}, O_);
       };
-      if (!outp) run_all(std::integral_constant<int, 0>{});
-      else if (o16) run_all(std::integral_constant<int, 2>{});
-      else run_all(std::integral_constant<int, 1>{});
+      if constexpr (DIRK) {
+        if (!outp) run_all(std::integral_constant<int, 0>{});
+        else run_all(std::integral_constant<int, 3>{});
+      } else {
+        if (!outp) run_all(std::integral_constant<int, 0>{});
+        else if (o16) run_all(std::integral_constant<int, 2>{});
+        else run_all(std::integral_constant<int, 1>{});
+      }
       lgkm_drain();
       if (k >= ks0 && lane == 0) {
         msa_stripe_meta* md = a.meta + pd.stripe0 + k;

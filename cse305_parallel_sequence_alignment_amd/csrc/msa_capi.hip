@@ -445,6 +445,8 @@ kfn_t pick_kernel(int alg, int out, int tp, bool sgl) {
     case MSA_ALG_NWA:
       if (out == MSA_OUT_NONE) return kf<MSA_ALG_NWA, MSA_OUT_NONE, 0>(sgl);
       if (out == MSA_OUT_H) return kf<MSA_ALG_NWA, MSA_OUT_H, 0>(sgl);
+      // (direction bytes: MSA_NW_ALIGN plans only -- msa_plan_create keeps (MSA_NW_BANDED, DIR) unsupported)
+      if (out == MSA_OUT_DIR) return kf<MSA_ALG_NWA, MSA_OUT_DIR, 0>(sgl);
       break;
     case MSA_ALG_REF:
       if (out == MSA_OUT_NONE) return kf<MSA_ALG_REF, MSA_OUT_NONE, 0>(sgl);
@@ -847,6 +849,20 @@ int msa_plan_traceback_gotoh(msa_plan* P, int64_t pair, int end_type, const uint
                                                : traceback_kernel<TB_REF>, dim3(1),
                      dim3(384), 0, st, dDir, P->d_pairs, P->d_meta, (const PairResult*)P->d_res, (int)pair, end_type,
                      (int)P->main.kp.h, d_ops, (long long)ops_cap, (long long*)d_info, P->mode == PM_FLOW ? 1 : 0,
+                     (const unsigned long long*)nullptr);
+  HIPCHK(hipGetLastError());
+  return MSA_OK;
+}
+
+int msa_plan_traceback_nw(msa_plan* P, int64_t pair, const uint8_t* dDir, uint8_t* d_ops, int64_t ops_cap,
+                          int64_t* d_info, void* stream) {
+  if (!P || !dDir || !d_ops || !d_info || ops_cap < 0 || pair < 0 || pair >= P->d.n_pairs) return MSA_ERR_ARG;
+  if (P->d.alg != MSA_NW_ALIGN) return MSA_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  P->note_stream(st);
+  // stripe starts from the stripe meta (band geometry); the walk needs no end type and no PairResult
+  hipLaunchKernelGGL(traceback_kernel<TB_NW>, dim3(1), dim3(384), 0, st, dDir, P->d_pairs, P->d_meta,
+                     (const PairResult*)P->d_res, (int)pair, 0, 0, d_ops, (long long)ops_cap, (long long*)d_info, 0,
                      (const unsigned long long*)nullptr);
   HIPCHK(hipGetLastError());
   return MSA_OK;

@@ -375,6 +375,14 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
     const int t2 = imax(L.S[0] - kp.gap_open, L.S[1] - kp.gap_ext);
     const int t1 = L.U[0] + s;
     nS[0] = imax3(t1, t2, t3);
+    if constexpr (OUT == MSA_OUT_DIR) {
+      // MSA_NW_ALIGN: the SW-affine byte (msa_traceback.hip) without the local start; ties go to
+      // the diagonal, then E, and to "open" in E and F
+      const unsigned hs = (nS[0] == t1) ? 1u : (nS[0] == t2 ? 2u : 3u);
+      const unsigned eb = (t2 == L.S[0] - kp.gap_open) ? 4u : 0u;
+      const unsigned fb = (t3 == upH - kp.gap_open) ? 8u : 0u;
+      dir = hs | eb | fb;
+    }
     nS[1] = t2;
     nS[2] = t3;
     L.U[0] = upH;

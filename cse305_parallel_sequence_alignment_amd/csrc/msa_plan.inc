@@ -169,6 +169,14 @@ int choose_algorithm(const msa_plan_desc* desc, int& kalg, int& tp) {
       break;
     case MSA_SW_AFFINE: kalg = MSA_ALG_SWA; break;
     case MSA_NW_BANDED: kalg = MSA_ALG_NWA; break;
+    case MSA_NW_ALIGN:
+      // MSA_NW_BANDED's recurrence with one direction byte per cell, walked by msa_plan_traceback_nw: direction
+      // bytes only, the reference's scores (f = 1 / 0; general scores are left for later) and gaps with g, h >= 0
+      kalg = MSA_ALG_NWA;
+      if (out_mode != MSA_OUT_DIR || desc->match != 1 || desc->mismatch != 0 || desc->gap_extend < 0 ||
+          desc->gap_open < desc->gap_extend)
+        return MSA_ERR_UNSUPPORTED;
+      break;
     case MSA_REF_GOTOH: {
       // start type -1 (main_alignment_function's single subproblem) with direction bytes or no
       // cells: the tagged-max form (every interior value is finite; values carried x4)
@@ -303,12 +311,15 @@ PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp) {
       return PM_FLOW;
     // A banded pair has only ~(2*band+64)/(64*lag) stripes in flight at once: band_kernel's chains of
     // 4-stripe items, as long as its code rows fit LDS; chunked from 4 chunks up, when cells are written
-    if (kalg == MSA_ALG_NWA && band >= 0 && (out_mode == MSA_OUT_H || out_mode == MSA_OUT_NONE)) {
+    // (direction bytes: MSA_NW_ALIGN, chunked like H -- a chunk's bytes do not depend on its constant)
+    if (kalg == MSA_ALG_NWA && band >= 0) {
       const int S = stripes_of(desc->m[0]);
       if (bk_lds_bytes(bk_code_bytes((int)desc->m[0], (int)desc->n[0], band)) <= device_lds_max()) {
-        const bool chunks = (S + band_chunk() - 1) / band_chunk() >= 4 && out_mode == MSA_OUT_H && band_warm() >= BK_W;
+        const bool chunks = (S + band_chunk() - 1) / band_chunk() >= 4 && out_mode != MSA_OUT_NONE && band_warm() >= BK_W;
         return chunks ? PM_BAND_CHUNKED : PM_BAND;
       }
+      // direction bytes never take the chunked stripe launch (its chunks write int32 cells): the exact stripe launch
+      if (out_mode == MSA_OUT_DIR) return PM_STRIPE;
       // else the stripe kernel: one workgroup per chunk of >= MSA_CHUNK_MIN stripes, from 4 chunks up
       const int cc = std::max(MSA_CHUNK_MIN, (S + device_cus() - 1) / device_cus());
       return (S + cc - 1) / cc >= 4 ? PM_CHUNKED : PM_STRIPE;
@@ -331,7 +342,8 @@ PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp) {
   // 4k, packed couples, ms): 64 couples 1.72 -> 0.80, 128: 1.39, 256: 2.38.
   bool eq_m = true;
   for (int64_t p = 1; p < desc->n_pairs; ++p) eq_m = eq_m && desc->m[p] == desc->m[0];
-  if (eq_m && batch_items(desc, kalg) < slots && stripes_of(desc->m[0]) >= 2 * MSA_WAVES_BATCH && band < 0)
+  if (eq_m && batch_items(desc, kalg) < slots && stripes_of(desc->m[0]) >= 2 * MSA_WAVES_BATCH && band < 0 &&
+      desc->alg != MSA_NW_ALIGN)  // (a batch of global alignments with direction bytes: whole pairs per workgroup)
     return PM_SPLIT;
   return PM_STRIPE;
 }
@@ -587,7 +599,8 @@ int shape_band(msa_plan& P, const msa_plan_desc* desc) {
   msa_kparams& kp = l.kp;
   const int m0 = (int)desc->m[0], n0 = (int)desc->n[0], band = kp.band;
   const int S = stripes_of(m0), ncu = device_cus();
-  l.fn = band_kernel;
+  // (direction bytes, MSA_NW_ALIGN: an instantiation of its own -- the value plans' code is unchanged)
+  l.fn = desc->cells == MSA_CELLS_DIR ? band_kernel<true> : band_kernel<false>;
   l.threads = (BK_W + 1) * 64;
   kp.lds_code_bytes = bk_code_bytes(m0, n0, band);
   l.lds = bk_lds_bytes(kp.lds_code_bytes);
@@ -625,7 +638,8 @@ int shape_band(msa_plan& P, const msa_plan_desc* desc) {
     // instead of reading and re-writing 4 B.  MSA_BAND_H16=0 (diagnostic, read once per process) keeps int32 cells.
     static const bool h16_on = env_int("MSA_BAND_H16", 1) != 0;
     const long long rows = (long long)(warm + cc) * 64 + 64;
-    P.h16 = h16_on && kp.h >= 0 && kp.gap_ext >= 0 && rows + kp.h + (long long)kp.gap_ext * band <= 30000;
+    P.h16 = h16_on && desc->cells == MSA_CELLS_H && kp.h >= 0 && kp.gap_ext >= 0 &&
+            rows + kp.h + (long long)kp.gap_ext * band <= 30000;
   }
   P.gslots = items > 1 ? 2 * items : 0;
   return MSA_OK;
@@ -713,6 +727,8 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** out) {
   if (desc->single && desc->n_pairs != 1) return MSA_ERR_ARG;
   // (alg, cells, tracking) combinations no kernel computes: every family takes a subset of the stripe kernel's
   if (!pick_kernel(kalg, desc->cells, tp, desc->single != 0)) return MSA_ERR_UNSUPPORTED;
+  // (direction bytes of the banded recurrence are MSA_NW_ALIGN's: their stripe kernel instantiation exists for it alone)
+  if (desc->alg == MSA_NW_BANDED && desc->cells == MSA_CELLS_DIR) return MSA_ERR_UNSUPPORTED;
   P->main.kp = base_kparams(desc, kalg);
   P->nc = nc_of(kalg);
   if (kalg == MSA_ALG_NWA && P->main.kp.h < 0) return MSA_ERR_UNSUPPORTED;

@@ -6,6 +6,7 @@
 //   msa_partial_tables    partial.cpp:13-79
 //   msa_partial_partition partial.cpp:81-163
 //   msa_sw_align          build extension (Smith-Waterman, configs C2/C5)
+//   msa_nw_align          build extension (banded global alignment with its CIGAR, config C3's recurrence)
 //
 // Every DP cell is computed on the GPU (stripe_kernel) and find_alignment's
 // walk runs there too (traceback_kernel<TB_REF_TAG>, or <TB_REF>): the host encodes the inputs,
@@ -1182,6 +1183,122 @@ int msa_sw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t mat
     if (c.size() + 1 > cigar_cap) return MSA_ERR_CAPACITY;
     std::memcpy(cigar, c.c_str(), c.size() + 1);
   }
+  return MSA_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Device footprint of one msa_nw_align call: the plan's cells (1 B per cell of the skewed band layout -- the
+// stripes' own phase counts, as lay_out_pairs sizes them -- or none for a score-only call), its granule slots (two
+// per item of 4 stripes, n + margins granules each; a chunked band plan has up to (warm-up + chunk) / 4 + 1 items
+// per chunk), the 16 code copies, the ops and the pooled size classes' slack.  A banded pair therefore reserves
+// ~(2 band + 64) B per row, not the full matrix.
+size_t footprint_nw(int64_t m, int64_t n, int band, bool dir) {
+  const int S = stripes_of(m);
+  int pmax = 0;
+  for (int k = 0; k < S; ++k) {
+    StripeGeom g;
+    stripe_geom(k, (int)m, (int)n, band, g, 16);
+    pmax = std::max(pmax, g.P);
+  }
+  const size_t cells = dir ? (size_t)S * pmax * MSA_K * 64 : 0;
+  size_t items = (size_t)(S + BK_W - 1) / BK_W;
+  if (band >= 0) {
+    const size_t nch = (size_t)(S + band_chunk() - 1) / band_chunk();
+    items = std::max(items, nch * (size_t)((band_warm() + band_chunk()) / BK_W + 1));
+  }
+  return cells + 2 * items * (size_t)(n + 2 * MSA_GOFF + 32) * sizeof(unsigned long long) + 16 * (size_t)(n + 512) +
+         3 * (size_t)(m + n) + (size_t(24) << 20);
+}
+
+}  // namespace
+
+extern "C" {
+
+int msa_nw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t gap_open, int32_t gap_extend,
+                 int64_t band_in, int32_t* score, char* cigar, size_t cigar_cap) {
+  if (!A0 || !B0 || m == 0 || n == 0 || m > (size_t(1) << 26) || n > (size_t(1) << 26) || band_in < -1)
+    return MSA_ERR_ARG;
+  if (gap_extend < 0 || gap_open < gap_extend) return MSA_ERR_UNSUPPORTED;
+  const int64_t mm = (int64_t)m, nn = (int64_t)n;
+  if (band_in >= 0 && std::llabs(mm - nn) > band_in) return MSA_ERR_ARG;
+  // (a band that holds every cell is no band)
+  const int band = (band_in < 0 || band_in >= std::max(mm, nn)) ? -1 : (int)band_in;
+  std::vector<uint8_t> ca(m), cb(n);
+  int rc = msa_encode_pair(A0, m, B0, n, ca.data(), cb.data());
+  if (rc != MSA_OK) return rc;
+  const bool want_tb = cigar != nullptr;
+  if ((rc = ensure_device()) != MSA_OK) return rc;
+  Admit adm(footprint_nw(mm, nn, band, want_tb));
+  StreamGuard sg;
+  if ((rc = sg.acquire()) != MSA_OK) return rc;
+  DevMem dA, dB, dDir, dOps, dInfo;
+  PlanGuard pg;
+  StreamSync sync{sg.s};
+  if ((rc = dA.alloc(m)) || (rc = dB.alloc(n))) return rc;
+  HIPCHK(hipMemcpyAsync(dA.p, ca.data(), m, hipMemcpyHostToDevice, sg.s));
+  HIPCHK(hipMemcpyAsync(dB.p, cb.data(), n, hipMemcpyHostToDevice, sg.s));
+  int64_t zero = 0;
+  msa_plan_desc d;
+  std::memset(&d, 0, sizeof(d));
+  // the score alone needs no direction bytes: the value plan of the same recurrence
+  d.alg = want_tb ? MSA_NW_ALIGN : MSA_NW_BANDED;
+  d.cells = want_tb ? MSA_CELLS_DIR : MSA_CELLS_NONE;
+  d.match = 1;
+  d.mismatch = 0;
+  d.gap_open = gap_open;
+  d.gap_extend = gap_extend;
+  d.start_type = -1;
+  d.band = band;
+  d.single = 1;
+  d.n_pairs = 1;
+  d.m = &mm;
+  d.n = &nn;
+  d.a_off = &zero;
+  d.b_off = &zero;
+  if ((rc = msa_plan_create(&d, &pg.p)) != MSA_OK) return rc;
+  const int64_t ops_cap = mm + nn + 2;
+  if (want_tb) {
+    int64_t elems = 0;
+    msa_plan_cells_size(pg.p, &elems);
+    if ((rc = dDir.alloc((size_t)elems)) || (rc = dOps.alloc((size_t)ops_cap)) || (rc = dInfo.alloc(64))) return rc;
+  }
+  if ((rc = msa_plan_run(pg.p, (const uint8_t*)dA.p, (const uint8_t*)dB.p, dDir.p, nullptr, nullptr, sg.s)))
+    return rc;
+  // the walk on the device: only the ops come back, not the band's bytes
+  if (want_tb &&
+      (rc = msa_plan_traceback_nw(pg.p, 0, (const uint8_t*)dDir.p, (uint8_t*)dOps.p, ops_cap, (int64_t*)dInfo.p, sg.s)))
+    return rc;
+  msa_pair_result res;
+  if ((rc = msa_plan_results(pg.p, &res, sg.s)) != MSA_OK) return rc;
+  if (score) *score = res.score;
+  if (!want_tb) return MSA_OK;
+  int64_t info[4];
+  HIPCHK(hipMemcpyAsync(info, dInfo.p, sizeof(info), hipMemcpyDeviceToHost, sg.s));
+  HIPCHK(hipStreamSynchronize(sg.s));
+  if (info[3] != 0) return (int)info[3];
+  std::vector<char> ops((size_t)info[0]);
+  if (info[0] > 0) {
+    HIPCHK(hipMemcpyAsync(ops.data(), dOps.p, (size_t)info[0], hipMemcpyDeviceToHost, sg.s));
+    HIPCHK(hipStreamSynchronize(sg.s));
+  }
+  // the walk stopped on the matrix border at (i, j): the rest is one gap along it
+  const int64_t bi = info[1] - 1, bj = info[2] - 1;
+  if (bi > 0) ops.insert(ops.end(), (size_t)bi, 'I');
+  else if (bj > 0) ops.insert(ops.end(), (size_t)bj, 'D');
+  // ops run from (m, n) back to (0, 0): run-length encode them reversed
+  std::string c;
+  for (int64_t k = (int64_t)ops.size() - 1; k >= 0;) {
+    const char op = ops[(size_t)k];
+    int64_t run = 0;
+    while (k >= 0 && ops[(size_t)k] == op) { run++; k--; }
+    c += std::to_string(run);
+    c.push_back(op);
+  }
+  if (c.size() + 1 > cigar_cap) return MSA_ERR_CAPACITY;
+  std::memcpy(cigar, c.c_str(), c.size() + 1);
   return MSA_OK;
 }
 

@@ -16,6 +16,11 @@
 //    step leaves from ('M' T1 / diagonal, 'D' T2 / consumes B, 'I' T3 / consumes
 //    A); the host turns them into the reference's align list (node coordinates,
 //    quirks Q1/Q2).
+//  * Global Gotoh (MSA_NW_ALIGN plans: band_kernel<true> or stripe_kernel<MSA_ALG_NWA, MSA_OUT_DIR>): the
+//    SW-affine byte, whose low bits are never 0 on an in-band interior cell.  The walk (TB_NW) uses the SW
+//    transitions, starts at (m, n) in state H and stops at the matrix border like the reference's walk; the
+//    caller completes the border gap.  A band changes nothing here: every stripe's start column comes from
+//    the stripe meta, and the bytes of a correct fill never lead out of the band.
 //
 // Both layouts are the skewed stripe layout: cell (64s + r + 1, cs_s + t - r) at
 // byte (s*pmax + t/16)*1024 + r*16 + t%16 of the pair's block -- a 16-step x
@@ -127,8 +132,8 @@ __device__ __forceinline__ int ref_end_state(const int32_t (&fin)[3], int end_ty
 }
 
 // Walk kinds: Smith-Waterman affine; the reference's Gotoh walk over table numbers (REF
-// fill) or over tags (REF1 fill, tag = 4 - table).
-enum { TB_SW = 0, TB_REF = 1, TB_REF_TAG = 2 };
+// fill) or over tags (REF1 fill, tag = 4 - table); the global walk over SW-affine bytes (MSA_NW_ALIGN).
+enum { TB_SW = 0, TB_REF = 1, TB_REF_TAG = 2, TB_NW = 3 };
 
 // The transition word of a cell (see the window comment in traceback_kernel): three 10-bit
 // fields, field s (bits 10s..) = 10 x the next state (30 = stop) | the lane step of leaving
@@ -152,7 +157,7 @@ __device__ __forceinline__ unsigned tb_word(unsigned dv) {
     // table numbers x = 1..3 (0: no predecessor): next state 10 (x - 1), or 30
     auto fld = [](unsigned step, unsigned x) { return (x ? 10u * (x - 1u) : 30u) | (step << 6); };
     return fld(9u, dv & 3u) | (fld(1u, (dv >> 2) & 3u) << 10) | (fld(8u, (dv >> 4) & 3u) << 20) | (1u << 31);
-  } else {
+  } else {  // TB_SW, TB_NW
     const unsigned fH = (unsigned)(TB_FH >> (16 * (dv & 3u))) & 0x3ffu;
     const unsigned fE = (1u << 6) | ((dv & 4u) ? 0u : 10u);
     const unsigned fF = (8u << 6) | ((dv & 8u) ? 0u : 20u);
@@ -205,7 +210,8 @@ __device__ __forceinline__ unsigned long long tb_u64(unsigned long long& x) {
 constexpr int TB_SPIN_MAX = 1 << 24;
 
 // KIND TB_SW: Smith-Waterman affine walk; TB_REF / TB_REF_TAG: the reference's Gotoh walk
-// (end_type, h: find_alignment's end rule).  RL = rows per lane of the layout: 1, or 2 for the
+// (end_type, h: find_alignment's end rule); TB_NW: the SW words from (m, n) in state H to the matrix
+// border (low bits 0 -- no predecessor, never written by a complete fill -- end it with MSA_ERR_NOMATCH).  RL = rows per lane of the layout: 1, or 2 for the
 // two-rows-per-lane Gotoh flow fill (128-row stripes, lane r holds rows 2r+1 and 2r+2 at column
 // cs + t - r; a 16-step block is 2 KiB: the row-1 segments, then the row-2 segments).
 //
@@ -227,7 +233,7 @@ __global__ __launch_bounds__(384) void traceback_kernel(const uint8_t* __restric
                                                         int hpen, uint8_t* __restrict__ ops, long long cap,
                                                         long long* __restrict__ info, int csflow,
                                                         const unsigned long long* __restrict__ best_key) {
-  constexpr bool REF = KIND != TB_SW;
+  constexpr bool REF = KIND != TB_SW;  // a global walk: from (m, n) to the matrix border
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const msa_pair_desc pd = pairs[pair];
   const uint8_t* base = dir + pd.out_off + lane * 16;
@@ -487,7 +493,7 @@ __global__ __launch_bounds__(384) void traceback_kernel(const uint8_t* __restric
     j = REF ? pd.n : (int)r0.end_j;
     // SW: 0 in H, 1 in E (horizontal gap), 2 in F (vertical gap); REF: 0, 1, 2 = T1, T2, T3
     int st = 0;
-    if constexpr (REF) st = ref_end_state(r0.fin, end_type, hpen);
+    if constexpr (REF && KIND != TB_NW) st = ref_end_state(r0.fin, end_type, hpen);
     int nw = 0, rseq = 0, eseq = 0;
     auto record = [&](unsigned w) __attribute__((always_inline)) {
       if ((nw & (TB_RAW / 2 - 1)) == 0 && nw >= TB_RAW) {

@@ -7,6 +7,8 @@ Skewed stripe layout of per-cell outputs (H / DIR / TAB planes), per pair:
 stripe s (rows 64s+1..64s+64) owns ``pmax*16*64`` elements; element
 ``((s*pmax*4 + t//4)*64 + r)*4 + t%4`` (DIR: ``(s*pmax + t//16)*1024 + r*16 + t%16``)
 holds cell ``(i, j) = (64s + r + 1, cs_s + t - r)``, cs_s from the stripe meta.
+A banded plan (NW_BANDED H cells, NW_ALIGN direction bytes) uses the same layout with the band's
+own stripe starts and phase counts: ``S*pmax*1024`` elements per pair, about ``2*band + 64`` per row.
 """
 from __future__ import annotations
 
@@ -236,6 +238,44 @@ class Plan:
         inf = info.cpu().tolist()
         LB.check(int(inf[3]), "msa_plan_traceback_gotoh")
         return dict(ops=bytes(ops[:inf[0]].cpu().numpy().tobytes()), stop=(int(inf[1]) - 1, int(inf[2]) - 1))
+
+    def traceback_nw_async(self, dDir, d_ops, d_info, pair=0, stream=None) -> None:
+        """Device walk of a global alignment (msa_plan_traceback_nw) over an NW_ALIGN plan's direction bytes,
+        stream-ordered after run(): d_ops (uint8, its size is the capacity; m+n suffices) receives the ops end ->
+        start ('M' diagonal, 'D' consumes B, 'I' consumes A) up to the matrix border, d_info (int64[8]) {n_ops,
+        i+1, j+1, status, ...} with (i, j) the border cell where the walk stopped."""
+        import torch
+
+        if not (dDir.is_cuda and dDir.dtype == torch.uint8 and dDir.numel() >= self.cells_elems):
+            raise ValueError("dDir must be the uint8 CUDA tensor the plan's run() wrote")
+        if not (d_ops.is_cuda and d_ops.dtype == torch.uint8 and d_ops.is_contiguous()):
+            raise ValueError("d_ops must be a contiguous uint8 CUDA tensor")
+        if not (d_info.is_cuda and d_info.dtype == torch.int64 and d_info.numel() >= 8):
+            raise ValueError("d_info must be an int64 CUDA tensor of >= 8 elements")
+        LB.check(LB.lib().msa_plan_traceback_nw(self._h, pair, _ptr(dDir), _ptr(d_ops), d_ops.numel(), _ptr(d_info),
+                                                _stream_ptr(stream)), "msa_plan_traceback_nw")
+
+    def traceback_nw(self, dDir, pair=0, stream=None, ops_cap=None):
+        """Device walk of a global alignment, fetched and completed: dict(ops=bytes end -> start that consume
+        exactly (m, n) -- the walk's ops, then the border gap from its stop cell: i x 'I' or j x 'D' --, stop=(i,
+        j), cigar=run-length string start -> end, stats=the walk's counters).  ops_cap (default m + n + 2, always
+        enough) bounds the walk's ops; a longer walk raises MsaError(MSA_ERR_CAPACITY)."""
+        import torch
+
+        dev = dDir.device
+        cap = self.ms[pair] + self.ns[pair] + 2 if ops_cap is None else int(ops_cap)
+        ops = torch.empty(cap, dtype=torch.uint8, device=dev)
+        info = torch.zeros(8, dtype=torch.int64, device=dev)
+        self.traceback_nw_async(dDir, ops, info, pair, stream)
+        if stream is not None:
+            # .cpu() below orders only against torch's current stream: wait for the walk's own
+            (torch.cuda.ExternalStream(stream) if isinstance(stream, int) else stream).synchronize()
+        inf = info.cpu().tolist()
+        LB.check(int(inf[3]), "msa_plan_traceback_nw")
+        i, j = int(inf[1]) - 1, int(inf[2]) - 1
+        o = bytes(ops[:inf[0]].cpu().numpy().tobytes()) + (b"I" * i if i > 0 else b"D" * max(j, 0))
+        return dict(ops=o, stop=(i, j), cigar=cigar_of(o),
+                    stats=dict(switches=int(inf[4]), on_demand=int(inf[5]), ticks=int(inf[6]), requests=int(inf[7])))
 
     def set_timing(self, on: bool) -> None:
         """Record HIP events around the DP kernel in run() (default on; kernel_ms() needs it)."""

@@ -29,6 +29,10 @@
  *   msa_plan_*           device-resident batch / single-pair fills (build extension:
  *                        configs C2-C5 of BASELINE.json; no reference counterpart,
  *                        same cell recurrence family as subproblem_alignment.cpp:396-398)
+ *   msa_nw_align, msa_plan_traceback_nw
+ *                        banded global (Gotoh) alignment with its CIGAR (build extension:
+ *                        MSA_NW_ALIGN plans write one direction byte per in-band cell, the
+ *                        walk runs on the device; same recurrence as MSA_NW_BANDED)
  */
 #ifndef MSA_H
 #define MSA_H
@@ -211,7 +215,9 @@ typedef enum msa_alg_e {
   MSA_SW_AFFINE = 1,  /* Smith-Waterman, affine gap */
   MSA_NW_BANDED = 2,  /* reference Gotoh (g=gap_extend, h=gap_open-gap_extend), start type -1, optional band */
   MSA_REF_GOTOH = 3,  /* reference Gotoh T1/T2/T3, any start type, exact -inf */
-  MSA_PARTIAL = 4     /* partial.cpp forward Gotoh, int32 wrap */
+  MSA_PARTIAL = 4,    /* partial.cpp forward Gotoh, int32 wrap */
+  MSA_NW_ALIGN = 5    /* MSA_NW_BANDED's recurrence with one direction byte per cell (MSA_CELLS_DIR only,
+                         match = 1, mismatch = 0; walked by msa_plan_traceback_nw) */
 } msa_alg_e;
 
 typedef enum msa_out_e { MSA_CELLS_NONE = 0, MSA_CELLS_H = 1, MSA_CELLS_DIR = 2, MSA_CELLS_TAB = 3 } msa_out_e;
@@ -223,7 +229,7 @@ typedef struct msa_plan_desc {
   int32_t gap_open;    /* SW: cost of the first gap char; Gotoh: g + h */
   int32_t gap_extend;  /* SW: each further gap char; Gotoh: g */
   int32_t start_type;  /* MSA_REF_GOTOH / MSA_PARTIAL */
-  int32_t band;        /* MSA_NW_BANDED: |i-j| <= band, -1 = none */
+  int32_t band;        /* MSA_NW_BANDED / MSA_NW_ALIGN: |i-j| <= band, -1 = none */
   int32_t track_end;   /* SW: also report the end cell (first max, row-major) */
   int32_t single;      /* 1: one pair spread over many workgroups; 0: one workgroup per pair */
   int64_t n_pairs;
@@ -324,6 +330,26 @@ int msa_plan_traceback(msa_plan* plan, int64_t pair, const uint8_t* dDir, uint8_
  * follow from the ops on the host in O(m+n) (msa_main_alignment does this). */
 int msa_plan_traceback_gotoh(msa_plan* plan, int64_t pair, int end_type, const uint8_t* dDir, uint8_t* d_ops,
                              int64_t ops_cap, int64_t* d_info, void* stream);
+/* Global (Needleman-Wunsch / Gotoh) traceback ON THE DEVICE for an MSA_NW_ALIGN plan, after
+ * msa_plan_run on the same stream.  The plan computes MSA_NW_BANDED's recurrence (f = 1 on equal
+ * codes else 0, g = gap_extend, h = gap_open - gap_extend >= 0; cells with |i - j| > band are -inf):
+ *   E(i,j) = max(H(i,j-1) - (g+h), E(i,j-1) - g)      F(i,j) = max(H(i-1,j) - (g+h), F(i-1,j) - g)
+ *   H(i,j) = max(H(i-1,j-1) + f, E(i,j), F(i,j))      score = H(m,n)
+ * and writes one byte per cell (skewed stripe layout, msa_plan_pair_layout), in the SW-affine
+ * format: bits 0-1 = 1 if H equals the diagonal term, else 2 if H equals E, else 3 (F); bit 2 set
+ * iff E(i,j) == H(i,j-1) - (g+h) (a tie with the extension goes to "open"); bit 3 the same for F and
+ * H(i-1,j).  Bits 2 / 3 mean nothing where E / F is -inf; bytes of cells outside the band mean nothing.
+ * The walk (tie order of the oracle's orc_sw) starts at (m, n) in state H.  H: low bits 1 -> 'M',
+ * to (i-1, j-1); 2 -> state E; 3 -> state F.  E: 'D', j--, back to H if bit 2, else stay.  F: 'I',
+ * i--, back to H if bit 3, else stay.  It stops as soon as i == 0 or j == 0; the rest of the
+ * alignment is the border gap (i x 'I' or j x 'D'), which the caller appends.  d_ops receives the
+ * ops end -> start (at most ops_cap; m+n suffices); d_info[8] as msa_plan_traceback_gotoh: {n_ops,
+ * i+1, j+1, status, stripes entered, groups staged on demand, ticks, waits} with (i, j) the border
+ * cell where the walk stopped and status 0 or MSA_ERR_CAPACITY.  Asynchronous, one walk per call
+ * (a batch plan is walked pair by pair).  MSA_ERR_UNSUPPORTED for any plan that is not MSA_NW_ALIGN;
+ * msa_plan_traceback and msa_plan_traceback_gotoh reject MSA_NW_ALIGN plans. */
+int msa_plan_traceback_nw(msa_plan* plan, int64_t pair, const uint8_t* dDir, uint8_t* d_ops, int64_t ops_cap,
+                          int64_t* d_info, void* stream);
 /* Order-independent digest of pair `pair`'s H cells (oracle orc_checksum_h). */
 int msa_plan_checksum(msa_plan* plan, const int32_t* dH, int64_t pair, uint64_t* digest, void* stream);
 /* Device time (ms) of the last msa_plan_run's stripe kernel, from HIP events
@@ -345,6 +371,17 @@ int msa_encode_pair(const char* A0, size_t m, const char* B0, size_t n, uint8_t*
 int msa_sw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t match, int32_t mismatch,
                  int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_i, int64_t* end_j,
                  int64_t* beg_i, int64_t* beg_j, char* cigar, size_t cigar_cap);
+
+/* Host-pointer global alignment (build extension): the MSA_NW_ALIGN fill, msa_plan_traceback_nw's
+ * walk and the border gap, as a run-length M/I/D string start -> end (I consumes A, D consumes B)
+ * that consumes exactly m and n.  Scoring as MSA_NW_BANDED: +1 on equal symbols, 0 otherwise, a gap
+ * of L costs (gap_open - gap_extend) + gap_extend * L; gap_open >= gap_extend >= 0, else
+ * MSA_ERR_UNSUPPORTED.  band = -1: no band; band >= 0 needs |m - n| <= band (MSA_ERR_ARG).  At most
+ * 8 distinct symbols (MSA_ERR_ALPHABET).  *score = H(m, n).  cigar == NULL: the score only (no
+ * direction bytes are written).  The call is admitted against the device budget with the band's
+ * footprint (~(2 band + 64) bytes per row), not the full matrix's. */
+int msa_nw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t gap_open, int32_t gap_extend,
+                 int64_t band, int32_t* score, char* cigar, size_t cigar_cap);
 
 #ifdef __cplusplus
 }
