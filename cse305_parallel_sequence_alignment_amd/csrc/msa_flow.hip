@@ -371,7 +371,8 @@ struct FillArgs {
 };
 #ifdef MSA_STAMPS
 // pass-2 totals (diagnostic build): [0] ticks waiting for the block's last granule, [1] ticks loading and
-// checking its inputs, [2] ticks computing + storing, [3] blocks, at item 62 / wave 15's stamp area
+// checking its inputs (both from p2_wait_load), [2] ticks staging, computing + storing, [3] blocks (p2_stat_done),
+// every block kind, at item 62 / wave 15's stamp area
 #define FL_P2STAT(a_, k_, v_) \
   do { if ((a_).stamps && lane == 0) atomicAdd((a_).stamps + ((size_t)(62 * 16 + 15) * 4096) * 4 + (k_), (unsigned long long)(v_)); } while (0)
 #else
@@ -1433,6 +1434,176 @@ __device__ __forceinline__ fl_v4u p2_codes(lds_int* lds, int k, int lane) {
                 __builtin_amdgcn_alignbyte(d3, d2, sh), __builtin_amdgcn_alignbyte(d4, d3, sh)};
 }
 
+// What the five pass-2 block bodies share around their recurrences: the block's geometry (p2_geom), the
+// wait for its inputs and their load (p2_wait_load), a phase's inputs out of the staged streams
+// (p2_unpack), the profile byte of a step (p2_sbyte), the block's first maximum (p2_block_best) and the
+// Gotoh phase dispatch (p2_got_phases).  All are inlined into the noinline bodies.
+//
+// Block blk = (stripe s, segment seg) of a plan with R rows per lane and PS phases per segment: phases
+// [q0, q1) of the stripe's P, first column cs, the lane's first row row_i and its one or two A codes,
+// nv bottom-row granules per BR stream from pass 1 (blocks [q0, qb) of the row above; none for stripe
+// 0), the lane's SNAP granules (SNAPW granules per block: 64 x the saved values) and the BR rows of
+// stripe s - 1 (value stream 0, and 1 for the two-stream kinds).  live: the block has phases.
+struct P2Geom {
+  int s, seg, S, P, q0, q1, cs, row_i, nv;
+  unsigned ac, ac2;
+  const unsigned long long* sp;
+  const unsigned long long* br0;
+  const unsigned long long* br1;
+  bool live;
+};
+template <int R, int PS, int SNAPW>
+__device__ __forceinline__ P2Geom p2_geom(const FillArgs& a, int blk, int lane) {
+  P2Geom G;
+  const int m = a.m, n = a.n;
+  G.S = (m + 64 * R - 1) / (64 * R);
+  G.s = blk / a.nseg;
+  G.seg = blk - G.s * a.nseg;
+  G.P = fl_P(G.s, m, n, R);
+  G.q0 = G.seg * PS;
+  // (the rest is computed for a block without phases too -- address arithmetic, and A codes of rows <= m
+  // only: a guard of its own here was a second divergent region in front of each body's, ~50 instructions)
+  G.live = G.s < G.S && G.q0 < G.P;
+  G.q1 = min(G.P, G.q0 + PS);
+  G.cs = fl_cs(G.s);
+  G.row_i = 64 * R * G.s + R * lane + 1;
+  G.ac = (G.row_i <= m) ? (a.A[a.a_off + G.row_i - 1] & 7u) : 0u;
+  G.ac2 = (R == 2 && G.row_i + 1 <= m) ? (a.A[a.a_off + G.row_i] & 7u) : 0u;
+  const int Bin = (G.s == 0) ? G.P - 1 : min(G.P - 1, fl_bmax(G.s, m, n, R));
+  G.sp = a.snap + ((size_t)G.s * a.nseg + G.seg) * SNAPW + lane;
+  G.br0 = a.br + (size_t)(G.s > 0 ? G.s - 1 : 0) * a.brw;
+  G.br1 = a.br + (size_t)(G.S + (G.s > 0 ? G.s - 1 : 0)) * a.brw;
+  const int qb = (G.s > 0) ? min(G.q1, Bin + 1) : G.q0;
+  G.nv = 16 * max(0, qb - G.q0);  // granules per stream, lane l holds l, l+64, ...
+  return G;
+}
+
+// The block's inputs are {epoch, value} granules that pass 1 may still be writing: the wave polls the
+// block's last bottom-row granule(s), then loads and epoch-checks them all -- the lane's NS SNAP values
+// into x, the NBR bottom-row streams into the LDS value streams (stream 1 + add1).  Returns whether they
+// are all of this epoch; if not after FL_SPIN_MAX tries, err = 15 and the caller computes nothing.
+// Uniform waits (ballots) and no early exits: the compiler keeps the wave whole, and the error store stays
+// behind the loops (a divergent store inside one would make its control divergent).  BACKOFF: the first
+// stage sleeps longer after FL_FSLONG polls (fl_poll_sleep).  MSA_STAMPS builds: a sample of the blocks
+// adds the ticks of the two stages to FL_P2STAT's totals; tload = s_memtime after them (p2_stat_done).
+template <int NS, int NBR, int PS, bool BACKOFF>
+__device__ __forceinline__ bool p2_wait_load(const FillArgs& a, const P2Geom& G, int blk, int lane, lds_int* lds,
+                                             int (&x)[NS], int add1, unsigned long long& tload) {
+  const unsigned ep = a.ep;
+  const int nv = G.nv;
+  const unsigned long long* b0 = G.br0 + 16 * G.q0;
+  const unsigned long long* b1 = G.br1 + 16 * G.q0;
+#ifdef MSA_STAMPS
+  const unsigned long long tp0 = __builtin_amdgcn_s_memtime();
+#endif
+  bool ready = (nv == 0);
+  for (int t2 = 0; !ready && t2 < (int)(FL_SPIN_MAX >> 2); ++t2) {  // the block's last granules first
+    const unsigned long long gz = gload(b0 + nv - 1), gf = (NBR == 2) ? gload(b1 + nv - 1) : gz;
+    ready = __ballot((unsigned)(gz >> 32) != ep || (unsigned)(gf >> 32) != ep) == 0;
+    if (!ready) {
+      if constexpr (BACKOFF) fl_poll_sleep(t2);
+      else __builtin_amdgcn_s_sleep(FL_FSLEEP);
+    }
+  }
+#ifdef MSA_STAMPS
+  const unsigned long long tp1 = __builtin_amdgcn_s_memtime();
+#endif
+  if (ready) {
+    ready = false;
+    for (int tries = 0; !ready && tries < (int)FL_SPIN_MAX; ++tries) {
+      unsigned long long sv[NS];
+#pragma unroll
+      for (int k = 0; k < NS; ++k) sv[k] = gload(G.sp + 64 * k);
+      bool ok = true;
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        ok = ok && ((unsigned)(sv[k] >> 32) == ep);
+        x[k] = (int)(unsigned)sv[k];
+      }
+      for (int v = lane; v < nv; v += 64) {
+        const unsigned long long gz = gload(b0 + v), gf = (NBR == 2) ? gload(b1 + v) : gz;
+        ok = ok && ((unsigned)(gz >> 32) == ep) && ((unsigned)(gf >> 32) == ep);
+        *L(lds + v) = (int)(unsigned)gz;
+        if constexpr (NBR == 2) *L(lds + fl_p2vs(PS) + v) = (int)(unsigned)gf + add1;
+      }
+      ready = __ballot(!ok) == 0;
+      if (!ready) __builtin_amdgcn_s_sleep(8);
+    }
+  }
+  if (!ready && lane == 0) atomicExch(a.err, 15);
+#ifdef MSA_STAMPS
+  tload = __builtin_amdgcn_s_memtime();
+  if ((blk & 15) == 0) {  // a sample of the blocks (the atomics would serialize all of them)
+    FL_P2STAT(a, 0, tp1 - tp0);
+    FL_P2STAT(a, 1, tload - tp1);
+  }
+#else
+  tload = 0;
+#endif
+  return ready;
+}
+// MSA_STAMPS builds: the sampled block's ticks since its inputs were loaded, and the block itself.
+__device__ __forceinline__ void p2_stat_done(const FillArgs& a, int blk, int lane, unsigned long long tload) {
+#ifdef MSA_STAMPS
+  if ((blk & 15) == 0) {
+    FL_P2STAT(a, 2, __builtin_amdgcn_s_memtime() - tload);
+    FL_P2STAT(a, 3, 1);
+  }
+#endif
+}
+
+// Lane-independent inputs of the block's phase k (its 16 columns of the row above) out of the NV staged
+// value streams.
+template <int NV, int PS>
+__device__ __forceinline__ void p2_unpack(lds_int* lds, int k, int (&IN0)[16], int (&IN1)[16]) {
+  const lds_int4* s0 = reinterpret_cast<const lds_int4*>(L(lds + 16 * k));
+  const lds_int4* s1 = reinterpret_cast<const lds_int4*>(L(lds + (NV == 2 ? fl_p2vs(PS) : 0) + 16 * k));
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const fl_v4i v0 = s0[u];
+    IN0[4 * u] = v0.x; IN0[4 * u + 1] = v0.y; IN0[4 * u + 2] = v0.z; IN0[4 * u + 3] = v0.w;
+    if constexpr (NV == 2) {
+      const fl_v4i v1 = s1[u];
+      IN1[4 * u] = v1.x; IN1[4 * u + 1] = v1.y; IN1[4 * u + 2] = v1.z; IN1[4 * u + 3] = v1.w;
+    }
+  }
+}
+template <int NV, int PS>
+__device__ __forceinline__ void p2_unpack(lds_int* lds, int k, int (&IN0)[16]) {
+  static_assert(NV == 1, "two streams: pass both arrays");
+  p2_unpack<1, PS>(lds, k, IN0, IN0);
+}
+// Signed byte kk of a profile word (the scores of four steps, v_perm of the lane's profile by the codes).
+__device__ __forceinline__ int p2_sbyte(unsigned s4, int kk) { return ((int)(s4 << (24 - 8 * kk))) >> 24; }
+
+// The block's best cell from each lane's (bb, bi, bj): first maximum in row-major order -- max score, then
+// min row, then min column -- to the block's slot or the pair's key (fl_block_result).
+__device__ __forceinline__ void p2_block_best(const FillArgs& a, int blk, int lane, int bb, int bi, int bj) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const int ob = __shfl_xor(bb, off), oi = __shfl_xor(bi, off), oj = __shfl_xor(bj, off);
+    const bool take = ob > bb || (ob == bb && (oi < bi || (oi == bi && oj < bj)));
+    bb = take ? ob : bb;
+    bi = take ? oi : bi;
+    bj = take ? oj : bj;
+  }
+  fl_block_result(a.blk, a.best_key, blk, lane, bb, bi, bj, a.n);
+}
+
+// Gotoh: phases [q0, q1) through phase(q, HEAD, CAP) -- CAP: the phase holds the final cell (m, n), some
+// lane's step tf; HEAD: lanes still left of column 1 hold the column-0 border (the first 6 phases).
+template <class PHASE>
+__device__ __forceinline__ void p2_got_phases(int q0, int q1, int tf, PHASE phase) {
+  using T_ = std::true_type;
+  using F_ = std::false_type;
+  for (int q = q0; q < q1; ++q) {
+    const bool cap = __ballot(tf >= 16 * q && tf < 16 * q + 16) != 0ull;
+    if (cap) phase(q, T_{}, T_{});
+    else if (q < 6) phase(q, T_{}, F_{});
+    else phase(q, F_{}, F_{});
+  }
+}
+
 // Pass 2: block (stripe s, segment seg) of PS phases, one wave.  Its inputs
 // are {epoch, value} granules that pass 1 may still be writing: the wave waits
 // for the block's last bottom-row granule, then loads and checks them all.
@@ -1442,152 +1613,97 @@ template <bool FLOOR, bool TRACKPOS, int R, int CALLER>
 __device__ __attribute__((noinline)) void fill_block(const FillArgs a, int blk, int lane, lds_int* lds) {
   constexpr int PS = fl_ps(CALLER);
   constexpr bool GS = !FLOOR;
-  const unsigned ep = a.ep;
-  const int m = a.m, n = a.n, S = (m + 64 * R - 1) / (64 * R), g = a.g;
-  const int s = blk / a.nseg, seg = blk - s * a.nseg;
+  const int m = a.m, g = a.g;
+  const P2Geom G = p2_geom<R, PS, 128 * R>(a, blk, lane);
+  const int s = G.s, q0 = G.q0, cs = G.cs, row_i = G.row_i;
   int bb = INT32_MIN, bi = 0, bj = 0;
-  if (s < S) {
-    const int P = fl_P(s, m, n, R);
-    const int q0 = seg * PS;
-    if (q0 < P) {
-      int q1 = min(P, q0 + PS);
-      const int cs = fl_cs(s);
-      const int row_i = 64 * R * s + R * lane + 1;
-      const unsigned ac = (row_i <= m) ? (a.A[a.a_off + row_i - 1] & 7u) : 0u;
-      const unsigned ac2 = (R == 2 && row_i + 1 <= m) ? (a.A[a.a_off + row_i] & 7u) : 0u;
-      unsigned plo, phi, plo2 = 0, phi2 = 0;
-      fl_profile<GS, FLOOR>(a.match, a.mismatch, g, ac, plo, phi);
-      if constexpr (R == 2) fl_profile<GS, FLOOR>(a.match, a.mismatch, g, ac2, plo2, phi2);
-      const int Bin = (s == 0) ? P - 1 : min(P - 1, fl_bmax(s, m, n, R));
-      const unsigned long long* sp = a.snap + ((size_t)s * a.nseg + seg) * (128 * R) + lane;
-      const unsigned long long* brow = a.br + (size_t)(s > 0 ? s - 1 : 0) * a.brw;
-      // bottom-row blocks [q0, qb) of the row above come from pass 1 (s > 0)
-      const int qb = (s > 0) ? min(q1, Bin + 1) : q0;
-      const int nv = 16 * max(0, qb - q0);  // granules, lane l holds l, l+64, ...
-      int X = 0, U = 0, X2 = 0;
-      // uniform waits (ballots) and no early exits: the compiler keeps the wave whole
-      bool ready = (nv == 0);
-      for (int t2 = 0; !ready && t2 < (int)(FL_SPIN_MAX >> 2); ++t2) {  // the block's last granule first
-        const unsigned long long gl = gload(brow + 16 * q0 + nv - 1);
-        ready = __ballot((unsigned)(gl >> 32) != ep) == 0;
-        if (!ready) __builtin_amdgcn_s_sleep(FL_FSLEEP);
-      }
-      if (ready) {
-        ready = false;
-        for (int tries = 0; !ready && tries < (int)FL_SPIN_MAX; ++tries) {
-          const unsigned long long x0 = gload(sp), u0 = gload(sp + 64);
-          bool ok = ((unsigned)(x0 >> 32) == ep) && ((unsigned)(u0 >> 32) == ep);
-          X = (int)(unsigned)x0;
-          U = (int)(unsigned)u0;
-          if constexpr (R == 2) {
-            const unsigned long long x2 = gload(sp + 128);
-            ok = ok && ((unsigned)(x2 >> 32) == ep);
-            X2 = (int)(unsigned)x2;
-          }
-          for (int v = lane; v < nv; v += 64) {
-            const unsigned long long gv = gload(brow + 16 * q0 + v);
-            ok = ok && ((unsigned)(gv >> 32) == ep);
-            *L(lds + v) = (int)(unsigned)gv;
-          }
-          ready = __ballot(!ok) == 0;
-          if (!ready) __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      if (!ready) {
-        if (lane == 0) atomicExch(a.err, 15);
-        q1 = q0;  // nothing computed; the block reports no cell
-      }
-      // row 0 (stripe 0): H = 0 left of and on the top border
-      p2_stage<1, PS>(lds, s, nv, 16 * (q1 - q0), lane,
-                  [&](int v, int) { return GS ? g * (cs + 16 * q0 + v) : -g; }, a.cod + a.cod_off, a.cod_copy, cs, q0);
-      // H = G - g(i+j); i+j = 64Rs + 1 + cs + t + (R-1) lane on row 1, +1 on row 2
-      const int negct0 = -g * (64 * R * s + 1 + cs + (R - 1) * lane);
-      int gk[16];
+  if (G.live) {
+    unsigned plo, phi, plo2 = 0, phi2 = 0;
+    fl_profile<GS, FLOOR>(a.match, a.mismatch, g, G.ac, plo, phi);
+    if constexpr (R == 2) fl_profile<GS, FLOOR>(a.match, a.mismatch, g, G.ac2, plo2, phi2);
+    int sn[R + 1] = {};  // SNAP: X, U (row 1's left and diagonal), R = 2: X2
+    unsigned long long tload;
+    // (not ready: nothing computed; the block reports no cell)
+    const int q1 = p2_wait_load<R + 1, 1, PS, false>(a, G, blk, lane, lds, sn, 0, tload) ? G.q1 : q0;
+    int X = sn[0], U = sn[1], X2 = sn[R];
+    // row 0 (stripe 0): H = 0 left of and on the top border
+    p2_stage<1, PS>(lds, s, G.nv, 16 * (q1 - q0), lane,
+                [&](int v, int) { return GS ? g * (cs + 16 * q0 + v) : -g; }, a.cod + a.cod_off, a.cod_copy, cs, q0);
+    // H = G - g(i+j); i+j = 64Rs + 1 + cs + t + (R-1) lane on row 1, +1 on row 2
+    const int negct0 = -g * (64 * R * s + 1 + cs + (R - 1) * lane);
+    int gk[16];
 #pragma unroll
-      for (int kx = 0; kx < 16; ++kx) {
-        gk[kx] = -g * kx;
-        asm("" : "+v"(gk[kx]));
-      }
-      int best = INT32_MIN, bt = -1, best2 = INT32_MIN, bt2 = -1;
-      msa_v4i* hp = reinterpret_cast<msa_v4i*>(a.outH + (size_t)a.out_off + (size_t)s * a.pmax * MSA_K * 64 * R) + lane;
-      for (int q = q0; q < q1; ++q) {
-        int IN[16];
-        {
-          const lds_int4* src = reinterpret_cast<const lds_int4*>(L(lds + 16 * (q - q0)));
+    for (int kx = 0; kx < 16; ++kx) {
+      gk[kx] = -g * kx;
+      asm("" : "+v"(gk[kx]));
+    }
+    int best = INT32_MIN, bt = -1, best2 = INT32_MIN, bt2 = -1;
+    msa_v4i* hp = reinterpret_cast<msa_v4i*>(a.outH + (size_t)a.out_off + (size_t)s * a.pmax * MSA_K * 64 * R) + lane;
+    for (int q = q0; q < q1; ++q) {
+      int IN[16];
+      p2_unpack<1, PS>(lds, q - q0, IN);
+      const fl_v4u c4 = p2_codes<PS>(lds, q - q0, lane);
+      const unsigned cw[4] = {c4.x, c4.y, c4.z, c4.w};
+      const int negct = negct0 - 16 * g * q;
+      int hv[16], hv2[16];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const fl_v4i v = src[u];
-            IN[4 * u] = v.x; IN[4 * u + 1] = v.y; IN[4 * u + 2] = v.z; IN[4 * u + 3] = v.w;
+      for (int u = 0; u < 4; ++u) {
+        const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
+        const unsigned s4b = (R == 2) ? __builtin_amdgcn_perm(phi2, plo2, cw[u]) : 0u;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+          const int kx = 4 * u + kk;
+          const int sc = p2_sbyte(s4, kk);
+          if constexpr (R == 1) {
+            const int h = fl_step<GS, FLOOR>(IN[kx], sc, X, U, g);
+            hv[kx] = GS ? h + negct + gk[kx] : h;
+          } else {
+            const int sb = p2_sbyte(s4b, kk);
+            const int up = dpp_shr1(IN[kx], X2);
+            int h1 = imax3(U + sc, up, X);
+            if constexpr (FLOOR) h1 = imax(h1, 0);
+            asm("" : "+v"(h1));
+            U = up;
+            const int xprev = X;
+            X = GS ? h1 : h1 - g;
+            int h2 = imax3(xprev + sb, X, X2);
+            if constexpr (FLOOR) h2 = imax(h2, 0);
+            asm("" : "+v"(h2));
+            X2 = GS ? h2 : h2 - g;
+            hv[kx] = GS ? h1 + negct + gk[kx] : h1;
+            hv2[kx] = GS ? h2 + negct + gk[kx] - g : h2;
+          }
+          if constexpr (TRACKPOS) {
+            if (hv[kx] > best) { best = hv[kx]; bt = 16 * q + kx; }
+            if (R == 2 && hv2[kx] > best2) { best2 = hv2[kx]; bt2 = 16 * q + kx; }
           }
         }
-        const fl_v4u c4 = p2_codes<PS>(lds, q - q0, lane);
-        const unsigned cw[4] = {c4.x, c4.y, c4.z, c4.w};
-        const int negct = negct0 - 16 * g * q;
-        int hv[16], hv2[16];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
-          const unsigned s4b = (R == 2) ? __builtin_amdgcn_perm(phi2, plo2, cw[u]) : 0u;
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) {
-            const int kx = 4 * u + kk;
-            const int sc = ((int)(s4 << (24 - 8 * kk))) >> 24;
-            if constexpr (R == 1) {
-              const int h = fl_step<GS, FLOOR>(IN[kx], sc, X, U, g);
-              hv[kx] = GS ? h + negct + gk[kx] : h;
-            } else {
-              const int sb = ((int)(s4b << (24 - 8 * kk))) >> 24;
-              const int up = dpp_shr1(IN[kx], X2);
-              int h1 = imax3(U + sc, up, X);
-              if constexpr (FLOOR) h1 = imax(h1, 0);
-              asm("" : "+v"(h1));
-              U = up;
-              const int xprev = X;
-              X = GS ? h1 : h1 - g;
-              int h2 = imax3(xprev + sb, X, X2);
-              if constexpr (FLOOR) h2 = imax(h2, 0);
-              asm("" : "+v"(h2));
-              X2 = GS ? h2 : h2 - g;
-              hv[kx] = GS ? h1 + negct + gk[kx] : h1;
-              hv2[kx] = GS ? h2 + negct + gk[kx] - g : h2;
-            }
-            if constexpr (TRACKPOS) {
-              if (hv[kx] > best) { best = hv[kx]; bt = 16 * q + kx; }
-              if (R == 2 && hv2[kx] > best2) { best2 = hv2[kx]; bt2 = 16 * q + kx; }
-            }
-          }
-          __builtin_nontemporal_store(msa_v4i{hv[4 * u], hv[4 * u + 1], hv[4 * u + 2], hv[4 * u + 3]},
-                                      hp + (size_t)(4 * q + u) * 64 * R);
-          if constexpr (R == 2)  // (each store: one contiguous 1 KiB)
-            __builtin_nontemporal_store(msa_v4i{hv2[4 * u], hv2[4 * u + 1], hv2[4 * u + 2], hv2[4 * u + 3]},
-                                        hp + (size_t)(4 * q + u) * 128 + 64);
-        }
-        if constexpr (!TRACKPOS) {
-#pragma unroll
-          for (int kx = 0; kx < 16; kx += 2) best = imax3(best, hv[kx], hv[kx + 1]);
-          if constexpr (R == 2) {
-#pragma unroll
-            for (int kx = 0; kx < 16; kx += 2) best2 = imax3(best2, hv2[kx], hv2[kx + 1]);
-          }
-        }
+        __builtin_nontemporal_store(msa_v4i{hv[4 * u], hv[4 * u + 1], hv[4 * u + 2], hv[4 * u + 3]},
+                                    hp + (size_t)(4 * q + u) * 64 * R);
+        if constexpr (R == 2)  // (each store: one contiguous 1 KiB)
+          __builtin_nontemporal_store(msa_v4i{hv2[4 * u], hv2[4 * u + 1], hv2[4 * u + 2], hv2[4 * u + 3]},
+                                      hp + (size_t)(4 * q + u) * 128 + 64);
       }
-      bb = (row_i <= m) ? best : INT32_MIN;
-      bi = row_i;
-      bj = TRACKPOS ? cs + bt - lane : -1;
-      if (R == 2 && row_i + 1 <= m && best2 > bb) {  // ties keep the upper row
-        bb = best2;
-        bi = row_i + 1;
-        bj = TRACKPOS ? cs + bt2 - lane : -1;
+      if constexpr (!TRACKPOS) {
+#pragma unroll
+        for (int kx = 0; kx < 16; kx += 2) best = imax3(best, hv[kx], hv[kx + 1]);
+        if constexpr (R == 2) {
+#pragma unroll
+          for (int kx = 0; kx < 16; kx += 2) best2 = imax3(best2, hv2[kx], hv2[kx + 1]);
+        }
       }
     }
+    bb = (row_i <= m) ? best : INT32_MIN;
+    bi = row_i;
+    bj = TRACKPOS ? cs + bt - lane : -1;
+    if (R == 2 && row_i + 1 <= m && best2 > bb) {  // ties keep the upper row
+      bb = best2;
+      bi = row_i + 1;
+      bj = TRACKPOS ? cs + bt2 - lane : -1;
+    }
+    p2_stat_done(a, blk, lane, tload);
   }
-  // first max in row-major order: max score, then min row, then min column
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int ob = __shfl_xor(bb, off), oi = __shfl_xor(bi, off), oj = __shfl_xor(bj, off);
-    if (ob > bb || (ob == bb && (oi < bi || (oi == bi && oj < bj)))) { bb = ob; bi = oi; bj = oj; }
-  }
-  fl_block_result(a.blk, a.best_key, blk, lane, bb, bi, bj, a.n);
+  p2_block_best(a, blk, lane, bb, bi, bj);
 }
 
 // Pass 2, affine (config C5): block (stripe s, segment seg) recomputes its PS phases from
@@ -1600,123 +1716,69 @@ template <int CALLER>
 __device__ __attribute__((noinline)) void fill_block_aff(kargs_c* ka, int blk, int lane, lds_int* lds) {
   constexpr int PS = fl_ps(CALLER);
   const FillArgs a = fill_args_of(ka);
-  const unsigned ep = a.ep;
-  const int m = a.m, n = a.n, S = (m + 63) / 64, g = a.g, oe = a.oe;
-  const int s = blk / a.nseg, seg = blk - s * a.nseg;
+  const int m = a.m, g = a.g, oe = a.oe;
+  const P2Geom G = p2_geom<1, PS, 256>(a, blk, lane);
+  const int s = G.s, q0 = G.q0, cs = G.cs, row_i = G.row_i;
   int bb = INT32_MIN, bi = 0, bj = 0;
-  if (s < S) {
-    const int P = fl_P(s, m, n, 1);
-    const int q0 = seg * PS;
-    if (q0 < P) {
-      int q1 = min(P, q0 + PS);
-      const int cs = fl_cs(s);
-      const int row_i = 64 * s + lane + 1;
-      const unsigned ac = (row_i <= m) ? (a.A[a.a_off + row_i - 1] & 7u) : 0u;
-      unsigned plo, phi;
-      fl_profile_aff(a.match, a.mismatch, g, oe, ac, plo, phi);
-      const int Bin = (s == 0) ? P - 1 : min(P - 1, fl_bmax(s, m, n, 1));
-      const unsigned long long* sp = a.snap + ((size_t)s * a.nseg + seg) * 256 + lane;
-      const unsigned long long* brz = a.br + (size_t)(s > 0 ? s - 1 : 0) * a.brw;
-      const unsigned long long* brf = a.br + (size_t)(S + (s > 0 ? s - 1 : 0)) * a.brw;
-      const int qb = (s > 0) ? min(q1, Bin + 1) : q0;
-      const int nv = 16 * max(0, qb - q0);  // granules per value, lane l holds l, l+64, ...
-      int Zl = 0, E = 0, Fo = 0, U = 0;
-      bool ready = (nv == 0);
-      for (int t2 = 0; !ready && t2 < (int)(FL_SPIN_MAX >> 2); ++t2) {  // the block's last granules first
-        const unsigned long long gz = gload(brz + 16 * q0 + nv - 1), gf = gload(brf + 16 * q0 + nv - 1);
-        ready = __ballot((unsigned)(gz >> 32) != ep || (unsigned)(gf >> 32) != ep) == 0;
-        if (!ready) fl_poll_sleep(t2);
-      }
-      if (ready) {
-        ready = false;
-        for (int tries = 0; !ready && tries < (int)FL_SPIN_MAX; ++tries) {
-          const unsigned long long x0 = gload(sp), x1 = gload(sp + 64), x2 = gload(sp + 128), x3 = gload(sp + 192);
-          bool ok = ((unsigned)(x0 >> 32) == ep) && ((unsigned)(x1 >> 32) == ep) && ((unsigned)(x2 >> 32) == ep) &&
-                    ((unsigned)(x3 >> 32) == ep);
-          Zl = (int)(unsigned)x0;
-          E = (int)(unsigned)x1;
-          Fo = (int)(unsigned)x2;
-          U = (int)(unsigned)x3;
-          for (int v = lane; v < nv; v += 64) {
-            const unsigned long long gz = gload(brz + 16 * q0 + v), gf = gload(brf + 16 * q0 + v);
-            ok = ok && ((unsigned)(gz >> 32) == ep) && ((unsigned)(gf >> 32) == ep);
-            *L(lds + v) = (int)(unsigned)gz;
-            *L(lds + fl_p2vs(PS) + v) = (int)(unsigned)gf;
-          }
-          ready = __ballot(!ok) == 0;
-          if (!ready) __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      if (!ready) {
-        if (lane == 0) atomicExch(a.err, 15);
-        q1 = q0;
-      }
-      // row 0 (stripe 0): Z = g col - oe (H = 0), F~ = -inf
-      p2_stage<2, PS>(lds, s, nv, 16 * (q1 - q0), lane,
-                  [&](int v, int k) { return k == 0 ? g * (cs + 16 * q0 + v) - oe : MSA_NEG; }, a.cod + a.cod_off,
-                  a.cod_copy, cs, q0);
-      const int flr0 = g * (64 * s + 1 + cs);
-      int best = INT32_MIN, bt = -1;
-      fl_v4u* dp = reinterpret_cast<fl_v4u*>(a.outDir + (size_t)a.out_off + (size_t)s * a.pmax * 1024) + lane;
-      for (int q = q0; q < q1; ++q) {
-        int INZ[16], INF[16];
-        {
-          const lds_int4* srz = reinterpret_cast<const lds_int4*>(L(lds + 16 * (q - q0)));
-          const lds_int4* srf = reinterpret_cast<const lds_int4*>(L(lds + fl_p2vs(PS) + 16 * (q - q0)));
+  if (G.live) {
+    unsigned plo, phi;
+    fl_profile_aff(a.match, a.mismatch, g, oe, G.ac, plo, phi);
+    int sn[4] = {};  // SNAP: Z left, E~, F~, diagonal Z
+    unsigned long long tload;
+    const int q1 = p2_wait_load<4, 2, PS, true>(a, G, blk, lane, lds, sn, 0, tload) ? G.q1 : q0;
+    int Zl = sn[0], E = sn[1], Fo = sn[2], U = sn[3];
+    // row 0 (stripe 0): Z = g col - oe (H = 0), F~ = -inf
+    p2_stage<2, PS>(lds, s, G.nv, 16 * (q1 - q0), lane,
+                [&](int v, int k) { return k == 0 ? g * (cs + 16 * q0 + v) - oe : MSA_NEG; }, a.cod + a.cod_off,
+                a.cod_copy, cs, q0);
+    const int flr0 = g * (64 * s + 1 + cs);
+    int best = INT32_MIN, bt = -1;
+    fl_v4u* dp = reinterpret_cast<fl_v4u*>(a.outDir + (size_t)a.out_off + (size_t)s * a.pmax * 1024) + lane;
+    for (int q = q0; q < q1; ++q) {
+      int INZ[16], INF[16];
+      p2_unpack<2, PS>(lds, q - q0, INZ, INF);
+      const fl_v4u c4 = p2_codes<PS>(lds, q - q0, lane);
+      const unsigned cw[4] = {c4.x, c4.y, c4.z, c4.w};
+      const int flq = flr0 + 16 * g * q;
+      unsigned dw[4];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const fl_v4i vz = srz[u], vf = srf[u];
-            INZ[4 * u] = vz.x; INZ[4 * u + 1] = vz.y; INZ[4 * u + 2] = vz.z; INZ[4 * u + 3] = vz.w;
-            INF[4 * u] = vf.x; INF[4 * u + 1] = vf.y; INF[4 * u + 2] = vf.z; INF[4 * u + 3] = vf.w;
-          }
-        }
-        const fl_v4u c4 = p2_codes<PS>(lds, q - q0, lane);
-        const unsigned cw[4] = {c4.x, c4.y, c4.z, c4.w};
-        const int flq = flr0 + 16 * g * q;
-        unsigned dw[4];
+      for (int u = 0; u < 4; ++u) {
+        const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
+        unsigned word = 0;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
-          unsigned word = 0;
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) {
-            const int kx = 4 * u + kk;
-            const int sc = ((int)(s4 << (24 - 8 * kk))) >> 24;
-            const int flr = flq + g * kx;
-            const int upZ = dpp_shr1(INZ[kx], Zl);
-            const int upF = dpp_shr1(INF[kx], Fo);
-            const int e = imax(E, Zl);
-            const int f = imax(upF, upZ);
-            const int draw = U + sc;
-            int h = imax3(imax(draw, flr), e, f);
-            asm("" : "+v"(h));
-            // stripe_kernel's SWA byte: H's source (0 local start, 1 diagonal, 2 E, 3 F), bit 2
-            // E opened from H(i, j-1), bit 3 F opened from H(i-1, j)
-            const unsigned hs = (h == flr) ? 0u : (h == draw ? 1u : (h == e ? 2u : 3u));
-            const unsigned dir = hs | ((e == Zl) ? 4u : 0u) | ((f == upZ) ? 8u : 0u);
-            word |= dir << (8 * kk);
-            const int hv = h - flr;
-            if (hv > best) { best = hv; bt = 16 * q + kx; }
-            U = upZ;
-            E = e;
-            Fo = f;
-            Zl = h - oe;
-          }
-          dw[u] = word;
+        for (int kk = 0; kk < 4; ++kk) {
+          const int kx = 4 * u + kk;
+          const int sc = p2_sbyte(s4, kk);
+          const int flr = flq + g * kx;
+          const int upZ = dpp_shr1(INZ[kx], Zl);
+          const int upF = dpp_shr1(INF[kx], Fo);
+          const int e = imax(E, Zl);
+          const int f = imax(upF, upZ);
+          const int draw = U + sc;
+          int h = imax3(imax(draw, flr), e, f);
+          asm("" : "+v"(h));
+          // stripe_kernel's SWA byte: H's source (0 local start, 1 diagonal, 2 E, 3 F), bit 2
+          // E opened from H(i, j-1), bit 3 F opened from H(i-1, j)
+          const unsigned hs = (h == flr) ? 0u : (h == draw ? 1u : (h == e ? 2u : 3u));
+          const unsigned dir = hs | ((e == Zl) ? 4u : 0u) | ((f == upZ) ? 8u : 0u);
+          word |= dir << (8 * kk);
+          const int hv = h - flr;
+          if (hv > best) { best = hv; bt = 16 * q + kx; }
+          U = upZ;
+          E = e;
+          Fo = f;
+          Zl = h - oe;
         }
-        __builtin_nontemporal_store(fl_v4u{dw[0], dw[1], dw[2], dw[3]}, dp + (size_t)q * 64);
+        dw[u] = word;
       }
-      bb = (row_i <= m) ? best : INT32_MIN;
-      bi = row_i;
-      bj = cs + bt - lane;
+      __builtin_nontemporal_store(fl_v4u{dw[0], dw[1], dw[2], dw[3]}, dp + (size_t)q * 64);
     }
+    bb = (row_i <= m) ? best : INT32_MIN;
+    bi = row_i;
+    bj = cs + bt - lane;
+    p2_stat_done(a, blk, lane, tload);
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int ob = __shfl_xor(bb, off), oi = __shfl_xor(bi, off), oj = __shfl_xor(bj, off);
-    if (ob > bb || (ob == bb && (oi < bi || (oi == bi && oj < bj)))) { bb = ob; bi = oi; bj = oj; }
-  }
-  fl_block_result(a.blk, a.best_key, blk, lane, bb, bi, bj, a.n);
+  p2_block_best(a, blk, lane, bb, bi, bj);
 }
 
 // Pass 2, affine, two rows per lane (R = 2: 128-row stripes, lane r holds rows 128s+2r+1 and
@@ -1728,148 +1790,90 @@ template <int CALLER>
 __device__ __attribute__((noinline)) void fill_block_aff2(kargs_c* ka, int blk, int lane, lds_int* lds) {
   constexpr int PS = fl_ps(CALLER);
   const FillArgs a = fill_args_of(ka);
-  const unsigned ep = a.ep;
-  const int m = a.m, n = a.n, S = (m + 127) / 128, g = a.g, oe = a.oe;
-  const int s = blk / a.nseg, seg = blk - s * a.nseg;
+  const int m = a.m, g = a.g, oe = a.oe;
+  const P2Geom G = p2_geom<2, PS, 384>(a, blk, lane);
+  const int s = G.s, q0 = G.q0, cs = G.cs, row_i = G.row_i;
   int bb = INT32_MIN, bi = 0, bj = 0;
-  if (s < S) {
-    const int P = fl_P(s, m, n, 2);
-    const int q0 = seg * PS;
-    if (q0 < P) {
-      int q1 = min(P, q0 + PS);
-      const int cs = fl_cs(s);
-      const int row_i = 128 * s + 2 * lane + 1;
-      const unsigned ac = (row_i <= m) ? (a.A[a.a_off + row_i - 1] & 7u) : 0u;
-      const unsigned ac2 = (row_i + 1 <= m) ? (a.A[a.a_off + row_i] & 7u) : 0u;
-      unsigned plo, phi, plo2, phi2;
-      fl_profile_aff(a.match, a.mismatch, g, oe, ac, plo, phi);
-      fl_profile_aff(a.match, a.mismatch, g, oe, ac2, plo2, phi2);
-      const int Bin = (s == 0) ? P - 1 : min(P - 1, fl_bmax(s, m, n, 2));
-      const unsigned long long* sp = a.snap + ((size_t)s * a.nseg + seg) * 384 + lane;
-      const unsigned long long* brz = a.br + (size_t)(s > 0 ? s - 1 : 0) * a.brw;
-      const unsigned long long* brf = a.br + (size_t)(S + (s > 0 ? s - 1 : 0)) * a.brw;
-      const int qb = (s > 0) ? min(q1, Bin + 1) : q0;
-      const int nv = 16 * max(0, qb - q0);
-      int Zl = 0, E = 0, U = 0, Zl2 = 0, E2 = 0, Fo2 = 0;
-      bool ready = (nv == 0);
-      for (int t2 = 0; !ready && t2 < (int)(FL_SPIN_MAX >> 2); ++t2) {
-        const unsigned long long gz = gload(brz + 16 * q0 + nv - 1), gf = gload(brf + 16 * q0 + nv - 1);
-        ready = __ballot((unsigned)(gz >> 32) != ep || (unsigned)(gf >> 32) != ep) == 0;
-        if (!ready) fl_poll_sleep(t2);
-      }
-      if (ready) {
-        ready = false;
-        for (int tries = 0; !ready && tries < (int)FL_SPIN_MAX; ++tries) {
-          const unsigned long long x0 = gload(sp), x1 = gload(sp + 64), x2 = gload(sp + 128), x3 = gload(sp + 192),
-                                   x4 = gload(sp + 256), x5 = gload(sp + 320);
-          bool ok = ((unsigned)(x0 >> 32) == ep) && ((unsigned)(x1 >> 32) == ep) && ((unsigned)(x2 >> 32) == ep) &&
-                    ((unsigned)(x3 >> 32) == ep) && ((unsigned)(x4 >> 32) == ep) && ((unsigned)(x5 >> 32) == ep);
-          Zl = (int)(unsigned)x0;
-          E = (int)(unsigned)x1;
-          U = (int)(unsigned)x2;
-          Zl2 = (int)(unsigned)x3;
-          E2 = (int)(unsigned)x4;
-          Fo2 = (int)(unsigned)x5;
-          for (int v = lane; v < nv; v += 64) {
-            const unsigned long long gz = gload(brz + 16 * q0 + v), gf = gload(brf + 16 * q0 + v);
-            ok = ok && ((unsigned)(gz >> 32) == ep) && ((unsigned)(gf >> 32) == ep);
-            *L(lds + v) = (int)(unsigned)gz;
-            *L(lds + fl_p2vs(PS) + v) = (int)(unsigned)gf;
-          }
-          ready = __ballot(!ok) == 0;
-          if (!ready) __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      if (!ready) {
-        if (lane == 0) atomicExch(a.err, 15);
-        q1 = q0;
-      }
-      // row 0 (stripe 0): Z = g col - oe (H = 0), F~ = -inf
-      p2_stage<2, PS>(lds, s, nv, 16 * (q1 - q0), lane,
-                  [&](int v, int k) { return k == 0 ? g * (cs + 16 * q0 + v) - oe : MSA_NEG; }, a.cod + a.cod_off,
-                  a.cod_copy, cs, q0);
-      const int flb = g * (128 * s + 1 + cs + lane);  // e(i+j) of row 1 at step 0 (row 2: + g)
-      int best = INT32_MIN, bt = -1, best2 = INT32_MIN, bt2 = -1;
-      fl_v4u* dp = reinterpret_cast<fl_v4u*>(a.outDir + (size_t)a.out_off + (size_t)s * a.pmax * 2048) + lane;
-      for (int q = q0; q < q1; ++q) {
-        int INZ[16], INF[16];
-        {
-          const lds_int4* srz = reinterpret_cast<const lds_int4*>(L(lds + 16 * (q - q0)));
-          const lds_int4* srf = reinterpret_cast<const lds_int4*>(L(lds + fl_p2vs(PS) + 16 * (q - q0)));
+  if (G.live) {
+    unsigned plo, phi, plo2, phi2;
+    fl_profile_aff(a.match, a.mismatch, g, oe, G.ac, plo, phi);
+    fl_profile_aff(a.match, a.mismatch, g, oe, G.ac2, plo2, phi2);
+    int sn[6] = {};  // SNAP: row 1's Z left, E~ and diagonal Z, row 2's Z left, E~ and F~
+    unsigned long long tload;
+    const int q1 = p2_wait_load<6, 2, PS, true>(a, G, blk, lane, lds, sn, 0, tload) ? G.q1 : q0;
+    int Zl = sn[0], E = sn[1], U = sn[2], Zl2 = sn[3], E2 = sn[4], Fo2 = sn[5];
+    // row 0 (stripe 0): Z = g col - oe (H = 0), F~ = -inf
+    p2_stage<2, PS>(lds, s, G.nv, 16 * (q1 - q0), lane,
+                [&](int v, int k) { return k == 0 ? g * (cs + 16 * q0 + v) - oe : MSA_NEG; }, a.cod + a.cod_off,
+                a.cod_copy, cs, q0);
+    const int flb = g * (128 * s + 1 + cs + lane);  // e(i+j) of row 1 at step 0 (row 2: + g)
+    int best = INT32_MIN, bt = -1, best2 = INT32_MIN, bt2 = -1;
+    fl_v4u* dp = reinterpret_cast<fl_v4u*>(a.outDir + (size_t)a.out_off + (size_t)s * a.pmax * 2048) + lane;
+    for (int q = q0; q < q1; ++q) {
+      int INZ[16], INF[16];
+      p2_unpack<2, PS>(lds, q - q0, INZ, INF);
+      const fl_v4u c4 = p2_codes<PS>(lds, q - q0, lane);
+      const unsigned cw[4] = {c4.x, c4.y, c4.z, c4.w};
+      const int flq = flb + 16 * g * q;
+      unsigned dw1[4], dw2[4];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const fl_v4i vz = srz[u], vf = srf[u];
-            INZ[4 * u] = vz.x; INZ[4 * u + 1] = vz.y; INZ[4 * u + 2] = vz.z; INZ[4 * u + 3] = vz.w;
-            INF[4 * u] = vf.x; INF[4 * u + 1] = vf.y; INF[4 * u + 2] = vf.z; INF[4 * u + 3] = vf.w;
-          }
-        }
-        const fl_v4u c4 = p2_codes<PS>(lds, q - q0, lane);
-        const unsigned cw[4] = {c4.x, c4.y, c4.z, c4.w};
-        const int flq = flb + 16 * g * q;
-        unsigned dw1[4], dw2[4];
+      for (int u = 0; u < 4; ++u) {
+        const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
+        const unsigned s4b = __builtin_amdgcn_perm(phi2, plo2, cw[u]);
+        unsigned word1 = 0, word2 = 0;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
-          const unsigned s4b = __builtin_amdgcn_perm(phi2, plo2, cw[u]);
-          unsigned word1 = 0, word2 = 0;
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) {
-            const int kx = 4 * u + kk;
-            const int sc = ((int)(s4 << (24 - 8 * kk))) >> 24;
-            const int sb = ((int)(s4b << (24 - 8 * kk))) >> 24;
-            const int flr = flq + g * kx, flr2 = flr + g;
-            // row 1
-            const int upZ = dpp_shr1(INZ[kx], Zl2);
-            const int upF = dpp_shr1(INF[kx], Fo2);
-            const int e1 = imax(E, Zl);
-            const int f1 = imax(upF, upZ);
-            const int d1 = U + sc;
-            int h1 = imax3(imax(d1, flr), e1, f1);
-            asm("" : "+v"(h1));
-            const unsigned hs1 = (h1 == flr) ? 0u : (h1 == d1 ? 1u : (h1 == e1 ? 2u : 3u));
-            word1 |= (hs1 | ((e1 == Zl) ? 4u : 0u) | ((f1 == upZ) ? 8u : 0u)) << (8 * kk);
-            if (h1 - flr > best) { best = h1 - flr; bt = 16 * q + kx; }
-            const int zprev = Zl;
-            U = upZ;
-            E = e1;
-            Zl = h1 - oe;
-            // row 2: diagonal = row 1's previous Z, above = row 1's new cell
-            const int e2 = imax(E2, Zl2);
-            const int f2 = imax(f1, Zl);
-            const int d2 = zprev + sb;
-            int h2 = imax3(imax(d2, flr2), e2, f2);
-            asm("" : "+v"(h2));
-            const unsigned hs2 = (h2 == flr2) ? 0u : (h2 == d2 ? 1u : (h2 == e2 ? 2u : 3u));
-            word2 |= (hs2 | ((e2 == Zl2) ? 4u : 0u) | ((f2 == Zl) ? 8u : 0u)) << (8 * kk);
-            if (h2 - flr2 > best2) { best2 = h2 - flr2; bt2 = 16 * q + kx; }
-            E2 = e2;
-            Fo2 = f2;
-            Zl2 = h2 - oe;
-          }
-          dw1[u] = word1;
-          dw2[u] = word2;
+        for (int kk = 0; kk < 4; ++kk) {
+          const int kx = 4 * u + kk;
+          const int sc = p2_sbyte(s4, kk);
+          const int sb = p2_sbyte(s4b, kk);
+          const int flr = flq + g * kx, flr2 = flr + g;
+          // row 1
+          const int upZ = dpp_shr1(INZ[kx], Zl2);
+          const int upF = dpp_shr1(INF[kx], Fo2);
+          const int e1 = imax(E, Zl);
+          const int f1 = imax(upF, upZ);
+          const int d1 = U + sc;
+          int h1 = imax3(imax(d1, flr), e1, f1);
+          asm("" : "+v"(h1));
+          const unsigned hs1 = (h1 == flr) ? 0u : (h1 == d1 ? 1u : (h1 == e1 ? 2u : 3u));
+          word1 |= (hs1 | ((e1 == Zl) ? 4u : 0u) | ((f1 == upZ) ? 8u : 0u)) << (8 * kk);
+          if (h1 - flr > best) { best = h1 - flr; bt = 16 * q + kx; }
+          const int zprev = Zl;
+          U = upZ;
+          E = e1;
+          Zl = h1 - oe;
+          // row 2: diagonal = row 1's previous Z, above = row 1's new cell
+          const int e2 = imax(E2, Zl2);
+          const int f2 = imax(f1, Zl);
+          const int d2 = zprev + sb;
+          int h2 = imax3(imax(d2, flr2), e2, f2);
+          asm("" : "+v"(h2));
+          const unsigned hs2 = (h2 == flr2) ? 0u : (h2 == d2 ? 1u : (h2 == e2 ? 2u : 3u));
+          word2 |= (hs2 | ((e2 == Zl2) ? 4u : 0u) | ((f2 == Zl) ? 8u : 0u)) << (8 * kk);
+          if (h2 - flr2 > best2) { best2 = h2 - flr2; bt2 = 16 * q + kx; }
+          E2 = e2;
+          Fo2 = f2;
+          Zl2 = h2 - oe;
         }
-        if constexpr ((MSA_ABL & 8) == 0) {
-          __builtin_nontemporal_store(fl_v4u{dw1[0], dw1[1], dw1[2], dw1[3]}, dp + (size_t)q * 128);
-          __builtin_nontemporal_store(fl_v4u{dw2[0], dw2[1], dw2[2], dw2[3]}, dp + (size_t)q * 128 + 64);
-        }
+        dw1[u] = word1;
+        dw2[u] = word2;
       }
-      bb = (row_i <= m) ? best : INT32_MIN;
-      bi = row_i;
-      bj = cs + bt - lane;
-      if (row_i + 1 <= m && best2 > bb) {  // ties keep the upper row
-        bb = best2;
-        bi = row_i + 1;
-        bj = cs + bt2 - lane;
+      if constexpr ((MSA_ABL & 8) == 0) {
+        __builtin_nontemporal_store(fl_v4u{dw1[0], dw1[1], dw1[2], dw1[3]}, dp + (size_t)q * 128);
+        __builtin_nontemporal_store(fl_v4u{dw2[0], dw2[1], dw2[2], dw2[3]}, dp + (size_t)q * 128 + 64);
       }
     }
+    bb = (row_i <= m) ? best : INT32_MIN;
+    bi = row_i;
+    bj = cs + bt - lane;
+    if (row_i + 1 <= m && best2 > bb) {  // ties keep the upper row
+      bb = best2;
+      bi = row_i + 1;
+      bj = cs + bt2 - lane;
+    }
+    p2_stat_done(a, blk, lane, tload);
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int ob = __shfl_xor(bb, off), oi = __shfl_xor(bi, off), oj = __shfl_xor(bj, off);
-    if (ob > bb || (ob == bb && (oi < bi || (oi == bi && oj < bj)))) { bb = ob; bi = oi; bj = oj; }
-  }
-  fl_block_result(a.blk, a.best_key, blk, lane, bb, bi, bj, a.n);
+  p2_block_best(a, blk, lane, bb, bi, bj);
 }
 
 // Pass 2, Gotoh (the reference's main_alignment_function path): block (stripe s, segment
@@ -1883,157 +1887,82 @@ template <int CALLER>
 __device__ __attribute__((noinline)) void fill_block_got(kargs_c* ka, int blk, int lane, lds_int* lds) {
   constexpr int PS = fl_ps(CALLER);
   const FillArgs a = fill_args_of(ka);
-  const unsigned ep = a.ep;
   const int m = a.m, n = a.n, S = (m + 63) / 64, g = a.g, h4 = 4 * a.oe;
-  const int s = blk / a.nseg, seg = blk - s * a.nseg;
-  if (s < S) {
-    const int P = fl_P(s, m, n, 1);
-    const int q0 = seg * PS;
-    if (q0 < P) {
-      int q1 = min(P, q0 + PS);
-      const int cs = fl_cs(s);
-      const int row_i = 64 * s + lane + 1;
-      const unsigned ac = (row_i <= m) ? (a.A[a.a_off + row_i - 1] & 7u) : 0u;
-      unsigned plo, phi;
-      fl_profile_got(g, ac, plo, phi);
-      const int Bin = (s == 0) ? P - 1 : min(P - 1, fl_bmax(s, m, n, 1));
-      const unsigned long long* sp = a.snap + ((size_t)s * a.nseg + seg) * 256 + lane;
-      const unsigned long long* brz = a.br + (size_t)(s > 0 ? s - 1 : 0) * a.brw;
-      const unsigned long long* brf = a.br + (size_t)(S + (s > 0 ? s - 1 : 0)) * a.brw;
-      const int qb = (s > 0) ? min(q1, Bin + 1) : q0;
-      const int nv = 16 * max(0, qb - q0);
-      int Hs = 0, Rs = 0, Ds = 0, U = 0;
-#ifdef MSA_STAMPS
-      const unsigned long long tp0 = __builtin_amdgcn_s_memtime();
-      unsigned long long tp1 = tp0;
-#endif
-      bool ready = (nv == 0);
-      for (int t2 = 0; !ready && t2 < (int)(FL_SPIN_MAX >> 2); ++t2) {
-        const unsigned long long gz = gload(brz + 16 * q0 + nv - 1), gf = gload(brf + 16 * q0 + nv - 1);
-        ready = __ballot((unsigned)(gz >> 32) != ep || (unsigned)(gf >> 32) != ep) == 0;
-        if (!ready) fl_poll_sleep(t2);
-      }
-#ifdef MSA_STAMPS
-      tp1 = __builtin_amdgcn_s_memtime();
-#endif
-      if (ready) {
-        ready = false;
-        for (int tries = 0; !ready && tries < (int)FL_SPIN_MAX; ++tries) {
-          const unsigned long long x0 = gload(sp), x1 = gload(sp + 64), x2 = gload(sp + 128), x3 = gload(sp + 192);
-          bool ok = ((unsigned)(x0 >> 32) == ep) && ((unsigned)(x1 >> 32) == ep) && ((unsigned)(x2 >> 32) == ep) &&
-                    ((unsigned)(x3 >> 32) == ep);
-          Hs = (int)(unsigned)x0;
-          Rs = (int)(unsigned)x1;
-          Ds = (int)(unsigned)x2;
-          U = (int)(unsigned)x3;
-          for (int v = lane; v < nv; v += 64) {
-            const unsigned long long gz = gload(brz + 16 * q0 + v), gf = gload(brf + 16 * q0 + v);
-            ok = ok && ((unsigned)(gz >> 32) == ep) && ((unsigned)(gf >> 32) == ep);
-            *L(lds + v) = (int)(unsigned)gz;
-            *L(lds + fl_p2vs(PS) + v) = (int)(unsigned)gf;
+  const P2Geom G = p2_geom<1, PS, 256>(a, blk, lane);
+  const int s = G.s, q0 = G.q0, cs = G.cs, row_i = G.row_i;
+  if (G.live) {
+    unsigned plo, phi;
+    fl_profile_got(g, G.ac, plo, phi);
+    int sn[4] = {};  // SNAP: H~, R~, D~, diagonal H~
+    unsigned long long tload;
+    const int q1 = p2_wait_load<4, 2, PS, true>(a, G, blk, lane, lds, sn, 0, tload) ? G.q1 : q0;
+    int Hs = sn[0], Rs = sn[1], Ds = sn[2], U = sn[3];
+    // row 0 (stripe 0), tagged and shifted: H~ 3 at column 0, 2 - 4h right of it; D~ 3 - 4h, 2 - 8h
+    p2_stage<2, PS>(lds, s, G.nv, 16 * (q1 - q0), lane,
+                [&](int v, int k) {
+                  const int col = cs + 16 * q0 + v;
+                  return col < 0 ? MSA_NEG : (k == 0 ? (col == 0 ? 3 : 2 - h4) : (col == 0 ? 3 - h4 : 2 - 2 * h4));
+                },
+                a.cod + a.cod_off, a.cod_copy, cs, q0);
+    const int tmin = 1 - cs + lane;
+    // the final cell (m, n): the lane of row m at step n - cs + lane of the last stripe
+    const int tf = (row_i == m) ? n - cs + lane : -1;
+    fl_v4u* dp = reinterpret_cast<fl_v4u*>(a.outDir + (size_t)a.out_off + (size_t)s * a.pmax * 1024) + lane;
+    auto phase = [&](const int q, auto HEAD_, auto CAP_) __attribute__((always_inline)) {
+      constexpr bool HEAD = decltype(HEAD_)::value;  // lanes left of column 1 hold the border
+      constexpr bool CAP = decltype(CAP_)::value;    // the phase holds cell (m, n)
+      int INZ[16], INF[16];
+      p2_unpack<2, PS>(lds, q - q0, INZ, INF);
+      const fl_v4u c4 = p2_codes<PS>(lds, q - q0, lane);
+      const unsigned cw[4] = {c4.x, c4.y, c4.z, c4.w};
+      unsigned dw[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
+        unsigned word = 0;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+          const int kx = 4 * u + kk;
+          const int sc = p2_sbyte(s4, kk);
+          const int uH = dpp_shr1(INZ[kx], Hs);
+          const int uD = dpp_shr1(INF[kx], Ds);
+          const int t1 = (int)((unsigned)U | 3u) + sc;
+          const int t2 = (int)(((unsigned)Rs & ~3u) | 2u);
+          const int t3 = (int)(((unsigned)uD & ~3u) | 1u);
+          const unsigned dir = ((unsigned)U & 3u) | (((unsigned)Rs & 3u) << 2) | (((unsigned)uD & 3u) << 4);
+          word |= dir << (8 * kk);
+          const int t1h = t1 - h4;
+          int hh = imax3(t1, t2, t3);
+          int rr = imax3(t1h, t2, t3 - h4);
+          int dd = imax3(t1h, t2 - h4, t3);
+          asm("" : "+v"(hh));
+          if constexpr (HEAD) {
+            const bool before = 16 * q + kx < tmin;
+            hh = before ? 1 - h4 : hh;
+            rr = before ? 1 - 2 * h4 : rr;
+            dd = before ? 1 - h4 : dd;
           }
-          ready = __ballot(!ok) == 0;
-          if (!ready) __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      if (!ready) {
-        if (lane == 0) atomicExch(a.err, 15);
-        q1 = q0;
-      }
-      // row 0 (stripe 0), tagged and shifted: H~ 3 at column 0, 2 - 4h right of it; D~ 3 - 4h, 2 - 8h
-      p2_stage<2, PS>(lds, s, nv, 16 * (q1 - q0), lane,
-                  [&](int v, int k) {
-                    const int col = cs + 16 * q0 + v;
-                    return col < 0 ? MSA_NEG : (k == 0 ? (col == 0 ? 3 : 2 - h4) : (col == 0 ? 3 - h4 : 2 - 2 * h4));
-                  },
-                  a.cod + a.cod_off, a.cod_copy, cs, q0);
-#ifdef MSA_STAMPS
-      const unsigned long long tp2 = __builtin_amdgcn_s_memtime();
-#endif
-      const int tmin = 1 - cs + lane;
-      // the final cell (m, n): the lane of row m at step n - cs + lane of the last stripe
-      const int tf = (row_i == m) ? n - cs + lane : -1;
-      fl_v4u* dp = reinterpret_cast<fl_v4u*>(a.outDir + (size_t)a.out_off + (size_t)s * a.pmax * 1024) + lane;
-      auto phase = [&](const int q, auto HEAD_, auto CAP_) __attribute__((always_inline)) {
-        constexpr bool HEAD = decltype(HEAD_)::value;  // lanes left of column 1 hold the border
-        constexpr bool CAP = decltype(CAP_)::value;    // the phase holds cell (m, n)
-        int INZ[16], INF[16];
-        {
-          const lds_int4* srz = reinterpret_cast<const lds_int4*>(L(lds + 16 * (q - q0)));
-          const lds_int4* srf = reinterpret_cast<const lds_int4*>(L(lds + fl_p2vs(PS) + 16 * (q - q0)));
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const fl_v4i vz = srz[u], vf = srf[u];
-            INZ[4 * u] = vz.x; INZ[4 * u + 1] = vz.y; INZ[4 * u + 2] = vz.z; INZ[4 * u + 3] = vz.w;
-            INF[4 * u] = vf.x; INF[4 * u + 1] = vf.y; INF[4 * u + 2] = vf.z; INF[4 * u + 3] = vf.w;
-          }
-        }
-        const fl_v4u c4 = p2_codes<PS>(lds, q - q0, lane);
-        const unsigned cw[4] = {c4.x, c4.y, c4.z, c4.w};
-        unsigned dw[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
-          unsigned word = 0;
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) {
-            const int kx = 4 * u + kk;
-            const int sc = ((int)(s4 << (24 - 8 * kk))) >> 24;
-            const int uH = dpp_shr1(INZ[kx], Hs);
-            const int uD = dpp_shr1(INF[kx], Ds);
-            const int t1 = (int)((unsigned)U | 3u) + sc;
-            const int t2 = (int)(((unsigned)Rs & ~3u) | 2u);
-            const int t3 = (int)(((unsigned)uD & ~3u) | 1u);
-            const unsigned dir = ((unsigned)U & 3u) | (((unsigned)Rs & 3u) << 2) | (((unsigned)uD & 3u) << 4);
-            word |= dir << (8 * kk);
-            const int t1h = t1 - h4;
-            int hh = imax3(t1, t2, t3);
-            int rr = imax3(t1h, t2, t3 - h4);
-            int dd = imax3(t1h, t2 - h4, t3);
-            asm("" : "+v"(hh));
-            if constexpr (HEAD) {
-              const bool before = 16 * q + kx < tmin;
-              hh = before ? 1 - h4 : hh;
-              rr = before ? 1 - 2 * h4 : rr;
-              dd = before ? 1 - h4 : dd;
+          if constexpr (CAP) {
+            if (16 * q + kx == tf) {
+              const int gmn = g * (m + n);  // unshift
+              msa_stripe_meta* md = a.meta + a.stripe0 + S - 1;
+              md->fin[0] = (t1 >> 2) - gmn;
+              md->fin[1] = (t2 >> 2) - gmn;
+              md->fin[2] = (t3 >> 2) - gmn;
+              md->has_fin = 1;
             }
-            if constexpr (CAP) {
-              if (16 * q + kx == tf) {
-                const int gmn = g * (m + n);  // unshift
-                msa_stripe_meta* md = a.meta + a.stripe0 + S - 1;
-                md->fin[0] = (t1 >> 2) - gmn;
-                md->fin[1] = (t2 >> 2) - gmn;
-                md->fin[2] = (t3 >> 2) - gmn;
-                md->has_fin = 1;
-              }
-            }
-            U = uH;
-            Hs = hh;
-            Rs = rr;
-            Ds = dd;
           }
-          dw[u] = word;
+          U = uH;
+          Hs = hh;
+          Rs = rr;
+          Ds = dd;
         }
-        __builtin_nontemporal_store(fl_v4u{dw[0], dw[1], dw[2], dw[3]}, dp + (size_t)q * 64);
-      };
-      using T_ = std::true_type;
-      using F_ = std::false_type;
-      for (int q = q0; q < q1; ++q) {
-        const bool cap = __ballot(tf >= 16 * q && tf < 16 * q + 16) != 0ull;
-        if (cap) phase(q, T_{}, T_{});
-        else if (q < 6) phase(q, T_{}, F_{});
-        else phase(q, F_{}, F_{});
+        dw[u] = word;
       }
-#ifdef MSA_STAMPS
-      const unsigned long long tp3 = __builtin_amdgcn_s_memtime();
-      if ((blk & 15) == 0) {  // a sample of the blocks (the atomics would serialize all of them)
-        FL_P2STAT(a, 0, tp1 - tp0);
-        FL_P2STAT(a, 1, tp2 - tp1);
-        FL_P2STAT(a, 2, tp3 - tp2);
-        FL_P2STAT(a, 3, 1);
-      }
-#endif
-    }
+      __builtin_nontemporal_store(fl_v4u{dw[0], dw[1], dw[2], dw[3]}, dp + (size_t)q * 64);
+    };
+    p2_got_phases(q0, q1, tf, phase);
+    p2_stat_done(a, blk, lane, tload);
   }
   if (lane == 0) a.blk[blk] = make_int4(0, 0, 0, 0);
 }
@@ -2047,184 +1976,124 @@ template <int CALLER>
 __device__ __attribute__((noinline)) void fill_block_got2(kargs_c* ka, int blk, int lane, lds_int* lds) {
   constexpr int PS = fl_ps(CALLER);
   const FillArgs a = fill_args_of(ka);
-  const unsigned ep = a.ep;
-  const int m = a.m, n = a.n, S = (m + 127) / 128, g = a.g, h4 = 4 * a.oe;
-  const int s = blk / a.nseg, seg = blk - s * a.nseg;
-  if (s < S) {
-    const int P = fl_P(s, m, n, 2);
-    const int q0 = seg * PS;
-    if (q0 < P) {
-      int q1 = min(P, q0 + PS);
-      const int cs = fl_cs(s);
-      const int row_i = 128 * s + 2 * lane + 1;
-      const unsigned ac = (row_i <= m) ? (a.A[a.a_off + row_i - 1] & 7u) : 0u;
-      const unsigned ac2 = (row_i + 1 <= m) ? (a.A[a.a_off + row_i] & 7u) : 0u;
-      unsigned plo, phi, plo2, phi2;
-      fl_profile_got(g, ac, plo, phi);
-      fl_profile_got(g, ac2, plo2, phi2);
-      const int Bin = (s == 0) ? P - 1 : min(P - 1, fl_bmax(s, m, n, 2));
-      const unsigned long long* sp = a.snap + ((size_t)s * a.nseg + seg) * 384 + lane;
-      const unsigned long long* brz = a.br + (size_t)(s > 0 ? s - 1 : 0) * a.brw;
-      const unsigned long long* brf = a.br + (size_t)(S + (s > 0 ? s - 1 : 0)) * a.brw;
-      const int qb = (s > 0) ? min(q1, Bin + 1) : q0;
-      const int nv = 16 * max(0, qb - q0);
-      int U = 0, Hs1 = 0, Rs1 = 0, Hs2 = 0, Rs2 = 0, Ds2 = 0;
-      bool ready = (nv == 0);
-      for (int t2 = 0; !ready && t2 < (int)(FL_SPIN_MAX >> 2); ++t2) {
-        const unsigned long long gz = gload(brz + 16 * q0 + nv - 1), gf = gload(brf + 16 * q0 + nv - 1);
-        ready = __ballot((unsigned)(gz >> 32) != ep || (unsigned)(gf >> 32) != ep) == 0;
-        if (!ready) fl_poll_sleep(t2);
-      }
-      if (ready) {
-        ready = false;
-        for (int tries = 0; !ready && tries < (int)FL_SPIN_MAX; ++tries) {
-          const unsigned long long x0 = gload(sp), x1 = gload(sp + 64), x2 = gload(sp + 128), x3 = gload(sp + 192),
-                                   x4 = gload(sp + 256), x5 = gload(sp + 320);
-          bool ok = ((unsigned)(x0 >> 32) == ep) && ((unsigned)(x1 >> 32) == ep) && ((unsigned)(x2 >> 32) == ep) &&
-                    ((unsigned)(x3 >> 32) == ep) && ((unsigned)(x4 >> 32) == ep) && ((unsigned)(x5 >> 32) == ep);
-          // R~ and D~ carried + 4h, as in pass 1 (the tag bits are unchanged): 2 subtractions per
-          // row-step instead of 3
-          Hs1 = (int)(unsigned)x0;
-          Rs1 = (int)(unsigned)x1 + h4;
-          U = (int)(unsigned)x2;
-          Hs2 = (int)(unsigned)x3;
-          Rs2 = (int)(unsigned)x4 + h4;
-          Ds2 = (int)(unsigned)x5 + h4;
-          for (int v = lane; v < nv; v += 64) {
-            const unsigned long long gz = gload(brz + 16 * q0 + v), gf = gload(brf + 16 * q0 + v);
-            ok = ok && ((unsigned)(gz >> 32) == ep) && ((unsigned)(gf >> 32) == ep);
-            *L(lds + v) = (int)(unsigned)gz;
-            *L(lds + fl_p2vs(PS) + v) = (int)(unsigned)gf + h4;
-          }
-          ready = __ballot(!ok) == 0;
-          if (!ready) __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      if (!ready) {
-        if (lane == 0) atomicExch(a.err, 15);
-        q1 = q0;
-      }
-      // row 0 (stripe 0), tagged and shifted: H~ 3 at column 0, 2 - 4h right of it; D~ + 4h 3, 2 - 4h
-      p2_stage<2, PS>(lds, s, nv, 16 * (q1 - q0), lane,
-                  [&](int v, int k) {
-                    const int col = cs + 16 * q0 + v;
-                    return col < 0 ? MSA_NEG : (k == 0 ? (col == 0 ? 3 : 2 - h4) : (col == 0 ? 3 : 2 - h4));
-                  },
-                  a.cod + a.cod_off, a.cod_copy, cs, q0);
-      const int tmin = 1 - cs + lane;
-      // the final cell (m, n): row m is row 1 or row 2 of one lane of the last stripe
-      const int tf1 = (row_i == m) ? n - cs + lane : -1;
-      const int tf2 = (row_i + 1 == m) ? n - cs + lane : -1;
-      const int tf = max(tf1, tf2);
-      fl_v4u* dp = reinterpret_cast<fl_v4u*>(a.outDir + (size_t)a.out_off + (size_t)s * a.pmax * 2048) + lane;
-      auto phase = [&](const int q, auto HEAD_, auto CAP_) __attribute__((always_inline)) {
-        constexpr bool HEAD = decltype(HEAD_)::value;  // lanes left of column 1 hold the border
-        constexpr bool CAP = decltype(CAP_)::value;    // the phase holds cell (m, n)
-        int INZ[16], INF[16];
-        {
-          const lds_int4* srz = reinterpret_cast<const lds_int4*>(L(lds + 16 * (q - q0)));
-          const lds_int4* srf = reinterpret_cast<const lds_int4*>(L(lds + fl_p2vs(PS) + 16 * (q - q0)));
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const fl_v4i vz = srz[u], vf = srf[u];
-            INZ[4 * u] = vz.x; INZ[4 * u + 1] = vz.y; INZ[4 * u + 2] = vz.z; INZ[4 * u + 3] = vz.w;
-            INF[4 * u] = vf.x; INF[4 * u + 1] = vf.y; INF[4 * u + 2] = vf.z; INF[4 * u + 3] = vf.w;
-          }
-        }
-        const fl_v4u c4 = p2_codes<PS>(lds, q - q0, lane);
-        const unsigned cw[4] = {c4.x, c4.y, c4.z, c4.w};
-        unsigned dw1[4], dw2[4];
-        // four cells' direction bytes, tags of their inputs H~ diag | R~ left << 2 | D~ up << 4: the
-        // low bytes of the four H~, R~ and D~ gathered by v_perm (3 each), then two byte-wise bfi
-        // merges and one mask -- 14 ops per 4 cells instead of 5 per cell
-        auto gather4 = [](const int* b) __attribute__((always_inline)) {
-          const unsigned lo = __builtin_amdgcn_perm((unsigned)b[1], (unsigned)b[0], 0x0c0c0400u);
-          const unsigned hi = __builtin_amdgcn_perm((unsigned)b[3], (unsigned)b[2], 0x0c0c0400u);
-          return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
-        };
-        auto dword = [&](const int* h, const int* r, const int* d) __attribute__((always_inline)) {
-          const unsigned HT = gather4(h), RT = gather4(r), DT = gather4(d), M = 0x03030303u;
-          unsigned x, y;
-          asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(x) : "s"(M), "v"(RT), "v"(DT << 2));
-          asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(y) : "s"(M), "v"(HT), "v"(x << 2));
-          return y & 0x3f3f3f3fu;
-        };
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
-          const unsigned s4b = __builtin_amdgcn_perm(phi2, plo2, cw[u]);
-          int h1t[4], r1t[4], d1t[4], h2t[4], r2t[4], d2t[4];
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) {
-            const int kx = 4 * u + kk;
-            const int sc = ((int)(s4 << (24 - 8 * kk))) >> 24;
-            const int sb = ((int)(s4b << (24 - 8 * kk))) >> 24;
-            // row 1 (R~ / D~ carried + 4h: Rs1, uD, and the results rr, dd)
-            const int uH = dpp_shr1(INZ[kx], Hs2);
-            const int uD = dpp_shr1(INF[kx], Ds2);
-            const int t1 = (int)((unsigned)U | 3u) + sc;
-            const int t2p = (int)(((unsigned)Rs1 & ~3u) | 2u);
-            const int t3p = (int)(((unsigned)uD & ~3u) | 1u);
-            h1t[kk] = U; r1t[kk] = Rs1; d1t[kk] = uD;
-            const int t2 = t2p - h4, t3 = t3p - h4;
-            int hh1 = vmax3(t1, t2, t3);
-            int rr1 = vmax3(t1, t2p, t3);
-            int dd1 = vmax3(t1, t2, t3p);
-            // row 2: diagonal = row 1's previous H~, above = row 1's new cell
-            const bool before = HEAD && (16 * q + kx < tmin);
-            if constexpr (HEAD) {
-              hh1 = before ? 1 - h4 : hh1;
-              rr1 = before ? 1 - h4 : rr1;
-              dd1 = before ? 1 : dd1;
-            }
-            const int s1 = (int)((unsigned)Hs1 | 3u) + sb;
-            const int s2p = (int)(((unsigned)Rs2 & ~3u) | 2u);
-            const int s3p = (int)(((unsigned)dd1 & ~3u) | 1u);
-            h2t[kk] = Hs1; r2t[kk] = Rs2; d2t[kk] = dd1;
-            const int s2 = s2p - h4, s3 = s3p - h4;
-            int hh2 = vmax3(s1, s2, s3);
-            int rr2 = vmax3(s1, s2p, s3);
-            int dd2 = vmax3(s1, s2, s3p);
-            if constexpr (HEAD) {
-              hh2 = before ? 1 - h4 : hh2;
-              rr2 = before ? 1 - h4 : rr2;
-              dd2 = before ? 1 : dd2;
-            }
-            if constexpr (CAP) {
-              if (16 * q + kx == tf) {
-                const int gmn = g * (m + n);  // unshift
-                // (the slot reduce_pairs_kernel reads: the last 64-row stripe's meta)
-                msa_stripe_meta* md = a.meta + a.stripe0 + (m + 63) / 64 - 1;
-                md->fin[0] = ((tf1 >= 0 ? t1 : s1) >> 2) - gmn;
-                md->fin[1] = ((tf1 >= 0 ? t2 : s2) >> 2) - gmn;
-                md->fin[2] = ((tf1 >= 0 ? t3 : s3) >> 2) - gmn;
-                md->has_fin = 1;
-              }
-            }
-            U = uH;
-            Hs1 = hh1;
-            Rs1 = rr1;
-            Hs2 = hh2;
-            Rs2 = rr2;
-            Ds2 = dd2;
-          }
-          dw1[u] = dword(h1t, r1t, d1t);
-          dw2[u] = dword(h2t, r2t, d2t);
-        }
-        if constexpr ((MSA_ABL & 8) == 0) {
-          __builtin_nontemporal_store(fl_v4u{dw1[0], dw1[1], dw1[2], dw1[3]}, dp + (size_t)q * 128);
-          __builtin_nontemporal_store(fl_v4u{dw2[0], dw2[1], dw2[2], dw2[3]}, dp + (size_t)q * 128 + 64);
-        }
+  const int m = a.m, n = a.n, g = a.g, h4 = 4 * a.oe;
+  const P2Geom G = p2_geom<2, PS, 384>(a, blk, lane);
+  const int s = G.s, q0 = G.q0, cs = G.cs, row_i = G.row_i;
+  if (G.live) {
+    unsigned plo, phi, plo2, phi2;
+    fl_profile_got(g, G.ac, plo, phi);
+    fl_profile_got(g, G.ac2, plo2, phi2);
+    int sn[6] = {};  // SNAP: row 1's H~ and R~, the diagonal H~, row 2's H~, R~ and D~
+    unsigned long long tload;
+    // R~ and D~ carried + 4h, as in pass 1 (the tag bits are unchanged): 2 subtractions per
+    // row-step instead of 3
+    const int q1 = p2_wait_load<6, 2, PS, true>(a, G, blk, lane, lds, sn, h4, tload) ? G.q1 : q0;
+    int Hs1 = sn[0], Rs1 = sn[1] + h4, U = sn[2], Hs2 = sn[3], Rs2 = sn[4] + h4, Ds2 = sn[5] + h4;
+    // row 0 (stripe 0), tagged and shifted: H~ 3 at column 0, 2 - 4h right of it; D~ + 4h 3, 2 - 4h
+    p2_stage<2, PS>(lds, s, G.nv, 16 * (q1 - q0), lane,
+                [&](int v, int k) {
+                  const int col = cs + 16 * q0 + v;
+                  return col < 0 ? MSA_NEG : (k == 0 ? (col == 0 ? 3 : 2 - h4) : (col == 0 ? 3 : 2 - h4));
+                },
+                a.cod + a.cod_off, a.cod_copy, cs, q0);
+    const int tmin = 1 - cs + lane;
+    // the final cell (m, n): row m is row 1 or row 2 of one lane of the last stripe
+    const int tf1 = (row_i == m) ? n - cs + lane : -1;
+    const int tf2 = (row_i + 1 == m) ? n - cs + lane : -1;
+    const int tf = max(tf1, tf2);
+    fl_v4u* dp = reinterpret_cast<fl_v4u*>(a.outDir + (size_t)a.out_off + (size_t)s * a.pmax * 2048) + lane;
+    auto phase = [&](const int q, auto HEAD_, auto CAP_) __attribute__((always_inline)) {
+      constexpr bool HEAD = decltype(HEAD_)::value;  // lanes left of column 1 hold the border
+      constexpr bool CAP = decltype(CAP_)::value;    // the phase holds cell (m, n)
+      int INZ[16], INF[16];
+      p2_unpack<2, PS>(lds, q - q0, INZ, INF);
+      const fl_v4u c4 = p2_codes<PS>(lds, q - q0, lane);
+      const unsigned cw[4] = {c4.x, c4.y, c4.z, c4.w};
+      unsigned dw1[4], dw2[4];
+      // four cells' direction bytes, tags of their inputs H~ diag | R~ left << 2 | D~ up << 4: the
+      // low bytes of the four H~, R~ and D~ gathered by v_perm (3 each), then two byte-wise bfi
+      // merges and one mask -- 14 ops per 4 cells instead of 5 per cell
+      auto gather4 = [](const int* b) __attribute__((always_inline)) {
+        const unsigned lo = __builtin_amdgcn_perm((unsigned)b[1], (unsigned)b[0], 0x0c0c0400u);
+        const unsigned hi = __builtin_amdgcn_perm((unsigned)b[3], (unsigned)b[2], 0x0c0c0400u);
+        return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
       };
-      using T_ = std::true_type;
-      using F_ = std::false_type;
-      for (int q = q0; q < q1; ++q) {
-        const bool cap = __ballot(tf >= 16 * q && tf < 16 * q + 16) != 0ull;
-        if (cap) phase(q, T_{}, T_{});
-        else if (q < 6) phase(q, T_{}, F_{});
-        else phase(q, F_{}, F_{});
+      auto dword = [&](const int* h, const int* r, const int* d) __attribute__((always_inline)) {
+        const unsigned HT = gather4(h), RT = gather4(r), DT = gather4(d), M = 0x03030303u;
+        unsigned x, y;
+        asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(x) : "s"(M), "v"(RT), "v"(DT << 2));
+        asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(y) : "s"(M), "v"(HT), "v"(x << 2));
+        return y & 0x3f3f3f3fu;
+      };
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
+        const unsigned s4b = __builtin_amdgcn_perm(phi2, plo2, cw[u]);
+        int h1t[4], r1t[4], d1t[4], h2t[4], r2t[4], d2t[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+          const int kx = 4 * u + kk;
+          const int sc = p2_sbyte(s4, kk);
+          const int sb = p2_sbyte(s4b, kk);
+          // row 1 (R~ / D~ carried + 4h: Rs1, uD, and the results rr, dd)
+          const int uH = dpp_shr1(INZ[kx], Hs2);
+          const int uD = dpp_shr1(INF[kx], Ds2);
+          const int t1 = (int)((unsigned)U | 3u) + sc;
+          const int t2p = (int)(((unsigned)Rs1 & ~3u) | 2u);
+          const int t3p = (int)(((unsigned)uD & ~3u) | 1u);
+          h1t[kk] = U; r1t[kk] = Rs1; d1t[kk] = uD;
+          const int t2 = t2p - h4, t3 = t3p - h4;
+          int hh1 = vmax3(t1, t2, t3);
+          int rr1 = vmax3(t1, t2p, t3);
+          int dd1 = vmax3(t1, t2, t3p);
+          // row 2: diagonal = row 1's previous H~, above = row 1's new cell
+          const bool before = HEAD && (16 * q + kx < tmin);
+          if constexpr (HEAD) {
+            hh1 = before ? 1 - h4 : hh1;
+            rr1 = before ? 1 - h4 : rr1;
+            dd1 = before ? 1 : dd1;
+          }
+          const int s1 = (int)((unsigned)Hs1 | 3u) + sb;
+          const int s2p = (int)(((unsigned)Rs2 & ~3u) | 2u);
+          const int s3p = (int)(((unsigned)dd1 & ~3u) | 1u);
+          h2t[kk] = Hs1; r2t[kk] = Rs2; d2t[kk] = dd1;
+          const int s2 = s2p - h4, s3 = s3p - h4;
+          int hh2 = vmax3(s1, s2, s3);
+          int rr2 = vmax3(s1, s2p, s3);
+          int dd2 = vmax3(s1, s2, s3p);
+          if constexpr (HEAD) {
+            hh2 = before ? 1 - h4 : hh2;
+            rr2 = before ? 1 - h4 : rr2;
+            dd2 = before ? 1 : dd2;
+          }
+          if constexpr (CAP) {
+            if (16 * q + kx == tf) {
+              const int gmn = g * (m + n);  // unshift
+              // (the slot reduce_pairs_kernel reads: the last 64-row stripe's meta)
+              msa_stripe_meta* md = a.meta + a.stripe0 + (m + 63) / 64 - 1;
+              md->fin[0] = ((tf1 >= 0 ? t1 : s1) >> 2) - gmn;
+              md->fin[1] = ((tf1 >= 0 ? t2 : s2) >> 2) - gmn;
+              md->fin[2] = ((tf1 >= 0 ? t3 : s3) >> 2) - gmn;
+              md->has_fin = 1;
+            }
+          }
+          U = uH;
+          Hs1 = hh1;
+          Rs1 = rr1;
+          Hs2 = hh2;
+          Rs2 = rr2;
+          Ds2 = dd2;
+        }
+        dw1[u] = dword(h1t, r1t, d1t);
+        dw2[u] = dword(h2t, r2t, d2t);
       }
-    }
+      if constexpr ((MSA_ABL & 8) == 0) {
+        __builtin_nontemporal_store(fl_v4u{dw1[0], dw1[1], dw1[2], dw1[3]}, dp + (size_t)q * 128);
+        __builtin_nontemporal_store(fl_v4u{dw2[0], dw2[1], dw2[2], dw2[3]}, dp + (size_t)q * 128 + 64);
+      }
+    };
+    p2_got_phases(q0, q1, tf, phase);
+    p2_stat_done(a, blk, lane, tload);
   }
   if (lane == 0) a.blk[blk] = make_int4(0, 0, 0, 0);
 }

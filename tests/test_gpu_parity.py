@@ -759,6 +759,11 @@ def test_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring):
     direction byte as the one-pass stripe kernel (the same pair as a one-pair batch) at every cell of the
     matrix, and the same score and first-maximum end cell.  Scores >= 0 run pass 1 with the zero floor in
     its head phases only; negative mismatches with it in every step."""
+    check_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring)
+
+
+def check_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring, rows=2):
+    """test_sw_affine_flow_dir_bytes' comparison for a flow plan of `rows` rows per lane; returns that plan."""
     import torch
     from cse305_parallel_sequence_alignment_amd.plan import Plan
 
@@ -779,11 +784,12 @@ def test_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring):
         r = pl.results()[0]
         info = pl.run_info()
         out.append((pl.deskew_dir(D.cpu().numpy(), 0, pl.stripe_meta()), r["score"], tuple(r["end"]), info["mode"],
-                    pl.geom[0].rows_per_lane))
-    (d1, s1, e1, mode1, r1), (d0, s0, e0, _, _) = out
-    assert mode1 == "flow" and r1 == 2  # the flow kernel's two-rows-per-lane layout
+                    pl.geom[0].rows_per_lane, pl))
+    (d1, s1, e1, mode1, r1, flow_plan), (d0, s0, e0, _, _, _) = out
+    assert mode1 == "flow" and r1 == rows  # (default: the flow kernel's two-rows-per-lane layout)
     assert (s1, e1) == (s0, e0)
     assert np.array_equal(d1[1:, 1:], d0[1:, 1:])
+    return flow_plan
 
 
 @pytest.mark.parametrize("m,n", [(3000, 2900), (1500, 4100), (4097, 130)])
@@ -891,6 +897,11 @@ def test_gotoh_flow_dir_bytes(dev, LB, gh, m, n):
     """The two-pass Gotoh flow kernel (single pair, start type -1, direction bytes: run_info mode 1) writes
     the same tag byte as the one-pass stripe kernel (the same pair as a one-pair batch) at every cell, and
     the same final-cell tables (score, find_alignment's end rule)."""
+    check_gotoh_flow_dir_bytes(dev, LB, gh, m, n)
+
+
+def check_gotoh_flow_dir_bytes(dev, LB, gh, m, n):
+    """test_gotoh_flow_dir_bytes' comparison; returns the flow plan."""
     import torch
     from cse305_parallel_sequence_alignment_amd.plan import Plan
 
@@ -905,11 +916,12 @@ def test_gotoh_flow_dir_bytes(dev, LB, gh, m, n):
         pl.run(_dev(A, dev), _dev(B, dev), D)
         r = pl.results()[0]
         out.append((pl.deskew_dir(D.cpu().numpy(), 0, pl.stripe_meta()), r["score"], tuple(r["fin"]),
-                    pl.run_info()["mode"]))
-    (d1, s1, f1, mode1), (d0, s0, f0, _) = out
+                    pl.run_info()["mode"], pl))
+    (d1, s1, f1, mode1, flow_plan), (d0, s0, f0, _, _) = out
     assert mode1 == "flow"
     assert (s1, f1) == (s0, f0)
     assert np.array_equal(d1[1:, 1:] & 63, d0[1:, 1:] & 63)
+    return flow_plan
 
 
 def _gotoh_tags(T1, T2, T3, g, h):
@@ -980,6 +992,11 @@ def test_flow_fill_launch_tall_pairs(oracle, dev, LB, kind):
     chooses per algorithm: SW linear with H (track_end off / on), SW affine with direction bytes (scores
     >= 0, and with a negative mismatch) and the reference's Gotoh.  Checked against the oracle: H checksum
     and score; score, end, begin and CIGAR of the device traceback; the printed alignment text."""
+    check_flow_fill_launch_tall_pair(oracle, dev, LB, kind)
+
+
+def check_flow_fill_launch_tall_pair(oracle, dev, LB, kind):
+    """test_flow_fill_launch_tall_pairs' checks for one kind; returns the plan."""
     import torch
     from cse305_parallel_sequence_alignment_amd import api
     from cse305_parallel_sequence_alignment_amd.plan import Plan
@@ -1037,6 +1054,7 @@ def test_flow_fill_launch_tall_pairs(oracle, dev, LB, kind):
         d = pl.deskew_dir(D.cpu().numpy(), 0, pl.stripe_meta())
         assert np.array_equal(d[1:, 1:] & 63, _gotoh_tags(T1, T2, T3, 1.0, 2.0))
     assert pl.error() == 0
+    return pl
 
 
 @pytest.mark.parametrize("how", ["batch_of_one", "g16_single"])
