@@ -115,12 +115,15 @@ def lib() -> C.CDLL:
     L.msa_plan_traceback.argtypes = [P, i64, P, P, i64, P, P]
     L.msa_plan_traceback_gotoh.argtypes = [P, i64, C.c_int, P, P, i64, P, P]
     L.msa_plan_traceback_nw.argtypes = [P, i64, P, P, i64, P, P]
+    L.msa_plan_traceback_batch.argtypes = [P, P, P, P, P, P]
     L.msa_plan_last_kernel_ms.argtypes = [P, C.POINTER(C.c_float)]
     L.msa_plan_set_timing.argtypes = [P, i32]
     L.msa_encode_pair.argtypes = [P, sz, P, sz, P, P]
     L.msa_sw_align.argtypes = [P, sz, P, sz, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64),
                                C.POINTER(i64), C.POINTER(i64), P, sz]
     L.msa_nw_align.argtypes = [P, sz, P, sz, i32, i32, i64, C.POINTER(i32), P, sz]
+    L.msa_sw_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, i32, i32, i32, i32, P, P, P, P, sz, P]
+    L.msa_nw_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, i32, i32, i64, P, P, sz, P]
     _lib = L.lib
     return _lib
 
@@ -146,4 +149,5 @@ EXPORTED = [
     "msa_plan_format_info",
     "msa_plan_checksum", "msa_plan_traceback", "msa_plan_traceback_gotoh", "msa_plan_traceback_nw",
     "msa_plan_last_kernel_ms", "msa_plan_set_timing", "msa_encode_pair", "msa_sw_align", "msa_nw_align",
+    "msa_plan_traceback_batch", "msa_sw_align_batch", "msa_nw_align_batch",
 ]

@@ -299,3 +299,83 @@ def nw_align(A, B, gap_open=3, gap_extend=1, band=-1, traceback=True):
     if traceback:
         r["cigar"] = cig.value.decode()
     return r
+
+
+def _batch_in(As, Bs):
+    """(A buffer, B buffer, a_off, m, b_off, n as int64 arrays) of a batch; ``Bs`` one bytes object = shared by
+    every pair (sent once)."""
+    As = [_buf(a) for a in As]
+    k = len(As)
+    m = np.array([len(a) for a in As], dtype=np.int64)
+    a_off = np.concatenate(([0], np.cumsum(m)[:-1])).astype(np.int64)
+    if isinstance(Bs, (bytes, bytearray, str, memoryview)):
+        B = _buf(Bs)
+        n = np.full(k, len(B), dtype=np.int64)
+        b_off = np.zeros(k, dtype=np.int64)
+    else:
+        Bs = [_buf(b) for b in Bs]
+        if len(Bs) != k:
+            raise ValueError("Bs must be as long as As, or one bytes object shared by every pair")
+        B = b"".join(Bs)
+        n = np.array([len(b) for b in Bs], dtype=np.int64)
+        b_off = np.concatenate(([0], np.cumsum(n)[:-1])).astype(np.int64)
+    return b"".join(As), B, a_off, m, b_off, n
+
+
+def _i64p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def sw_align_batch(As, Bs, match=1, mismatch=0, gap_open=1, gap_extend=1, traceback=True):
+    """A batch of Smith-Waterman local alignments (msa_sw_align_batch) -> a list of sw_align()'s dicts.
+
+    ``Bs``: a list as long as ``As``, or one bytes object every A is aligned against (uploaded once).  One symbol
+    map serves the whole call: at most 7 distinct symbols in all of As and Bs together.  The pairs run as batch
+    plans (one fill and one walk launch per chunk of pairs that fits a quarter of the device budget)."""
+    if len(As) == 0:
+        return []
+    A, B, a_off, m, b_off, n = _batch_in(As, Bs)
+    k = len(m)
+    sc = np.zeros(k, dtype=np.int32)
+    end = np.zeros((k, 2), dtype=np.int64)
+    beg = np.zeros((k, 2), dtype=np.int64)
+    coff = np.zeros(k + 1, dtype=np.int64)
+    cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
+    cig = C.create_string_buffer(cap) if traceback else None
+    LB.check(LB.lib().msa_sw_align_batch(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
+                                         match, mismatch, gap_open, gap_extend, sc.ctypes.data_as(C.c_void_p),
+                                         _i64p(end), _i64p(beg) if traceback else None, cig, cap,
+                                         _i64p(coff) if traceback else None), "msa_sw_align_batch")
+    out = []
+    for p in range(k):
+        r = dict(score=int(sc[p]), end=(int(end[p, 0]), int(end[p, 1])))
+        if traceback:
+            r["beg"] = (int(beg[p, 0]), int(beg[p, 1]))
+            r["cigar"] = cig.raw[coff[p]:coff[p + 1] - 1].decode()
+        out.append(r)
+    return out
+
+
+def nw_align_batch(As, Bs, gap_open=3, gap_extend=1, band=-1, traceback=True):
+    """A batch of global (Gotoh) alignments (msa_nw_align_batch) -> a list of nw_align()'s dicts.
+
+    ``Bs`` as for sw_align_batch; scoring and ``band`` as for nw_align (the band holds for every pair).  One
+    symbol map serves the whole call: at most 8 distinct symbols in all of As and Bs together."""
+    if len(As) == 0:
+        return []
+    A, B, a_off, m, b_off, n = _batch_in(As, Bs)
+    k = len(m)
+    sc = np.zeros(k, dtype=np.int32)
+    coff = np.zeros(k + 1, dtype=np.int64)
+    cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
+    cig = C.create_string_buffer(cap) if traceback else None
+    LB.check(LB.lib().msa_nw_align_batch(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
+                                         gap_open, gap_extend, band, sc.ctypes.data_as(C.c_void_p), cig, cap,
+                                         _i64p(coff) if traceback else None), "msa_nw_align_batch")
+    out = []
+    for p in range(k):
+        r = dict(score=int(sc[p]))
+        if traceback:
+            r["cigar"] = cig.raw[coff[p]:coff[p + 1] - 1].decode()
+        out.append(r)
+    return out

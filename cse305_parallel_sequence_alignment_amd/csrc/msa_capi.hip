@@ -29,6 +29,7 @@
 #include "msa_band.hip"
 #include "msa_rowsweep.hip"
 #include "msa_traceback.hip"
+#include "msa_tbatch.hip"
 
 using namespace msa;
 
@@ -864,6 +865,28 @@ int msa_plan_traceback_nw(msa_plan* P, int64_t pair, const uint8_t* dDir, uint8_
   hipLaunchKernelGGL(traceback_kernel<TB_NW>, dim3(1), dim3(384), 0, st, dDir, P->d_pairs, P->d_meta,
                      (const PairResult*)P->d_res, (int)pair, 0, 0, d_ops, (long long)ops_cap, (long long*)d_info, 0,
                      (const unsigned long long*)nullptr);
+  HIPCHK(hipGetLastError());
+  return MSA_OK;
+}
+
+int msa_plan_traceback_batch(msa_plan* P, const uint8_t* dDir, uint8_t* d_ops, const int64_t* d_ops_off,
+                             int64_t* d_info, void* stream) {
+  if (!P || !dDir || !d_ops || !d_ops_off || !d_info) return MSA_ERR_ARG;
+  // one row per lane, stripe starts in the stripe meta, a PairResult per pair: the flow kernels' plans (two rows
+  // per lane, computed stripe starts, the fused best-cell key) stay with the single walker
+  if (P->mode == PM_FLOW || P->R == 2 || P->fused_reduce) return MSA_ERR_UNSUPPORTED;
+  const bool nw = P->d.alg == MSA_NW_ALIGN && P->d.cells == MSA_CELLS_DIR;
+  // (the SW walk starts at the fill's end cell: plans without track_end have none)
+  const bool sw = P->d.alg == MSA_SW_AFFINE && P->main.kp.alg == MSA_ALG_SWA && P->d.cells == MSA_CELLS_DIR &&
+                  P->d.track_end;
+  if (!nw && !sw) return MSA_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  P->note_stream(st);
+  const int np = (int)P->d.n_pairs;
+  hipLaunchKernelGGL((nw ? traceback_batch_kernel<TB_NW> : traceback_batch_kernel<TB_SW>),
+                     dim3((unsigned)((np + TBB_WPB - 1) / TBB_WPB)), dim3(64 * TBB_WPB), 0, st, dDir, P->d_pairs,
+                     P->d_meta, (const PairResult*)P->d_res, np, d_ops, (const long long*)d_ops_off,
+                     (long long*)d_info);
   HIPCHK(hipGetLastError());
   return MSA_OK;
 }

@@ -1303,3 +1303,221 @@ int msa_nw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t gap
 }
 
 }  // extern "C"
+
+// ---- batches of alignments with their CIGARs (msa_sw_align_batch, msa_nw_align_batch) ----------------------
+namespace {
+
+struct BatchIn {
+  const char *A, *B;
+  size_t a_len, b_len;
+  int64_t np;
+  const int64_t *a_off, *m, *b_off, *n;
+};
+
+// run-length string (start -> end) of ops given end -> start, NUL included, appended to `out`
+void append_cigar(std::string& out, const std::string& ops) {
+  for (int64_t k = (int64_t)ops.size() - 1; k >= 0;) {
+    const char op = ops[(size_t)k];
+    int64_t run = 0;
+    while (k >= 0 && ops[(size_t)k] == op) { run++; k--; }
+    out += std::to_string(run);
+    out.push_back(op);
+  }
+  out.push_back('\0');
+}
+
+// Both entries: validate, encode with one symbol map, then chunk by chunk (consecutive pairs whose summed
+// single-pair footprints fit a quarter of the device budget): admit, upload the chunk's code spans, one batch
+// plan, one run, one msa_plan_traceback_batch, fetch results, info and ops, build the CIGARs.
+int align_batch(bool nw, const BatchIn& in, int32_t match, int32_t mismatch, int32_t gap_open, int32_t gap_extend,
+                int64_t band_in, int32_t* score, int64_t* end_ij, int64_t* beg_ij, char* cigars, size_t cigar_cap,
+                int64_t* cigar_off) {
+  if (!in.A || !in.B || !in.a_off || !in.m || !in.b_off || !in.n || in.np < 1 || (cigars && !cigar_off))
+    return MSA_ERR_ARG;
+  if (nw && band_in < -1) return MSA_ERR_ARG;
+  const int64_t lim = int64_t(1) << 26;
+  int64_t span_max = 0;
+  for (int64_t p = 0; p < in.np; ++p) {
+    const int64_t m = in.m[p], n = in.n[p], ao = in.a_off[p], bo = in.b_off[p];
+    if (m < 1 || n < 1 || m > lim || n > lim || ao < 0 || bo < 0 || (uint64_t)ao + (uint64_t)m > in.a_len ||
+        (uint64_t)bo + (uint64_t)n > in.b_len)
+      return MSA_ERR_ARG;
+    span_max = std::max(span_max, std::max(m, n));
+  }
+  if (nw) {
+    if (gap_extend < 0 || gap_open < gap_extend) return MSA_ERR_UNSUPPORTED;
+    if (band_in >= 0)
+      for (int64_t p = 0; p < in.np; ++p)
+        if (std::llabs(in.m[p] - in.n[p]) > band_in) return MSA_ERR_ARG;
+  } else if (match < -128 || match > 127 || mismatch < -128 || mismatch > 127 || gap_open < 0 || gap_extend < 0) {
+    return MSA_ERR_UNSUPPORTED;
+  }
+  // (a band that holds every cell of every pair is no band)
+  const int band = (!nw || band_in < 0 || band_in >= span_max) ? -1 : (int)band_in;
+  // one code map for the call, first-seen order over A then B (code 7 is the SW kernels' sentinel)
+  std::vector<uint8_t> ca(in.a_len), cb(in.b_len);
+  {
+    int map[256], next = 0;
+    const int max_codes = nw ? 8 : 7;
+    std::fill(map, map + 256, -1);
+    auto enc = [&](const char* s, size_t len, uint8_t* out) -> int {
+      for (size_t k = 0; k < len; ++k) {
+        const unsigned char c = (unsigned char)s[k];
+        if (map[c] < 0) {
+          if (next >= max_codes) return MSA_ERR_ALPHABET;
+          map[c] = next++;
+        }
+        out[k] = (uint8_t)map[c];
+      }
+      return MSA_OK;
+    };
+    int rc = enc(in.A, in.a_len, ca.data());
+    if (rc == MSA_OK) rc = enc(in.B, in.b_len, cb.data());
+    if (rc != MSA_OK) return rc;
+  }
+  const bool want_tb = cigars != nullptr || (!nw && beg_ij != nullptr);
+  int rc = ensure_device();
+  if (rc != MSA_OK) return rc;
+  auto fp = [&](int64_t p) -> size_t {
+    if (nw) return footprint_nw(in.m[p], in.n[p], band, want_tb);
+    return want_tb ? footprint_dir(in.m[p], in.n[p]) : footprint_planes(in.m[p], in.n[p], 0, 1);
+  };
+  int64_t binfo[5];
+  admission().info(current_device(), binfo);
+  const size_t quarter = (size_t)binfo[0] / 4;
+  std::string all;  // the CIGARs, back to back
+  for (int64_t p0 = 0; p0 < in.np;) {
+    size_t bytes = fp(p0);
+    int64_t p1 = p0 + 1;
+    while (p1 < in.np && p1 - p0 < (int64_t(1) << 20) && bytes + fp(p1) <= quarter) bytes += fp(p1++);
+    const int64_t K = p1 - p0;
+    // the chunk's code spans and its pairs relative to them
+    int64_t a_lo = INT64_MAX, a_hi = 0, b_lo = INT64_MAX, b_hi = 0;
+    for (int64_t p = p0; p < p1; ++p) {
+      a_lo = std::min(a_lo, in.a_off[p]);
+      a_hi = std::max(a_hi, in.a_off[p] + in.m[p]);
+      b_lo = std::min(b_lo, in.b_off[p]);
+      b_hi = std::max(b_hi, in.b_off[p] + in.n[p]);
+    }
+    std::vector<int64_t> ms(in.m + p0, in.m + p1), ns(in.n + p0, in.n + p1), ao((size_t)K), bo((size_t)K),
+        off((size_t)K + 1, 0);
+    for (int64_t k = 0; k < K; ++k) {
+      ao[(size_t)k] = in.a_off[p0 + k] - a_lo;
+      bo[(size_t)k] = in.b_off[p0 + k] - b_lo;
+      off[(size_t)k + 1] = off[(size_t)k] + ((ms[(size_t)k] + ns[(size_t)k] + 2 + 15) & ~int64_t(15));
+    }
+    Admit adm(bytes);  // waits until the chunk fits the device budget
+    StreamGuard sg;
+    if ((rc = sg.acquire()) != MSA_OK) return rc;
+    DevMem dA, dB, dDir, dOps, dOff, dInfo;
+    PlanGuard pg;
+    StreamSync sync{sg.s};
+    if ((rc = dA.alloc((size_t)(a_hi - a_lo))) || (rc = dB.alloc((size_t)(b_hi - b_lo)))) return rc;
+    HIPCHK(hipMemcpyAsync(dA.p, ca.data() + a_lo, (size_t)(a_hi - a_lo), hipMemcpyHostToDevice, sg.s));
+    HIPCHK(hipMemcpyAsync(dB.p, cb.data() + b_lo, (size_t)(b_hi - b_lo), hipMemcpyHostToDevice, sg.s));
+    msa_plan_desc d;
+    std::memset(&d, 0, sizeof(d));
+    if (nw) {
+      // the scores alone need no direction bytes: the value plan of the same recurrence
+      d.alg = want_tb ? MSA_NW_ALIGN : MSA_NW_BANDED;
+      d.match = 1;
+      d.mismatch = 0;
+      d.start_type = -1;
+    } else {
+      d.alg = MSA_SW_AFFINE;
+      d.match = match;
+      d.mismatch = mismatch;
+      d.track_end = 1;
+    }
+    d.cells = want_tb ? MSA_CELLS_DIR : MSA_CELLS_NONE;
+    d.gap_open = gap_open;
+    d.gap_extend = gap_extend;
+    d.band = band;
+    d.single = 0;
+    d.n_pairs = K;
+    d.m = ms.data();
+    d.n = ns.data();
+    d.a_off = ao.data();
+    d.b_off = bo.data();
+    if ((rc = msa_plan_create(&d, &pg.p)) != MSA_OK) return rc;
+    if (want_tb) {
+      int64_t elems = 0;
+      msa_plan_cells_size(pg.p, &elems);
+      if ((rc = dDir.alloc((size_t)elems)) || (rc = dOps.alloc((size_t)off[(size_t)K])) ||
+          (rc = dOff.alloc(sizeof(int64_t) * (size_t)(K + 1))) || (rc = dInfo.alloc(64 * (size_t)K)))
+        return rc;
+      HIPCHK(hipMemcpyAsync(dOff.p, off.data(), sizeof(int64_t) * (size_t)(K + 1), hipMemcpyHostToDevice, sg.s));
+    }
+    if ((rc = msa_plan_run(pg.p, (const uint8_t*)dA.p, (const uint8_t*)dB.p, dDir.p, nullptr, nullptr, sg.s)))
+      return rc;
+    // every walk of the chunk in one launch: only the ops come back, not the direction bytes
+    if (want_tb && (rc = msa_plan_traceback_batch(pg.p, (const uint8_t*)dDir.p, (uint8_t*)dOps.p,
+                                                  (const int64_t*)dOff.p, (int64_t*)dInfo.p, sg.s)))
+      return rc;
+    std::vector<msa_pair_result> res((size_t)K);
+    if ((rc = msa_plan_results(pg.p, res.data(), sg.s)) != MSA_OK) return rc;
+    for (int64_t k = 0; k < K; ++k) {
+      if (score) score[p0 + k] = res[(size_t)k].score;
+      if (end_ij) {
+        end_ij[2 * (p0 + k)] = res[(size_t)k].end_i;
+        end_ij[2 * (p0 + k) + 1] = res[(size_t)k].end_j;
+      }
+    }
+    if (want_tb) {
+      std::vector<int64_t> info(8 * (size_t)K);
+      std::vector<char> ops((size_t)off[(size_t)K]);
+      HIPCHK(hipMemcpyAsync(info.data(), dInfo.p, 64 * (size_t)K, hipMemcpyDeviceToHost, sg.s));
+      HIPCHK(hipMemcpyAsync(ops.data(), dOps.p, ops.size(), hipMemcpyDeviceToHost, sg.s));
+      HIPCHK(hipStreamSynchronize(sg.s));
+      for (int64_t k = 0; k < K; ++k) {
+        const int64_t* inf = &info[8 * (size_t)k];
+        if (inf[3] != 0) return (int)inf[3];
+        std::string o(ops.data() + off[(size_t)k], (size_t)inf[0]);
+        if (nw) {
+          // the walk stopped on the matrix border at (i, j): the rest is one gap along it
+          const int64_t bi = inf[1] - 1, bj = inf[2] - 1;
+          if (bi > 0) o.append((size_t)bi, 'I');
+          else if (bj > 0) o.append((size_t)bj, 'D');
+        } else if (beg_ij) {
+          beg_ij[2 * (p0 + k)] = inf[1];
+          beg_ij[2 * (p0 + k) + 1] = inf[2];
+        }
+        if (cigars) {
+          cigar_off[p0 + k] = (int64_t)all.size();
+          append_cigar(all, o);
+        }
+      }
+    }
+    p0 = p1;
+  }
+  if (cigars) {
+    cigar_off[in.np] = (int64_t)all.size();
+    if (all.size() > cigar_cap) return MSA_ERR_CAPACITY;
+    std::memcpy(cigars, all.data(), all.size());
+  }
+  return MSA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msa_sw_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                       const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n, int32_t match,
+                       int32_t mismatch, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_ij,
+                       int64_t* beg_ij, char* cigars, size_t cigar_cap, int64_t* cigar_off) {
+  const BatchIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  return align_batch(false, in, match, mismatch, gap_open, gap_extend, -1, score, end_ij, beg_ij, cigars, cigar_cap,
+                     cigar_off);
+}
+
+int msa_nw_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                       const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                       int32_t gap_open, int32_t gap_extend, int64_t band, int32_t* score, char* cigars,
+                       size_t cigar_cap, int64_t* cigar_off) {
+  const BatchIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  return align_batch(true, in, 1, 0, gap_open, gap_extend, band, score, nullptr, nullptr, cigars, cigar_cap,
+                     cigar_off);
+}
+
+}  // extern "C"

@@ -277,6 +277,70 @@ class Plan:
         return dict(ops=o, stop=(i, j), cigar=cigar_of(o),
                     stats=dict(switches=int(inf[4]), on_demand=int(inf[5]), ticks=int(inf[6]), requests=int(inf[7])))
 
+    @staticmethod
+    def ops_layout(ms, ns) -> list:
+        """Default byte offsets of a batch walk's ops (n_pairs + 1 of them): pair p gets m_p + n_p + 2 bytes rounded
+        up to 16, back to back."""
+        off = [0]
+        for m, n in zip(ms, ns):
+            off.append(off[-1] + (int(m) + int(n) + 2 + 15) // 16 * 16)
+        return off
+
+    def traceback_batch_async(self, dDir, d_ops, d_ops_off, d_info, stream=None) -> None:
+        """Every pair's device walk in one launch (msa_plan_traceback_batch), stream-ordered after run(), for an
+        SW-affine DIR plan with track_end or an NW_ALIGN plan: pair p's ops (end -> start) go to d_ops[d_ops_off[p]:],
+        at most d_ops_off[p+1] - d_ops_off[p] of them; d_info (int64, 8 per pair) {n_ops, i+1, j+1, status, stripes
+        entered, groups staged, ticks, 0}.  d_ops_off: int64 CUDA tensor of n_pairs + 1 non-decreasing offsets, the
+        last one within d_ops."""
+        import torch
+
+        npairs = len(self.ms)
+        if not (dDir.is_cuda and dDir.dtype == torch.uint8 and dDir.numel() >= self.cells_elems):
+            raise ValueError("dDir must be the uint8 CUDA tensor the plan's run() wrote")
+        if not (d_ops.is_cuda and d_ops.dtype == torch.uint8 and d_ops.is_contiguous()):
+            raise ValueError("d_ops must be a contiguous uint8 CUDA tensor")
+        if not (d_ops_off.is_cuda and d_ops_off.dtype == torch.int64 and d_ops_off.is_contiguous() and
+                d_ops_off.numel() == npairs + 1):
+            raise ValueError("d_ops_off must be a contiguous int64 CUDA tensor of n_pairs + 1 offsets")
+        if not (d_info.is_cuda and d_info.dtype == torch.int64 and d_info.is_contiguous() and
+                d_info.numel() >= 8 * npairs):
+            raise ValueError("d_info must be a contiguous int64 CUDA tensor of >= 8 * n_pairs elements")
+        LB.check(LB.lib().msa_plan_traceback_batch(self._h, _ptr(dDir), _ptr(d_ops), _ptr(d_ops_off), _ptr(d_info),
+                                                   _stream_ptr(stream)), "msa_plan_traceback_batch")
+
+    def traceback_batch(self, dDir, stream=None, ops_off=None):
+        """Every pair's device walk in one launch, fetched: a list of per-pair dicts -- traceback()'s for an SW plan,
+        traceback_nw()'s (the border gap appended) for an NW_ALIGN plan.  ops_off (default ops_layout(ms, ns)): n_pairs
+        + 1 non-decreasing byte offsets, pair p's capacity being their difference.  Raises MsaError on the first
+        nonzero walk status."""
+        import torch
+
+        dev = dDir.device
+        off = self.ops_layout(self.ms, self.ns) if ops_off is None else [int(x) for x in ops_off]
+        if len(off) != len(self.ms) + 1 or off[0] < 0 or any(b < a for a, b in zip(off, off[1:])):
+            raise ValueError("ops_off must be n_pairs + 1 non-decreasing offsets")
+        ops = torch.empty(max(off[-1], 1), dtype=torch.uint8, device=dev)
+        info = torch.empty(8 * len(self.ms), dtype=torch.int64, device=dev)  # (the launch writes every word)
+        d_off = torch.tensor(off, dtype=torch.int64, device=dev)
+        self.traceback_batch_async(dDir, ops, d_off, info, stream)
+        if stream is not None:
+            # .cpu() below orders only against torch's current stream: wait for the walks' own
+            (torch.cuda.ExternalStream(stream) if isinstance(stream, int) else stream).synchronize()
+        inf = info.cpu().numpy().reshape(-1, 8)
+        oh = ops.cpu().numpy()
+        out = []
+        for k in range(len(self.ms)):
+            LB.check(int(inf[k, 3]), "msa_plan_traceback_batch")
+            o = oh[off[k]:off[k] + int(inf[k, 0])].tobytes()
+            stats = dict(switches=int(inf[k, 4]), staged=int(inf[k, 5]), ticks=int(inf[k, 6]))
+            if self.alg == LB.NW_ALIGN:
+                i, j = int(inf[k, 1]) - 1, int(inf[k, 2]) - 1
+                o += b"I" * i if i > 0 else b"D" * max(j, 0)
+                out.append(dict(ops=o, stop=(i, j), cigar=cigar_of(o), stats=stats))
+            else:
+                out.append(dict(ops=o, beg=(int(inf[k, 1]), int(inf[k, 2])), cigar=cigar_of(o), stats=stats))
+        return out
+
     def set_timing(self, on: bool) -> None:
         """Record HIP events around the DP kernel in run() (default on; kernel_ms() needs it)."""
         LB.check(LB.lib().msa_plan_set_timing(self._h, int(bool(on))), "msa_plan_set_timing")

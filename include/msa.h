@@ -33,6 +33,10 @@
  *                        banded global (Gotoh) alignment with its CIGAR (build extension:
  *                        MSA_NW_ALIGN plans write one direction byte per in-band cell, the
  *                        walk runs on the device; same recurrence as MSA_NW_BANDED)
+ *   msa_plan_traceback_batch, msa_sw_align_batch, msa_nw_align_batch
+ *                        the walks of a whole batch plan in one launch, and batches of local / global
+ *                        alignments with their CIGARs from host pointers (build extension: one wave per
+ *                        walk over the bytes msa_plan_traceback / msa_plan_traceback_nw walk)
  */
 #ifndef MSA_H
 #define MSA_H
@@ -346,10 +350,29 @@ int msa_plan_traceback_gotoh(msa_plan* plan, int64_t pair, int end_type, const u
  * ops end -> start (at most ops_cap; m+n suffices); d_info[8] as msa_plan_traceback_gotoh: {n_ops,
  * i+1, j+1, status, stripes entered, groups staged on demand, ticks, waits} with (i, j) the border
  * cell where the walk stopped and status 0 or MSA_ERR_CAPACITY.  Asynchronous, one walk per call
- * (a batch plan is walked pair by pair).  MSA_ERR_UNSUPPORTED for any plan that is not MSA_NW_ALIGN;
+ * (msa_plan_traceback_batch walks every pair of a batch plan in one launch).  MSA_ERR_UNSUPPORTED for any plan that is not MSA_NW_ALIGN;
  * msa_plan_traceback and msa_plan_traceback_gotoh reject MSA_NW_ALIGN plans. */
 int msa_plan_traceback_nw(msa_plan* plan, int64_t pair, const uint8_t* dDir, uint8_t* d_ops, int64_t ops_cap,
                           int64_t* d_info, void* stream);
+/* Every pair's traceback ON THE DEVICE in ONE launch (msa_tbatch.hip), after msa_plan_run on the same
+ * stream: one wave per pair, four walks per workgroup, each wave staging its own stripe groups and writing
+ * its own ops (the single walkers above spend a six-wave workgroup on one long walk and take a launch
+ * per pair).  Plans: MSA_SW_AFFINE with MSA_CELLS_DIR and track_end (msa_plan_traceback's walk, from each
+ * pair's end cell; no walk for a score <= 0) or MSA_NW_ALIGN (msa_plan_traceback_nw's walk, from (m, n) to
+ * the matrix border; the caller appends the border gap), laid out one row per lane with the stripe starts
+ * in the stripe meta: the stripe kernel's batch, split-batch and single launches and the band kernel's.
+ * MSA_ERR_UNSUPPORTED, before any launch, for the flow kernels' plans (msa_plan_launch_info mode 1: the
+ * single walkers serve them) and for every other algorithm / cells combination (MSA_REF_GOTOH included);
+ * MSA_ERR_ARG for a NULL pointer.  d_ops_off: DEVICE array of n_pairs + 1 non-decreasing byte offsets;
+ * pair p's ops (end -> start, 'M' / 'D' / 'I' as above) go to d_ops + d_ops_off[p], at most
+ * d_ops_off[p+1] - d_ops_off[p] of them (m + n suffices; any byte alignment); bytes outside a pair's n_ops
+ * are not written.  d_info: 8 int64 per pair, {n_ops, i+1, j+1, status, stripes entered, groups staged,
+ * s_memtime ticks of the walk, 0}; words 0-3 are the single walker's for that pair (SW: the first aligned
+ * cell; NW: the border cell where the walk stopped, + 1; status 0, MSA_ERR_CAPACITY with the true n_ops,
+ * MSA_ERR_NOMATCH, or MSA_ERR_TIMEOUT: every walk is bounded by m + n + 2 stripes + 8 stripe / group
+ * changes, whatever bytes dDir holds).  Asynchronous: no allocation, no host sync. */
+int msa_plan_traceback_batch(msa_plan* plan, const uint8_t* dDir, uint8_t* d_ops, const int64_t* d_ops_off,
+                             int64_t* d_info, void* stream);
 /* Order-independent digest of pair `pair`'s H cells (oracle orc_checksum_h). */
 int msa_plan_checksum(msa_plan* plan, const int32_t* dH, int64_t pair, uint64_t* digest, void* stream);
 /* Device time (ms) of the last msa_plan_run's stripe kernel, from HIP events
@@ -382,6 +405,35 @@ int msa_sw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t mat
  * footprint (~(2 band + 64) bytes per row), not the full matrix's. */
 int msa_nw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t gap_open, int32_t gap_extend,
                  int64_t band, int32_t* score, char* cigar, size_t cigar_cap);
+
+/* Host-pointer batches (build extension): n_pairs local (msa_sw_align_batch) or global (msa_nw_align_batch)
+ * alignments with their CIGARs.  Pair p is A[a_off[p] .. a_off[p] + m[p]) against B[b_off[p] .. b_off[p] +
+ * n[p]), 0-based; ranges may overlap or coincide (many queries against one reference: b_off all 0, the
+ * reference uploaded once).  A range outside [0, a_len) / [0, b_len), m[p] or n[p] < 1, n_pairs < 1 or a NULL
+ * array: MSA_ERR_ARG.  ONE symbol map serves the whole call -- first-seen order over A[0..a_len), then
+ * B[0..b_len) -- which is what lets pairs share a sequence; it is stricter than msa_sw_align's and
+ * msa_nw_align's per-pair maps: at most 7 (SW) / 8 (NW) distinct symbols in the two buffers together, else
+ * MSA_ERR_ALPHABET.  Scoring, the band rule (band >= 0 needs |m[p] - n[p]| <= band for every pair; a band >=
+ * every max(m[p], n[p]) is no band) and the other errors are msa_sw_align's and msa_nw_align's.
+ * score: n_pairs.  end_ij / beg_ij (SW; either may be NULL): 2 n_pairs, {i, j} per pair.  cigars receives the
+ * NUL-terminated run-length strings back to back (start -> end, I consumes A, D consumes B; NW strings
+ * consume exactly m[p] and n[p]), cigar_off[p] = the start of pair p's, cigar_off[n_pairs] = the bytes used;
+ * cigar_off (n_pairs + 1) is required with cigars.  A cigars too small: MSA_ERR_CAPACITY with the needed size
+ * in cigar_off[n_pairs].  cigars == NULL (SW: and beg_ij == NULL): scores (and SW end cells) only, from plans
+ * without direction bytes.
+ * Consecutive pairs run in chunks whose summed single-pair footprint estimates stay within a quarter of the
+ * device budget (a larger pair is a chunk alone); a chunk is admitted once and is one upload, one batch plan,
+ * one msa_plan_run, one msa_plan_traceback_batch and two downloads.  The first nonzero walk status or plan
+ * error is the call's status. */
+int msa_sw_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                       const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                       int32_t match, int32_t mismatch, int32_t gap_open, int32_t gap_extend,
+                       int32_t* score, int64_t* end_ij, int64_t* beg_ij,
+                       char* cigars, size_t cigar_cap, int64_t* cigar_off);
+int msa_nw_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                       const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                       int32_t gap_open, int32_t gap_extend, int64_t band,
+                       int32_t* score, char* cigars, size_t cigar_cap, int64_t* cigar_off);
 
 #ifdef __cplusplus
 }
