@@ -24,7 +24,7 @@ STATUS = {
 }
 
 # msa_alg_e / msa_out_e
-SW_LINEAR, SW_AFFINE, NW_BANDED, REF_GOTOH, PARTIAL, NW_ALIGN = 0, 1, 2, 3, 4, 5
+SW_LINEAR, SW_AFFINE, NW_BANDED, REF_GOTOH, PARTIAL, NW_ALIGN, NW_SCORED = 0, 1, 2, 3, 4, 5, 6
 CELLS_NONE, CELLS_H, CELLS_DIR, CELLS_TAB = 0, 1, 2, 3
 
 
@@ -96,6 +96,7 @@ def lib() -> C.CDLL:
     L.msa_main_alignment_partitioned.argtypes = [P, P, sz, sz, sz, C.c_double, C.c_double, C.c_int, P, sz,
                                                  C.POINTER(sz)]
     L.msa_plan_create.argtypes = [C.POINTER(PlanDesc), C.POINTER(P)]
+    L.msa_plan_create_scored.argtypes = [C.POINTER(PlanDesc), P, C.POINTER(P)]
     L.msa_plan_destroy.argtypes = [P]
     L.msa_plan_destroy.restype = None
     L.msa_plan_cells_size.argtypes = [P, C.POINTER(i64)]
@@ -124,6 +125,8 @@ def lib() -> C.CDLL:
     L.msa_nw_align.argtypes = [P, sz, P, sz, i32, i32, i64, C.POINTER(i32), P, sz]
     L.msa_sw_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, i32, i32, i32, i32, P, P, P, P, sz, P]
     L.msa_nw_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, i32, i32, i64, P, P, sz, P]
+    L.msa_nw_align_scored.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, i64, C.POINTER(i32), P, sz]
+    L.msa_nw_align_batch_scored.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, i64, P, P, sz, P]
     _lib = L.lib
     return _lib
 
@@ -150,4 +153,5 @@ EXPORTED = [
     "msa_plan_checksum", "msa_plan_traceback", "msa_plan_traceback_gotoh", "msa_plan_traceback_nw",
     "msa_plan_last_kernel_ms", "msa_plan_set_timing", "msa_encode_pair", "msa_sw_align", "msa_nw_align",
     "msa_plan_traceback_batch", "msa_sw_align_batch", "msa_nw_align_batch",
+    "msa_plan_create_scored", "msa_nw_align_scored", "msa_nw_align_batch_scored",
 ]

@@ -282,19 +282,66 @@ def sw_align(A, B, match=1, mismatch=0, gap_open=1, gap_extend=1, traceback=True
     return r
 
 
-def nw_align(A, B, gap_open=3, gap_extend=1, band=-1, traceback=True):
+def _nw_scoring(seqs, match, mismatch, alphabet, matrix):
+    """The scoring of nw_align / nw_align_batch: None when none of the four arguments is given (+1 / 0), else
+    (alphabet bytes, n_sym x n_sym int8 matrix, row = A's symbol).  ``match`` / ``mismatch`` (the other defaults to
+    1 / 0): the alphabet is the distinct symbols of ``seqs`` in first-seen order (more than 8: MsaError with the
+    ALPHABET status).  ``matrix`` needs ``alphabet`` and excludes ``match`` / ``mismatch`` (ValueError)."""
+    if match is None and mismatch is None and alphabet is None and matrix is None:
+        return None
+    if matrix is not None:
+        if match is not None or mismatch is not None:
+            raise ValueError("give either matrix (with alphabet) or match / mismatch, not both")
+        if alphabet is None:
+            raise ValueError("matrix needs alphabet")
+        alphabet = _buf(alphabet)
+        S = np.asarray(matrix)
+        if S.ndim != 2 or (S != S.astype(np.int8)).any():
+            raise ValueError("matrix must be a square array of scores in [-128, 127]")
+        # (the library checks the alphabet and that the matrix is n_sym x n_sym before it reads either)
+        if S.shape != (len(alphabet), len(alphabet)):
+            raise ValueError("matrix must be len(alphabet) x len(alphabet)")
+        return alphabet, np.ascontiguousarray(S, dtype=np.int8)
+    if alphabet is not None:
+        raise ValueError("alphabet comes with matrix")
+    seen = dict.fromkeys(b"".join(seqs))  # first-seen order
+    if len(seen) > 8:
+        raise LB.MsaError(-2, "nw_align")
+    ma, mi = (1 if match is None else int(match)), (0 if mismatch is None else int(mismatch))
+    if not (-128 <= ma <= 127 and -128 <= mi <= 127):
+        raise LB.MsaError(-5, "nw_align")
+    k = len(seen)
+    S = np.full((k, k), mi, dtype=np.int8)
+    np.fill_diagonal(S, ma)
+    return bytes(seen), S
+
+
+def nw_align(A, B, gap_open=3, gap_extend=1, band=-1, traceback=True, match=None, mismatch=None, alphabet=None,
+             matrix=None):
     """Global (Gotoh) alignment (build extension) -> dict(score, cigar).
 
     +1 on equal symbols, 0 otherwise; a gap of L costs (gap_open - gap_extend) + gap_extend * L.  ``band`` >= 0
     restricts the alignment to |i - j| <= band (-1: none).  The fill writes one direction byte per in-band cell,
     the walk runs on the device, and the CIGAR (start -> end, I consumes A, D consumes B) consumes all of A and
-    B.  ``traceback=False`` returns the score only."""
+    B.  ``traceback=False`` returns the score only.
+
+    Other scores (msa_nw_align_scored): ``match`` and / or ``mismatch`` (the other stays 1 / 0) over the symbols
+    of A and B, at most 8; or ``alphabet`` (up to 8 distinct bytes) with ``matrix``, len(alphabet) x len(alphabet)
+    scores in [-128, 127], ``matrix[a][b]`` = alphabet[a] in A against alphabet[b] in B (it need not be
+    symmetric).  With none of the four given, today's +1 / 0 call runs."""
     A, B = _buf(A), _buf(B)
+    scoring = _nw_scoring((A, B), match, mismatch, alphabet, matrix)
     sc = C.c_int32()
     cap = 4 * (len(A) + len(B)) + 16
     cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(LB.lib().msa_nw_align(A, len(A), B, len(B), gap_open, gap_extend, band, C.byref(sc), cig,
-                                   cap if traceback else 0), "msa_nw_align")
+    if scoring is None:
+        LB.check(LB.lib().msa_nw_align(A, len(A), B, len(B), gap_open, gap_extend, band, C.byref(sc), cig,
+                                       cap if traceback else 0), "msa_nw_align")
+    else:
+        alpha, S = scoring
+        LB.check(LB.lib().msa_nw_align_scored(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p),
+                                              gap_open, gap_extend, band, C.byref(sc), cig,
+                                              cap if traceback else 0), "msa_nw_align_scored")
     r = dict(score=sc.value)
     if traceback:
         r["cigar"] = cig.value.decode()
@@ -356,22 +403,34 @@ def sw_align_batch(As, Bs, match=1, mismatch=0, gap_open=1, gap_extend=1, traceb
     return out
 
 
-def nw_align_batch(As, Bs, gap_open=3, gap_extend=1, band=-1, traceback=True):
+def nw_align_batch(As, Bs, gap_open=3, gap_extend=1, band=-1, traceback=True, match=None, mismatch=None,
+                   alphabet=None, matrix=None):
     """A batch of global (Gotoh) alignments (msa_nw_align_batch) -> a list of nw_align()'s dicts.
 
     ``Bs`` as for sw_align_batch; scoring and ``band`` as for nw_align (the band holds for every pair).  One
-    symbol map serves the whole call: at most 8 distinct symbols in all of As and Bs together."""
+    symbol map serves the whole call: at most 8 distinct symbols in all of As and Bs together.  ``match`` /
+    ``mismatch`` / ``alphabet`` / ``matrix`` as for nw_align (msa_nw_align_batch_scored); the alphabet of ``match`` /
+    ``mismatch`` is the distinct symbols of all As, then all Bs, in first-seen order."""
     if len(As) == 0:
         return []
     A, B, a_off, m, b_off, n = _batch_in(As, Bs)
+    scoring = _nw_scoring((A, B), match, mismatch, alphabet, matrix)
     k = len(m)
     sc = np.zeros(k, dtype=np.int32)
     coff = np.zeros(k + 1, dtype=np.int64)
     cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
     cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(LB.lib().msa_nw_align_batch(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
-                                         gap_open, gap_extend, band, sc.ctypes.data_as(C.c_void_p), cig, cap,
-                                         _i64p(coff) if traceback else None), "msa_nw_align_batch")
+    if scoring is None:
+        LB.check(LB.lib().msa_nw_align_batch(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off),
+                                             _i64p(n), gap_open, gap_extend, band, sc.ctypes.data_as(C.c_void_p),
+                                             cig, cap, _i64p(coff) if traceback else None), "msa_nw_align_batch")
+    else:
+        alpha, S = scoring
+        LB.check(LB.lib().msa_nw_align_batch_scored(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off),
+                                                    _i64p(n), alpha, len(alpha), S.ctypes.data_as(C.c_void_p),
+                                                    gap_open, gap_extend, band, sc.ctypes.data_as(C.c_void_p), cig,
+                                                    cap, _i64p(coff) if traceback else None),
+                 "msa_nw_align_batch_scored")
     out = []
     for p in range(k):
         r = dict(score=int(sc[p]))

@@ -20,7 +20,8 @@
 // extension out of the recurrence:
 //     F~(i,j) = max(Z(i-1,j), F~(i-1,j)),  E~(i,j) = max(Z(i,j-1), E~(i,j-1)),
 //     H~(i,j) = max(Z(i-1,j-1) + f + 2g + h, E~, F~),  Z = H~ - h,   H = H~ - g(i+j)
-// (T3 = F, T2 = E; f = 1 on a match, else 0).  Band edges as stripe_kernel's band_fix: a lane
+// (T3 = F, T2 = E; f + 2g + h = the plan's table entry for (row code, column code), KArgs::sub: f = 1 on a match,
+// else 0, or an MSA_NW_SCORED plan's S).  Band edges as stripe_kernel's band_fix: a lane
 // runs the bare recurrence on every step, also outside its row's band; those values reach an
 // in-band cell only through two cells, fixed up in the head / tail phases: at column jlo - 1 the
 // state becomes the left border (column 0 for rows <= band, else -inf), at column jhi + 1 Z and
@@ -286,6 +287,12 @@ __global__ __launch_bounds__((BK_W + 1) * 64) void band_kernel(KArgs a) {
       const int cs = uni(sg.cs), P = uni(sg.P);
       const int row_i = 64 * k + lane + 1;
       const unsigned ac = (row_i <= m) ? (a.A[pd.a_off + row_i - 1] & 7u) : 0u;
+      // the plan's table, f + 2g + h per (row code, column code): the whole 64 bytes at wave-uniform addresses, in
+      // flight with the row code's cold load (a per-lane load at a.sub[ac] waits for ac first: two latencies in a
+      // row at every item's start, in front of the chain); the lane's row is taken by selects below
+      uint2 tab[8];
+#pragma unroll
+      for (int c = 0; c < 8; ++c) tab[c] = a.sub[c];
       const int tmin = jlo_of(row_i, band) - cs + lane;
       const int tmax = (row_i <= m) ? jhi_of(row_i, n, band) - cs + lane : -1;
       const int ZLB = (row_i <= band) ? -2 * hh : MSA_NEG;  // left border: column 0 (rows <= band), else -inf
@@ -319,16 +326,11 @@ __global__ __launch_bounds__((BK_W + 1) * 64) void band_kernel(KArgs a) {
       // direction bytes: block q of the stripe is the phase's 1 KiB, 16 B per lane
       uint8_t* odir = nullptr;
       if constexpr (DIRK) odir = a.outDir + pd.out_off + (size_t)k * pd.pmax * MSA_K * 64 + 16 * lane;
-      unsigned plo, phi;
-      {
-        const int sm = 1 + 2 * g + hh, sx = 2 * g + hh;  // f + 2g + h, f = 1 on a match
-        const unsigned bx = (unsigned)(sx & 0xff) * 0x01010101u;
-        unsigned lo = bx, hi = bx;
-        const unsigned bm = (unsigned)(sm & 0xff);
-        if (ac < 4) lo = (lo & ~(0xffu << (8 * ac))) | (bm << (8 * ac));
-        else hi = (hi & ~(0xffu << (8 * (ac - 4)))) | (bm << (8 * (ac - 4)));
-        plo = lo;
-        phi = hi;
+      unsigned plo = tab[0].x, phi = tab[0].y;  // the row's profile: row ac of the table
+#pragma unroll
+      for (int c = 1; c < 8; ++c) {
+        plo = (ac == (unsigned)c) ? tab[c].x : plo;
+        phi = (ac == (unsigned)c) ? tab[c].y : phi;
       }
       unsigned a_code;
       {

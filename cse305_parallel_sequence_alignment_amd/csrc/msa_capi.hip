@@ -638,6 +638,7 @@ int msa_plan_run(msa_plan* P, const uint8_t* dA, const uint8_t* dB, void* c0, vo
   a.stamps = P->stamps;
   a.cod = P->d_cod;
   a.cod_copy = P->cod_copy;
+  a.sub = P->d_sub;
   a.br = P->d_br;
   a.snap = P->d_snap;
   a.blk = P->d_blk;
@@ -858,7 +859,7 @@ int msa_plan_traceback_gotoh(msa_plan* P, int64_t pair, int end_type, const uint
 int msa_plan_traceback_nw(msa_plan* P, int64_t pair, const uint8_t* dDir, uint8_t* d_ops, int64_t ops_cap,
                           int64_t* d_info, void* stream) {
   if (!P || !dDir || !d_ops || !d_info || ops_cap < 0 || pair < 0 || pair >= P->d.n_pairs) return MSA_ERR_ARG;
-  if (P->d.alg != MSA_NW_ALIGN) return MSA_ERR_UNSUPPORTED;
+  if (!nw_bytes(P)) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   P->note_stream(st);
   // stripe starts from the stripe meta (band geometry); the walk needs no end type and no PairResult
@@ -875,7 +876,7 @@ int msa_plan_traceback_batch(msa_plan* P, const uint8_t* dDir, uint8_t* d_ops, c
   // one row per lane, stripe starts in the stripe meta, a PairResult per pair: the flow kernels' plans (two rows
   // per lane, computed stripe starts, the fused best-cell key) stay with the single walker
   if (P->mode == PM_FLOW || P->R == 2 || P->fused_reduce) return MSA_ERR_UNSUPPORTED;
-  const bool nw = P->d.alg == MSA_NW_ALIGN && P->d.cells == MSA_CELLS_DIR;
+  const bool nw = nw_bytes(P);
   // (the SW walk starts at the fill's end cell: plans without track_end have none)
   const bool sw = P->d.alg == MSA_SW_AFFINE && P->main.kp.alg == MSA_ALG_SWA && P->d.cells == MSA_CELLS_DIR &&
                   P->d.track_end;

@@ -190,6 +190,9 @@ struct KArgs {
   // two-pass SW single pair: the pass-2 blocks fold the pair result into this key themselves
   // (fl_block_result, msa_flow.hip) when set; else reduce_blocks_kernel runs after the launch
   unsigned long long* best_key;
+  // MSA_ALG_NWA: the plan's substitution table, one 8-byte profile per row code (byte b of entry a = the
+  // score of row code a against column code b, in the launch's own space: msa_plan.inc, sub_table)
+  const uint2* sub;
 };
 #ifndef MSA_H16_PAIRED
 #define MSA_H16_PAIRED 1  // int16 chunk cells: two u-blocks of a lane per 16 B (msa_band.hip)
@@ -966,6 +969,15 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
       const int row_i = 64 * ks + lane + 1;
       const unsigned ac = (row_i <= m) ? (a.A[pd.a_off + row_i - 1] & 7u) : 0u;
       const unsigned ac2 = (pk16(ALG) && row_i <= m) ? (a.A[pd2.a_off + row_i - 1] & 7u) : 0u;
+      // banded Gotoh: the row's profile is row ac of the plan's table.  The whole 64-byte table is loaded here at
+      // wave-uniform addresses, independent of the row code's load and like it ahead of the idle phases; the lane's
+      // row is taken by selects at the stripe's start (a load at a.sub[ac] would wait for ac here, in front of the
+      // workgroup's barriers)
+      uint2 tab[8] = {};
+      if constexpr (ALG == MSA_ALG_NWA) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) tab[c] = a.sub[c];
+      }
       for (; ph < sg.T; ++ph) MSA_SYNC(ph);
       // ---- stripe init ----
       LaneState<ALG> L;
@@ -1003,9 +1015,18 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         }
       }
       // substitution profile of this row (codes 0..7)
-      {
+      if constexpr (ALG == MSA_ALG_NWA) {
+        L.plo = tab[0].x;
+        L.phi = tab[0].y;
+#pragma unroll
+        for (int c = 1; c < 8; ++c) {
+          L.plo = (ac == (unsigned)c) ? tab[c].x : L.plo;
+          L.phi = (ac == (unsigned)c) ? tab[c].y : L.phi;
+        }
+        L.plo2 = L.phi2 = 0;
+      } else {
         int sm, sx;
-        if constexpr (ALG == MSA_ALG_REF || ALG == MSA_ALG_NWA) { sm = 1; sx = 0; }
+        if constexpr (ALG == MSA_ALG_REF) { sm = 1; sx = 0; }
         else if constexpr (ALG == MSA_ALG_REF1) { sm = 4; sx = 0; }  // 4f: tagged values
         else if constexpr (ALG == MSA_ALG_PART) { sm = 0; sx = 1; }
         else if constexpr (swlin(ALG)) { sm = kp.match + 2 * kp.gap_open; sx = kp.mismatch + 2 * kp.gap_open; }

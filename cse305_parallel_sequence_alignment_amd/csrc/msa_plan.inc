@@ -120,6 +120,10 @@ struct msa_plan {
   int* d_skip = nullptr;  // 1: every chunk converged (the exact launch exits)
   bool h16 = false;       // band_kernel chunks >= 1 write int16 cells to d_h16 (chunk_add_kernel widens)
   int16_t* d_h16 = nullptr;
+  // MSA_ALG_NWA: the substitution scores S[8 a + b] (row code a, column code b; 1 / 0 unless MSA_NW_SCORED) and
+  // their device table, one 8-byte profile per row code in the launch's space (alloc_buffers)
+  int8_t sub[64] = {};
+  uint2* d_sub = nullptr;
 
   bool chunked() const { return mode == PM_CHUNKED || mode == PM_BAND_CHUNKED; }
   void note_stream(hipStream_t s) {
@@ -144,6 +148,11 @@ struct msa_plan {
 namespace {
 
 struct Extents { int S = 0, P = 0; };  // most stripes / most 16-step layout blocks of any pair
+
+// the plan wrote the global alignment's direction bytes (msa_plan_traceback_nw's and the batch walk's plans)
+bool nw_bytes(const msa_plan* P) {
+  return (P->d.alg == MSA_NW_ALIGN || P->d.alg == MSA_NW_SCORED) && P->d.cells == MSA_CELLS_DIR;
+}
 
 // ---- step 1: kernel algorithm and end-cell tracking mode --------------------------------------------
 int choose_algorithm(const msa_plan_desc* desc, int& kalg, int& tp) {
@@ -171,9 +180,17 @@ int choose_algorithm(const msa_plan_desc* desc, int& kalg, int& tp) {
     case MSA_NW_BANDED: kalg = MSA_ALG_NWA; break;
     case MSA_NW_ALIGN:
       // MSA_NW_BANDED's recurrence with one direction byte per cell, walked by msa_plan_traceback_nw: direction
-      // bytes only, the reference's scores (f = 1 / 0; general scores are left for later) and gaps with g, h >= 0
+      // bytes only, the reference's scores (f = 1 / 0; any other scoring is MSA_NW_SCORED's) and gaps with g, h >= 0
       kalg = MSA_ALG_NWA;
       if (out_mode != MSA_OUT_DIR || desc->match != 1 || desc->mismatch != 0 || desc->gap_extend < 0 ||
+          desc->gap_open < desc->gap_extend)
+        return MSA_ERR_UNSUPPORTED;
+      break;
+    case MSA_NW_SCORED:
+      // MSA_NW_ALIGN with f = S[row code][column code] (the plan's table: plan_create), direction bytes or the
+      // score alone; the table's and the gaps' sizes are check_ranges'
+      kalg = MSA_ALG_NWA;
+      if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->gap_extend < 0 ||
           desc->gap_open < desc->gap_extend)
         return MSA_ERR_UNSUPPORTED;
       break;
@@ -224,10 +241,43 @@ msa_kparams base_kparams(const msa_plan_desc* desc, int kalg) {
 }
 
 // ---- step 2: every pair's sizes and scores are inside what the kernels' number formats hold ---------
-int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp) {
+// the largest |score| of a substitution table
+int sub_abs_max(const int8_t* sub) {
+  int s = 0;
+  for (int k = 0; k < 64; ++k) s = std::max(s, std::abs((int)sub[k]));
+  return s;
+}
+// `scored`: the table of an MSA_NW_SCORED plan (nullptr for every other plan)
+int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t* scored) {
   for (int64_t p = 0; p < desc->n_pairs; ++p) {
     const int64_t m = desc->m[p], n = desc->n[p];
     if (m <= 0 || n <= 0 || m > (1 << 26) || n > (1 << 26)) return MSA_ERR_ARG;
+    if (scored) {
+      // MSA_NW_SCORED (MSA_ALG_NWA in band_kernel or stripe_kernel).  With s = the largest |S|, g, h >= 0, G = g + h:
+      //   K = (s + 2 G + 2 g) T + h < 2^28,   T = m + n + 256.
+      // Every value either kernel forms -- in or out of a row's band, E / F / H, stripe_kernel's H or band_kernel's
+      // shifted H~ = H + g (i + j), Z = H~ - h -- is a SOURCE plus one STEP change per cell of a dependency path.
+      // A step moves left, up or diagonally, so it moves to a later anti-diagonal, and a lane touches rows 1..m and
+      // columns 1 - 79 .. n + 78 (stripe_geom: a stripe starts <= 16 + 63 columns before its band and ends within
+      // 63 + 15 after it): a path has fewer than T steps, and |i + j| < T everywhere.
+      //   steps, unshifted: the diagonal adds S (|.| <= s), E and F subtract g or G: at most max(s, G) a step;
+      //   steps, shifted:   the diagonal adds the profile byte S + 2g + h and Z takes h off, E~ and F~ add 0 or take
+      //                     h off: at most s + 2g + h a step (the byte itself is sign-extended from int8: choose_mode
+      //                     keeps it <= 127, and it is >= -128 since S >= -128);
+      //   sources: 0; the borders and the guessed rows -h - g k, k <= max(m, n), shifted by at most g T + h more:
+      //            within 2h + 2g T; and -inf = MSA_NEG = -2^30 (U, E, F at a stripe's start, U + sc included; the
+      //            masked inputs; band_fix's and the head / tail phases' edge values; the left border past the band).
+      // So a finite value stays within 2h + 2g T + (s + 2g + h) T <= K of 0, shifted or not, and so does what the
+      // kernels form from it: the unshifted final state and checkpoint rows (a shifted value less g (i + j), h added).
+      // A -inf drifts by at most (s + 2g + h) T while shifted and by g T + h more where it is unshifted (the
+      // checkpoint rows; the out-of-band lanes between the edge fix-ups drift like any other path): within K of -2^30.
+      // K < 2^28 therefore keeps every finite value above -2^28 > MSA_NEG / 2, the threshold chunk_check_kernel and
+      // chunk_add_kernel take for -inf (the walk reads bytes only), every drifted -inf in [-2^30 - 2^28, -2^30 + 2^28],
+      // below that threshold, and everything inside int32.  (The chunk warm-up compares rows up to a constant and
+      // falls back to the exact launch: negative scores change how often it converges, not what it computes.)
+      const int64_t s = sub_abs_max(scored), g = kp.gap_ext, h = kp.h, G = kp.gap_open;
+      if ((s + 2 * G + 2 * g) * (m + n + 256) + h >= (int64_t(1) << 28)) return MSA_ERR_UNSUPPORTED;
+    }
     if (is_linear(kp.alg)) {
       // shifted recurrence G = H + g*(i+j): G must stay far from the -2^30 sentinel
       // and from int32 overflow; the profile byte holds score + 2g
@@ -280,7 +330,8 @@ int band_chunk() {
   return v;
 }
 
-PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp) {
+// smax: the largest score of an MSA_NW_SCORED plan's table (unused by every other plan)
+PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp, int smax) {
   const int out_mode = desc->cells;
   const int band = (kalg == MSA_ALG_NWA) ? desc->band : -1;
   if (desc->single) {
@@ -314,6 +365,10 @@ PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp) {
     // (direction bytes: MSA_NW_ALIGN, chunked like H -- a chunk's bytes do not depend on its constant)
     if (kalg == MSA_ALG_NWA && band >= 0) {
       const int S = stripes_of(desc->m[0]);
+      // MSA_NW_SCORED: band_kernel works on values shifted by g (i + j), so its profile bytes are S + 2g + h; a
+      // table whose largest does not fit int8 runs the exact stripe launch, whose bytes are the raw S (lin_ok's
+      // precedent above; the low side cannot fail: S >= -128 and g, h >= 0)
+      if (desc->alg == MSA_NW_SCORED && (int64_t)smax + desc->gap_extend + desc->gap_open > 127) return PM_STRIPE;
       if (bk_lds_bytes(bk_code_bytes((int)desc->m[0], (int)desc->n[0], band)) <= device_lds_max()) {
         const bool chunks = (S + band_chunk() - 1) / band_chunk() >= 4 && out_mode != MSA_OUT_NONE && band_warm() >= BK_W;
         return chunks ? PM_BAND_CHUNKED : PM_BAND;
@@ -343,7 +398,8 @@ PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp) {
   bool eq_m = true;
   for (int64_t p = 1; p < desc->n_pairs; ++p) eq_m = eq_m && desc->m[p] == desc->m[0];
   if (eq_m && batch_items(desc, kalg) < slots && stripes_of(desc->m[0]) >= 2 * MSA_WAVES_BATCH && band < 0 &&
-      desc->alg != MSA_NW_ALIGN)  // (a batch of global alignments with direction bytes: whole pairs per workgroup)
+      desc->alg != MSA_NW_ALIGN && desc->alg != MSA_NW_SCORED)  // (a batch of global alignments with direction
+                                                                // bytes, or scored: whole pairs per workgroup)
     return PM_SPLIT;
   return PM_STRIPE;
 }
@@ -656,6 +712,16 @@ int alloc_buffers(msa_plan& P) {
   if (!P.alloc(&P.d_segs, sizeof(msa_pair_desc) * P.segs.size())) return MSA_ERR_HIP;
   HIPCHK(hipMemcpy(P.d_segs, P.segs.data(), sizeof(msa_pair_desc) * P.segs.size(), hipMemcpyHostToDevice));
   if (!P.alloc(&P.d_res, sizeof(PairResult) * np) || !P.alloc(&P.d_sum, 64)) return MSA_ERR_HIP;
+  if (P.main.kp.alg == MSA_ALG_NWA) {
+    // the substitution table, one 8-byte profile per row code: band_kernel's bytes are S + 2g + h (its values are
+    // shifted by g (i + j); wrapped to a byte as the kernel's own arithmetic did for the 1 / 0 plans), stripe_kernel's S
+    const bool bandk = P.mode == PM_BAND || P.mode == PM_BAND_CHUNKED;
+    const int add = bandk ? 2 * P.main.kp.gap_ext + P.main.kp.h : 0;
+    uint8_t tab[64];
+    for (int k = 0; k < 64; ++k) tab[k] = (uint8_t)((P.sub[k] + add) & 0xff);
+    if (!P.alloc(&P.d_sub, sizeof(tab))) return MSA_ERR_HIP;
+    HIPCHK(hipMemcpy(P.d_sub, tab, sizeof(tab), hipMemcpyHostToDevice));
+  }
   if (P.gslots > 0) {  // granules: one slot of the longest column count (+ margins) per publishing item
     int nmax = 0;
     for (const msa_pair_desc& pd : P.pairs) nmax = std::max(nmax, pd.n);
@@ -710,9 +776,12 @@ int alloc_buffers(msa_plan& P) {
 
 }  // namespace
 
-// ---- the C entry point (C linkage by its declaration in msa.h; msa_plan_destroy: msa_capi.hip) ------
-int msa_plan_create(const msa_plan_desc* desc, msa_plan** out) {
+// ---- the C entry points (C linkage by their declarations in msa.h; msa_plan_destroy: msa_capi.hip) ------
+int msa_plan_create(const msa_plan_desc* desc, msa_plan** out) { return msa_plan_create_scored(desc, nullptr, out); }
+
+int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_plan** out) {
   if (!desc || !out || desc->n_pairs <= 0 || !desc->m || !desc->n || !desc->a_off || !desc->b_off) return MSA_ERR_ARG;
+  if (sub && desc->alg != MSA_NW_SCORED) return MSA_ERR_UNSUPPORTED;
   int rc = ensure_device();
   if (rc != MSA_OK) return rc;
   // (a plan without device buffers yet destroys cleanly: no streams, no blocks, null events)
@@ -732,8 +801,19 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** out) {
   P->main.kp = base_kparams(desc, kalg);
   P->nc = nc_of(kalg);
   if (kalg == MSA_ALG_NWA && P->main.kp.h < 0) return MSA_ERR_UNSUPPORTED;
-  if ((rc = check_ranges(desc, P->main.kp)) != MSA_OK) return rc;
-  P->mode = choose_mode(desc, kalg, tp);
+  // the substitution scores of the banded recurrence: MSA_NW_SCORED's table, or its match / mismatch; 1 / 0 for
+  // MSA_NW_BANDED and MSA_NW_ALIGN, whatever their description says
+  const bool scored = desc->alg == MSA_NW_SCORED;
+  int smax = 0;
+  if (scored && !sub && (desc->match < -128 || desc->match > 127 || desc->mismatch < -128 || desc->mismatch > 127))
+    return MSA_ERR_UNSUPPORTED;
+  for (int k = 0; k < 64; ++k) {
+    const bool diag = k / 8 == k % 8;
+    P->sub[k] = sub ? sub[k] : (int8_t)(scored ? (diag ? desc->match : desc->mismatch) : (diag ? 1 : 0));
+    smax = k ? std::max(smax, (int)P->sub[k]) : (int)P->sub[k];
+  }
+  if ((rc = check_ranges(desc, P->main.kp, scored ? P->sub : nullptr)) != MSA_OK) return rc;
+  P->mode = choose_mode(desc, kalg, tp, smax);
   set_layout_mode(*P, desc);
   const Extents ex = lay_out_pairs(*P, desc);
   switch (P->mode) {

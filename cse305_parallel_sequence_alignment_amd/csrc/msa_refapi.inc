@@ -1213,12 +1213,39 @@ size_t footprint_nw(int64_t m, int64_t n, int band, bool dir) {
          3 * (size_t)(m + n) + (size_t(24) << 20);
 }
 
-}  // namespace
+// The scoring of a scored global alignment entry (msa_nw_align_scored, msa_nw_align_batch_scored): the caller's
+// alphabet as a symbol -> code map (a symbol's code is its index) and its n_sym x n_sym matrix as the plan's 8 x 8
+// table.  The unscored entries pass no NwScoring: +1 / 0 over a symbol map of the call's own.
+struct NwScoring {
+  int map[256];
+  int8_t tab[64];
+  // MSA_ERR_ARG for a NULL alphabet or matrix, n_sym outside 1..8 or a duplicate symbol
+  int set(const char* alphabet, size_t n_sym, const int8_t* sub) {
+    if (!alphabet || !sub || n_sym < 1 || n_sym > 8) return MSA_ERR_ARG;
+    std::fill(map, map + 256, -1);
+    std::fill(tab, tab + 64, (int8_t)0);
+    for (size_t a = 0; a < n_sym; ++a) {
+      int& code = map[(unsigned char)alphabet[a]];
+      if (code >= 0) return MSA_ERR_ARG;
+      code = (int)a;
+      for (size_t b = 0; b < n_sym; ++b) tab[8 * a + b] = sub[n_sym * a + b];
+    }
+    return MSA_OK;
+  }
+  // MSA_ERR_ALPHABET for a symbol outside the alphabet
+  int encode(const char* s, size_t len, uint8_t* out) const {
+    for (size_t k = 0; k < len; ++k) {
+      const int code = map[(unsigned char)s[k]];
+      if (code < 0) return MSA_ERR_ALPHABET;
+      out[k] = (uint8_t)code;
+    }
+    return MSA_OK;
+  }
+};
 
-extern "C" {
-
-int msa_nw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t gap_open, int32_t gap_extend,
-                 int64_t band_in, int32_t* score, char* cigar, size_t cigar_cap) {
+// msa_nw_align (sc == nullptr) and msa_nw_align_scored
+int nw_align_one(const char* A0, size_t m, const char* B0, size_t n, const NwScoring* sc, int32_t gap_open,
+                 int32_t gap_extend, int64_t band_in, int32_t* score, char* cigar, size_t cigar_cap) {
   if (!A0 || !B0 || m == 0 || n == 0 || m > (size_t(1) << 26) || n > (size_t(1) << 26) || band_in < -1)
     return MSA_ERR_ARG;
   if (gap_extend < 0 || gap_open < gap_extend) return MSA_ERR_UNSUPPORTED;
@@ -1227,7 +1254,8 @@ int msa_nw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t gap
   // (a band that holds every cell is no band)
   const int band = (band_in < 0 || band_in >= std::max(mm, nn)) ? -1 : (int)band_in;
   std::vector<uint8_t> ca(m), cb(n);
-  int rc = msa_encode_pair(A0, m, B0, n, ca.data(), cb.data());
+  int rc = sc ? sc->encode(A0, m, ca.data()) : msa_encode_pair(A0, m, B0, n, ca.data(), cb.data());
+  if (rc == MSA_OK && sc) rc = sc->encode(B0, n, cb.data());
   if (rc != MSA_OK) return rc;
   const bool want_tb = cigar != nullptr;
   if ((rc = ensure_device()) != MSA_OK) return rc;
@@ -1243,8 +1271,8 @@ int msa_nw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t gap
   int64_t zero = 0;
   msa_plan_desc d;
   std::memset(&d, 0, sizeof(d));
-  // the score alone needs no direction bytes: the value plan of the same recurrence
-  d.alg = want_tb ? MSA_NW_ALIGN : MSA_NW_BANDED;
+  // the score alone needs no direction bytes: the value plan of the same recurrence (a scored plan has both)
+  d.alg = sc ? MSA_NW_SCORED : (want_tb ? MSA_NW_ALIGN : MSA_NW_BANDED);
   d.cells = want_tb ? MSA_CELLS_DIR : MSA_CELLS_NONE;
   d.match = 1;
   d.mismatch = 0;
@@ -1258,7 +1286,7 @@ int msa_nw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t gap
   d.n = &nn;
   d.a_off = &zero;
   d.b_off = &zero;
-  if ((rc = msa_plan_create(&d, &pg.p)) != MSA_OK) return rc;
+  if ((rc = msa_plan_create_scored(&d, sc ? sc->tab : nullptr, &pg.p)) != MSA_OK) return rc;
   const int64_t ops_cap = mm + nn + 2;
   if (want_tb) {
     int64_t elems = 0;
@@ -1302,6 +1330,24 @@ int msa_nw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t gap
   return MSA_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int msa_nw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t gap_open, int32_t gap_extend,
+                 int64_t band, int32_t* score, char* cigar, size_t cigar_cap) {
+  return nw_align_one(A0, m, B0, n, nullptr, gap_open, gap_extend, band, score, cigar, cigar_cap);
+}
+
+int msa_nw_align_scored(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                        const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band, int32_t* score,
+                        char* cigar, size_t cigar_cap) {
+  NwScoring sc;
+  const int rc = sc.set(alphabet, n_sym, sub);
+  if (rc != MSA_OK) return rc;
+  return nw_align_one(A0, m, B0, n, &sc, gap_open, gap_extend, band, score, cigar, cigar_cap);
+}
+
 }  // extern "C"
 
 // ---- batches of alignments with their CIGARs (msa_sw_align_batch, msa_nw_align_batch) ----------------------
@@ -1329,9 +1375,10 @@ void append_cigar(std::string& out, const std::string& ops) {
 // Both entries: validate, encode with one symbol map, then chunk by chunk (consecutive pairs whose summed
 // single-pair footprints fit a quarter of the device budget): admit, upload the chunk's code spans, one batch
 // plan, one run, one msa_plan_traceback_batch, fetch results, info and ops, build the CIGARs.
-int align_batch(bool nw, const BatchIn& in, int32_t match, int32_t mismatch, int32_t gap_open, int32_t gap_extend,
-                int64_t band_in, int32_t* score, int64_t* end_ij, int64_t* beg_ij, char* cigars, size_t cigar_cap,
-                int64_t* cigar_off) {
+// sc (nw only): the scored entry's alphabet and matrix instead of +1 / 0 over the call's own symbol map
+int align_batch(bool nw, const BatchIn& in, const NwScoring* sc, int32_t match, int32_t mismatch, int32_t gap_open,
+                int32_t gap_extend, int64_t band_in, int32_t* score, int64_t* end_ij, int64_t* beg_ij, char* cigars,
+                size_t cigar_cap, int64_t* cigar_off) {
   if (!in.A || !in.B || !in.a_off || !in.m || !in.b_off || !in.n || in.np < 1 || (cigars && !cigar_off))
     return MSA_ERR_ARG;
   if (nw && band_in < -1) return MSA_ERR_ARG;
@@ -1371,8 +1418,8 @@ int align_batch(bool nw, const BatchIn& in, int32_t match, int32_t mismatch, int
       }
       return MSA_OK;
     };
-    int rc = enc(in.A, in.a_len, ca.data());
-    if (rc == MSA_OK) rc = enc(in.B, in.b_len, cb.data());
+    int rc = sc ? sc->encode(in.A, in.a_len, ca.data()) : enc(in.A, in.a_len, ca.data());
+    if (rc == MSA_OK) rc = sc ? sc->encode(in.B, in.b_len, cb.data()) : enc(in.B, in.b_len, cb.data());
     if (rc != MSA_OK) return rc;
   }
   const bool want_tb = cigars != nullptr || (!nw && beg_ij != nullptr);
@@ -1418,8 +1465,8 @@ int align_batch(bool nw, const BatchIn& in, int32_t match, int32_t mismatch, int
     msa_plan_desc d;
     std::memset(&d, 0, sizeof(d));
     if (nw) {
-      // the scores alone need no direction bytes: the value plan of the same recurrence
-      d.alg = want_tb ? MSA_NW_ALIGN : MSA_NW_BANDED;
+      // the scores alone need no direction bytes: the value plan of the same recurrence (a scored plan has both)
+      d.alg = sc ? MSA_NW_SCORED : (want_tb ? MSA_NW_ALIGN : MSA_NW_BANDED);
       d.match = 1;
       d.mismatch = 0;
       d.start_type = -1;
@@ -1439,7 +1486,7 @@ int align_batch(bool nw, const BatchIn& in, int32_t match, int32_t mismatch, int
     d.n = ns.data();
     d.a_off = ao.data();
     d.b_off = bo.data();
-    if ((rc = msa_plan_create(&d, &pg.p)) != MSA_OK) return rc;
+    if ((rc = msa_plan_create_scored(&d, sc ? sc->tab : nullptr, &pg.p)) != MSA_OK) return rc;
     if (want_tb) {
       int64_t elems = 0;
       msa_plan_cells_size(pg.p, &elems);
@@ -1507,8 +1554,8 @@ int msa_sw_align_batch(const char* A, size_t a_len, const char* B, size_t b_len,
                        int32_t mismatch, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_ij,
                        int64_t* beg_ij, char* cigars, size_t cigar_cap, int64_t* cigar_off) {
   const BatchIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
-  return align_batch(false, in, match, mismatch, gap_open, gap_extend, -1, score, end_ij, beg_ij, cigars, cigar_cap,
-                     cigar_off);
+  return align_batch(false, in, nullptr, match, mismatch, gap_open, gap_extend, -1, score, end_ij, beg_ij, cigars,
+                     cigar_cap, cigar_off);
 }
 
 int msa_nw_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
@@ -1516,7 +1563,20 @@ int msa_nw_align_batch(const char* A, size_t a_len, const char* B, size_t b_len,
                        int32_t gap_open, int32_t gap_extend, int64_t band, int32_t* score, char* cigars,
                        size_t cigar_cap, int64_t* cigar_off) {
   const BatchIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
-  return align_batch(true, in, 1, 0, gap_open, gap_extend, band, score, nullptr, nullptr, cigars, cigar_cap,
+  return align_batch(true, in, nullptr, 1, 0, gap_open, gap_extend, band, score, nullptr, nullptr, cigars, cigar_cap,
+                     cigar_off);
+}
+
+int msa_nw_align_batch_scored(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                              const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                              const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                              int32_t gap_extend, int64_t band, int32_t* score, char* cigars, size_t cigar_cap,
+                              int64_t* cigar_off) {
+  NwScoring sc;
+  const int rc = sc.set(alphabet, n_sym, sub);
+  if (rc != MSA_OK) return rc;
+  const BatchIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  return align_batch(true, in, &sc, 1, 0, gap_open, gap_extend, band, score, nullptr, nullptr, cigars, cigar_cap,
                      cigar_off);
 }
 

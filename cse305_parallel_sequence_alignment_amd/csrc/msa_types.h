@@ -12,7 +12,8 @@ enum msa_alg {
   MSA_ALG_SWL = 0,   // Smith-Waterman, linear gap        (config C2, C4)
   MSA_ALG_SWA = 1,   // Smith-Waterman, affine gap        (config C5)
   MSA_ALG_NWA = 2,   // reference Gotoh, start type -1, h>=0 (banded, C3): values, or with MSA_OUT_DIR
-                     // (MSA_NW_ALIGN plans only) direction bytes in the SW-affine format
+                     // (MSA_NW_ALIGN / MSA_NW_SCORED plans only) direction bytes in the SW-affine format;
+                     // substitution scores from the plan's 8 x 8 table (KArgs::sub; 1 / 0 unless MSA_NW_SCORED)
   MSA_ALG_REF = 3,   // reference Gotoh T1/T2/T3, any start type, exact -inf
   MSA_ALG_PART = 4,  // partial.cpp Gotoh with int32 wrap semantics
   MSA_ALG_SWL0 = 5,  // Smith-Waterman, linear gap, every substitution score >= 0 (plan's

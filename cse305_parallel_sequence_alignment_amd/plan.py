@@ -50,7 +50,9 @@ class Plan:
     """One launch shape: ``n_pairs`` pairs of (m_k, n_k) codes at (a_off_k, b_off_k)."""
 
     def __init__(self, alg: int, cells: int, ms, ns, a_offs, b_offs, match=1, mismatch=0, gap_open=1,
-                 gap_extend=1, start_type=-1, band=-1, track_end=False, single=None):
+                 gap_extend=1, start_type=-1, band=-1, track_end=False, single=None, sub=None):
+        """``sub`` (NW_SCORED only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code a against column
+        code b (msa_plan_create_scored); None scores ``match`` on the diagonal and ``mismatch`` elsewhere."""
         L = LB.lib()
         self.alg, self.cells = alg, cells
         self.ms = [int(x) for x in ms]
@@ -65,7 +67,15 @@ class Plan:
                         single=int(bool(single)), n_pairs=npairs, m=self._arrs[0], n=self._arrs[1],
                         a_off=self._arrs[2], b_off=self._arrs[3])
         self._h = C.c_void_p()
-        LB.check(L.msa_plan_create(C.byref(d), C.byref(self._h)), "msa_plan_create")
+        if sub is None:
+            LB.check(L.msa_plan_create(C.byref(d), C.byref(self._h)), "msa_plan_create")
+        else:
+            tab = np.asarray(sub)
+            if tab.shape != (8, 8) or (tab != tab.astype(np.int8)).any():
+                raise ValueError("sub must be 8 x 8 scores in [-128, 127]")
+            tab = np.ascontiguousarray(tab, dtype=np.int8)
+            LB.check(L.msa_plan_create_scored(C.byref(d), tab.ctypes.data_as(C.c_void_p), C.byref(self._h)),
+                     "msa_plan_create_scored")
         self.band = band
         self.single = bool(single)
         e = C.c_int64()
@@ -333,7 +343,7 @@ class Plan:
             LB.check(int(inf[k, 3]), "msa_plan_traceback_batch")
             o = oh[off[k]:off[k] + int(inf[k, 0])].tobytes()
             stats = dict(switches=int(inf[k, 4]), staged=int(inf[k, 5]), ticks=int(inf[k, 6]))
-            if self.alg == LB.NW_ALIGN:
+            if self.alg in (LB.NW_ALIGN, LB.NW_SCORED):
                 i, j = int(inf[k, 1]) - 1, int(inf[k, 2]) - 1
                 o += b"I" * i if i > 0 else b"D" * max(j, 0)
                 out.append(dict(ops=o, stop=(i, j), cigar=cigar_of(o), stats=stats))

@@ -32,7 +32,11 @@
  *   msa_nw_align, msa_plan_traceback_nw
  *                        banded global (Gotoh) alignment with its CIGAR (build extension:
  *                        MSA_NW_ALIGN plans write one direction byte per in-band cell, the
- *                        walk runs on the device; same recurrence as MSA_NW_BANDED)
+ *                        walk runs on the device; same recurrence as MSA_NW_BANDED, +1 on equal symbols
+ *                        and 0 otherwise)
+ *   msa_plan_create_scored, msa_nw_align_scored, msa_nw_align_batch_scored
+ *                        the same alignment under match / mismatch scores or an 8 x 8 substitution
+ *                        matrix over the symbol codes (build extension: MSA_NW_SCORED plans)
  *   msa_plan_traceback_batch, msa_sw_align_batch, msa_nw_align_batch
  *                        the walks of a whole batch plan in one launch, and batches of local / global
  *                        alignments with their CIGARs from host pointers (build extension: one wave per
@@ -220,8 +224,12 @@ typedef enum msa_alg_e {
   MSA_NW_BANDED = 2,  /* reference Gotoh (g=gap_extend, h=gap_open-gap_extend), start type -1, optional band */
   MSA_REF_GOTOH = 3,  /* reference Gotoh T1/T2/T3, any start type, exact -inf */
   MSA_PARTIAL = 4,    /* partial.cpp forward Gotoh, int32 wrap */
-  MSA_NW_ALIGN = 5    /* MSA_NW_BANDED's recurrence with one direction byte per cell (MSA_CELLS_DIR only,
+  MSA_NW_ALIGN = 5,   /* MSA_NW_BANDED's recurrence with one direction byte per cell (MSA_CELLS_DIR only,
                          match = 1, mismatch = 0; walked by msa_plan_traceback_nw) */
+  MSA_NW_SCORED = 6   /* MSA_NW_ALIGN's recurrence, band rule, borders, tie order and direction byte with
+                         f(i,j) = S[code of A_i][code of B_j]: S from match / mismatch, or an 8 x 8 table
+                         (msa_plan_create_scored); MSA_CELLS_DIR (walked by msa_plan_traceback_nw /
+                         msa_plan_traceback_batch) or MSA_CELLS_NONE (the score only) */
 } msa_alg_e;
 
 typedef enum msa_out_e { MSA_CELLS_NONE = 0, MSA_CELLS_H = 1, MSA_CELLS_DIR = 2, MSA_CELLS_TAB = 3 } msa_out_e;
@@ -254,6 +262,16 @@ typedef struct msa_pair_result {
 typedef struct msa_plan msa_plan;
 
 int msa_plan_create(const msa_plan_desc* desc, msa_plan** plan);
+/* msa_plan_create with a substitution table for MSA_NW_SCORED: sub = 64 scores, row-major sub[8*a + b] = the
+ * score of A's code a against B's code b (it need not be symmetric).  sub == NULL: msa_plan_create (an
+ * MSA_NW_SCORED plan then scores desc->match on the diagonal, desc->mismatch elsewhere).  A non-NULL sub with
+ * any other algorithm is MSA_ERR_UNSUPPORTED.  MSA_NW_SCORED needs every score in [-128, 127], gap_extend >= 0,
+ * gap_open >= gap_extend, MSA_CELLS_NONE or MSA_CELLS_DIR, and scores, gap costs and sizes inside the value
+ * range of the int32 cells: with s = the largest |score|, g = gap_extend, G = gap_open,
+ *     (s + 2 G + 2 g) (m + n + 256) + (G - g) < 2^28
+ * for every pair (the derivation is at check_ranges, msa_plan.inc); anything else is MSA_ERR_UNSUPPORTED.  The
+ * band rule and its MSA_ERR_ARG are MSA_NW_ALIGN's. */
+int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_plan** plan);
 void msa_plan_destroy(msa_plan* plan);
 /* Elements (int32 for H/TAB planes, bytes for DIR) the per-cell output needs. */
 int msa_plan_cells_size(const msa_plan* plan, int64_t* elems);
@@ -334,9 +352,11 @@ int msa_plan_traceback(msa_plan* plan, int64_t pair, const uint8_t* dDir, uint8_
  * follow from the ops on the host in O(m+n) (msa_main_alignment does this). */
 int msa_plan_traceback_gotoh(msa_plan* plan, int64_t pair, int end_type, const uint8_t* dDir, uint8_t* d_ops,
                              int64_t ops_cap, int64_t* d_info, void* stream);
-/* Global (Needleman-Wunsch / Gotoh) traceback ON THE DEVICE for an MSA_NW_ALIGN plan, after
+/* Global (Needleman-Wunsch / Gotoh) traceback ON THE DEVICE for an MSA_NW_ALIGN plan (or an MSA_NW_SCORED
+ * plan with MSA_CELLS_DIR), after
  * msa_plan_run on the same stream.  The plan computes MSA_NW_BANDED's recurrence (f = 1 on equal
- * codes else 0, g = gap_extend, h = gap_open - gap_extend >= 0; cells with |i - j| > band are -inf):
+ * codes else 0 -- MSA_NW_SCORED: the plan's table entry --, g = gap_extend, h = gap_open - gap_extend >= 0;
+ * cells with |i - j| > band are -inf):
  *   E(i,j) = max(H(i,j-1) - (g+h), E(i,j-1) - g)      F(i,j) = max(H(i-1,j) - (g+h), F(i-1,j) - g)
  *   H(i,j) = max(H(i-1,j-1) + f, E(i,j), F(i,j))      score = H(m,n)
  * and writes one byte per cell (skewed stripe layout, msa_plan_pair_layout), in the SW-affine
@@ -350,15 +370,15 @@ int msa_plan_traceback_gotoh(msa_plan* plan, int64_t pair, int end_type, const u
  * ops end -> start (at most ops_cap; m+n suffices); d_info[8] as msa_plan_traceback_gotoh: {n_ops,
  * i+1, j+1, status, stripes entered, groups staged on demand, ticks, waits} with (i, j) the border
  * cell where the walk stopped and status 0 or MSA_ERR_CAPACITY.  Asynchronous, one walk per call
- * (msa_plan_traceback_batch walks every pair of a batch plan in one launch).  MSA_ERR_UNSUPPORTED for any plan that is not MSA_NW_ALIGN;
- * msa_plan_traceback and msa_plan_traceback_gotoh reject MSA_NW_ALIGN plans. */
+ * (msa_plan_traceback_batch walks every pair of a batch plan in one launch).  MSA_ERR_UNSUPPORTED for any plan that is not MSA_NW_ALIGN
+ * or MSA_NW_SCORED with direction bytes; msa_plan_traceback and msa_plan_traceback_gotoh reject both. */
 int msa_plan_traceback_nw(msa_plan* plan, int64_t pair, const uint8_t* dDir, uint8_t* d_ops, int64_t ops_cap,
                           int64_t* d_info, void* stream);
 /* Every pair's traceback ON THE DEVICE in ONE launch (msa_tbatch.hip), after msa_plan_run on the same
  * stream: one wave per pair, four walks per workgroup, each wave staging its own stripe groups and writing
  * its own ops (the single walkers above spend a six-wave workgroup on one long walk and take a launch
  * per pair).  Plans: MSA_SW_AFFINE with MSA_CELLS_DIR and track_end (msa_plan_traceback's walk, from each
- * pair's end cell; no walk for a score <= 0) or MSA_NW_ALIGN (msa_plan_traceback_nw's walk, from (m, n) to
+ * pair's end cell; no walk for a score <= 0) or MSA_NW_ALIGN / MSA_NW_SCORED (msa_plan_traceback_nw's walk, from (m, n) to
  * the matrix border; the caller appends the border gap), laid out one row per lane with the stripe starts
  * in the stripe meta: the stripe kernel's batch, split-batch and single launches and the band kernel's.
  * MSA_ERR_UNSUPPORTED, before any launch, for the flow kernels' plans (msa_plan_launch_info mode 1: the
@@ -434,6 +454,23 @@ int msa_nw_align_batch(const char* A, size_t a_len, const char* B, size_t b_len,
                        const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
                        int32_t gap_open, int32_t gap_extend, int64_t band,
                        int32_t* score, char* cigars, size_t cigar_cap, int64_t* cigar_off);
+
+/* msa_nw_align and msa_nw_align_batch under a substitution matrix (build extension: MSA_NW_SCORED plans).
+ * alphabet: n_sym distinct bytes, 1 <= n_sym <= 8; a symbol's code is its index.  sub: n_sym x n_sym scores,
+ * row-major, the row is A's symbol (sub[n_sym * a + b] scores alphabet[a] in A against alphabet[b] in B; it need
+ * not be symmetric).  A duplicate in alphabet, n_sym outside 1..8, or a NULL alphabet or sub: MSA_ERR_ARG.  A
+ * symbol of A or B that is not in alphabet: MSA_ERR_ALPHABET.  Scores and gap costs outside the plan's value
+ * range (msa_plan_create_scored): MSA_ERR_UNSUPPORTED.  Everything else -- the gap and band rules, admission,
+ * chunks of pairs, the border gap, the CIGAR format, MSA_ERR_CAPACITY, cigar(s) == NULL for the score(s) alone
+ * -- is msa_nw_align's and msa_nw_align_batch's. */
+int msa_nw_align_scored(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                        const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band, int32_t* score,
+                        char* cigar, size_t cigar_cap);
+int msa_nw_align_batch_scored(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                              const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                              const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                              int32_t gap_extend, int64_t band, int32_t* score, char* cigars, size_t cigar_cap,
+                              int64_t* cigar_off);
 
 #ifdef __cplusplus
 }
