@@ -279,7 +279,8 @@ __device__ __forceinline__ void fl_profile_aff(int match, int mismatch, int e, i
 }
 
 // Gotoh profile (tagged, shifted): 4 (f + 2g), f = 1 on a match, 0 otherwise (the reference's
-// f, main_alignment.cpp); the virtual code 7 (columns past n) gets 0.
+// f, main_alignment.cpp) for all eight codes: Gotoh has no virtual code (msa_plan_run stages the columns
+// outside [1, n] as code 0), and msa_encode_pair hands code 7 to the eighth symbol of a pair.
 __device__ __forceinline__ void fl_profile_got(int g, unsigned ac, unsigned& plo, unsigned& phi) {
   const int sm = 4 * (1 + 2 * g), sx = 8 * g;
   const unsigned bx = (unsigned)(sx & 0xff) * 0x01010101u;
@@ -288,7 +289,7 @@ __device__ __forceinline__ void fl_profile_got(int g, unsigned ac, unsigned& plo
   if (ac < 4) lo = (lo & ~(0xffu << (8 * ac))) | (bm << (8 * ac));
   else hi = (hi & ~(0xffu << (8 * (ac - 4)))) | (bm << (8 * (ac - 4)));
   plo = lo;
-  phi = hi & 0x00ffffffu;
+  phi = hi;
 }
 
 // Substitution profile of a row: score + g (X-space) or + 2g (G-space) for

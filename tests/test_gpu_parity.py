@@ -762,25 +762,32 @@ def test_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring):
     check_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring)
 
 
-def check_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring, rows=2):
-    """test_sw_affine_flow_dir_bytes' comparison for a flow plan of `rows` rows per lane; returns that plan."""
+def check_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring, rows=2, pair=None, to_dev=None):
+    """test_sw_affine_flow_dir_bytes' comparison for a flow plan of `rows` rows per lane; returns that plan.
+    pair / to_dev: another input (A, B) of m rows and how to bring it to the device as codes (default: the
+    test's own ACGT input)."""
     import torch
     from cse305_parallel_sequence_alignment_amd.plan import Plan
 
-    rng = np.random.default_rng(m * 7 + n)
-    A = rs(rng, m)
-    B = bytes(bytearray(A[: min(m, n)]) + rs(rng, max(0, n - m)))
-    b = bytearray(B)
-    for k in rng.choice(len(b), size=max(1, len(b) // 10), replace=False):
-        b[k] = ACGT[rng.integers(4)]
-    B = bytes(b)
+    to_dev = to_dev or _dev
+    if pair is None:
+        rng = np.random.default_rng(m * 7 + n)
+        A = rs(rng, m)
+        B = bytes(bytearray(A[: min(m, n)]) + rs(rng, max(0, n - m)))
+        b = bytearray(B)
+        for k in rng.choice(len(b), size=max(1, len(b) // 10), replace=False):
+            b[k] = ACGT[rng.integers(4)]
+        B = bytes(b)
+    else:
+        A, B = pair
+        assert len(A) == m
     ma, mi, go, ge = scoring
     out = []
     for single in (True, False):
         pl = Plan(LB.SW_AFFINE, LB.CELLS_DIR, [m], [len(B)], [0], [0], match=ma, mismatch=mi, gap_open=go,
                   gap_extend=ge, track_end=True, single=single)
         D = torch.empty(pl.cells_elems, dtype=torch.uint8, device=dev)
-        pl.run(_dev(A, dev), _dev(B, dev), D)
+        pl.run(to_dev(A, dev), to_dev(B, dev), D)
         r = pl.results()[0]
         info = pl.run_info()
         out.append((pl.deskew_dir(D.cpu().numpy(), 0, pl.stripe_meta()), r["score"], tuple(r["end"]), info["mode"],
@@ -900,20 +907,23 @@ def test_gotoh_flow_dir_bytes(dev, LB, gh, m, n):
     check_gotoh_flow_dir_bytes(dev, LB, gh, m, n)
 
 
-def check_gotoh_flow_dir_bytes(dev, LB, gh, m, n):
-    """test_gotoh_flow_dir_bytes' comparison; returns the flow plan."""
+def check_gotoh_flow_dir_bytes(dev, LB, gh, m, n, pair=None, to_dev=None):
+    """test_gotoh_flow_dir_bytes' comparison; returns the flow plan.  pair / to_dev: another m x n input and how
+    to bring it to the device as codes (default: the test's own ACGT input)."""
     import torch
     from cse305_parallel_sequence_alignment_amd.plan import Plan
 
+    to_dev = to_dev or _dev
     g, h = gh
     rng = np.random.default_rng(m * 3 + n + 17 * g + h)
-    A, B = _mutated(rng, m, n) if m > 100 else (rs(rng, m), rs(rng, n))
+    A, B = pair if pair is not None else (_mutated(rng, m, n) if m > 100 else (rs(rng, m), rs(rng, n)))
+    assert (len(A), len(B)) == (m, n)
     out = []
     for single in (True, False):
         pl = Plan(LB.REF_GOTOH, LB.CELLS_DIR, [m], [n], [0], [0], match=1, mismatch=0, gap_open=g + h,
                   gap_extend=g, start_type=-1, single=single)
         D = torch.empty(pl.cells_elems, dtype=torch.uint8, device=dev)
-        pl.run(_dev(A, dev), _dev(B, dev), D)
+        pl.run(to_dev(A, dev), to_dev(B, dev), D)
         r = pl.results()[0]
         out.append((pl.deskew_dir(D.cpu().numpy(), 0, pl.stripe_meta()), r["score"], tuple(r["fin"]),
                     pl.run_info()["mode"], pl))
@@ -995,20 +1005,29 @@ def test_flow_fill_launch_tall_pairs(oracle, dev, LB, kind):
     check_flow_fill_launch_tall_pair(oracle, dev, LB, kind)
 
 
-def check_flow_fill_launch_tall_pair(oracle, dev, LB, kind):
-    """test_flow_fill_launch_tall_pairs' checks for one kind; returns the plan."""
+TALL_PAIR = (70000, 300)
+
+
+def check_flow_fill_launch_tall_pair(oracle, dev, LB, kind, pair=None, to_dev=None):
+    """test_flow_fill_launch_tall_pairs' checks for one kind; returns the plan.  pair / to_dev: another
+    70,000 x 300 input and how to bring it to the device as codes (default: the test's own ACGT input)."""
     import torch
     from cse305_parallel_sequence_alignment_amd import api
     from cse305_parallel_sequence_alignment_amd.plan import Plan
 
-    m, n = 70000, 300
-    rng = np.random.default_rng(7000 + len(kind))
-    A = rs(rng, m)
-    B = bytearray(A[20000:20000 + n])  # a local match deep in A, mutated
-    for k in rng.choice(n, size=n // 12, replace=False):
-        B[k] = ACGT[rng.integers(4)]
-    B = bytes(B)
-    dA, dB = _dev(A, dev), _dev(B, dev)
+    to_dev = to_dev or _dev
+    m, n = TALL_PAIR
+    if pair is None:
+        rng = np.random.default_rng(7000 + len(kind))
+        A = rs(rng, m)
+        B = bytearray(A[20000:20000 + n])  # a local match deep in A, mutated
+        for k in rng.choice(n, size=n // 12, replace=False):
+            B[k] = ACGT[rng.integers(4)]
+        B = bytes(B)
+    else:
+        A, B = pair
+        assert (len(A), len(B)) == (m, n)
+    dA, dB = to_dev(A, dev), to_dev(B, dev)
     if kind.startswith("swl"):
         te = kind == "swl_h_end"
         pl = Plan(LB.SW_LINEAR, LB.CELLS_H, [m], [n], [0], [0], match=1, mismatch=0, gap_open=1, gap_extend=1,

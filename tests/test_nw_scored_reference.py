@@ -5,6 +5,7 @@ import functools
 import numpy as np
 import pytest
 
+import alphabet8 as A8
 import nw_reference as R
 import nw_scored_reference as RS
 
@@ -15,6 +16,11 @@ BRUTE_SHAPES = [(65, 70, 8), (40, 37, -1), (130, 129, 3), (90, 90, 1)]
 
 def brute_gotoh(A, B, alphabet, S, g, h, band):
     """H(m, n) of the recurrence include/msa.h documents, cell by cell in plain Python (exact -inf)."""
+    return int(brute_gotoh_h(A, B, alphabet, S, g, h, band)[len(A)][len(B)])
+
+
+def brute_gotoh_h(A, B, alphabet, S, g, h, band):
+    """That recurrence's whole H, row-major (m + 1) x (n + 1), -inf outside the band."""
     a, b = RS.codes(A, alphabet), RS.codes(B, alphabet)
     m, n = len(a), len(b)
     w = max(m, n) if band < 0 else band
@@ -32,7 +38,7 @@ def brute_gotoh(A, B, alphabet, S, g, h, band):
             E[i][j] = max(H[i][j - 1] - op, E[i][j - 1] - g)
             F[i][j] = max(H[i - 1][j] - op, F[i - 1][j] - g)
             H[i][j] = max(H[i - 1][j - 1] + int(S[a[i - 1]][b[j - 1]]), E[i][j], F[i][j])
-    return int(H[m][n])
+    return H
 
 
 @functools.lru_cache(maxsize=None)
@@ -50,6 +56,23 @@ def test_against_brute_force(shape, set_name):
     ref = RS.nw_scored_reference(A, B, alphabet, S, g, h, band)
     assert ref["score"] == brute_gotoh(A, B, alphabet, S, g, h, band)
     assert RS.rescore(A, B, ref["ops"], alphabet, S, g, h, band) == ref["score"]
+
+
+@pytest.mark.parametrize("gh", A8.EDGE_GH, ids=lambda t: f"g{t[0]}h{t[1]}")
+@pytest.mark.parametrize("shape", A8.EDGE_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}_w{s[2]}")
+def test_edge_shapes_every_cell_against_brute_force(shape, gh):
+    """The edge shapes of test_gpu_full_alphabet.py over eight symbols and the dense table: every in-band H cell,
+    not only H(m, n), and the walk's ops rescored."""
+    (m, n, band), (g, h) = shape, gh
+    A, B = A8.edge_pair(m, n)
+    ref = RS.nw_scored_reference(A, B, A8.AL8, A8.TABLE8, g, h, band)
+    H = np.array(brute_gotoh_h(A, B, A8.AL8, A8.TABLE8, g, h, band))
+    assert ref["score"] == int(H[m][n])
+    want = R.to_band(np.where(np.isinf(H), R.NEG, H).astype(np.int64), ref["w"], fill=R.NEG)
+    v = ref["valid"]
+    assert v.sum() == sum(min(n, i + ref["w"]) - max(1, i - ref["w"]) + 1 for i in range(1, m + 1))
+    assert np.array_equal(ref["H"][v], want[v])
+    assert RS.rescore(A, B, ref["ops"], A8.AL8, A8.TABLE8, g, h, band) == ref["score"]
 
 
 def test_titv_inputs_hold_n():
