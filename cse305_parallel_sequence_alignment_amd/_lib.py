@@ -24,7 +24,7 @@ STATUS = {
 }
 
 # msa_alg_e / msa_out_e
-SW_LINEAR, SW_AFFINE, NW_BANDED, REF_GOTOH, PARTIAL, NW_ALIGN, NW_SCORED = 0, 1, 2, 3, 4, 5, 6
+SW_LINEAR, SW_AFFINE, NW_BANDED, REF_GOTOH, PARTIAL, NW_ALIGN, NW_SCORED, NW_FIT = 0, 1, 2, 3, 4, 5, 6, 7
 CELLS_NONE, CELLS_H, CELLS_DIR, CELLS_TAB = 0, 1, 2, 3
 
 
@@ -127,6 +127,9 @@ def lib() -> C.CDLL:
     L.msa_nw_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, i32, i32, i64, P, P, sz, P]
     L.msa_nw_align_scored.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, i64, C.POINTER(i32), P, sz]
     L.msa_nw_align_batch_scored.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, i64, P, P, sz, P]
+    L.msa_fit_align.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), P,
+                                sz]
+    L.msa_fit_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, P, P, P, sz, P]
     _lib = L.lib
     return _lib
 
@@ -154,4 +157,5 @@ EXPORTED = [
     "msa_plan_last_kernel_ms", "msa_plan_set_timing", "msa_encode_pair", "msa_sw_align", "msa_nw_align",
     "msa_plan_traceback_batch", "msa_sw_align_batch", "msa_nw_align_batch",
     "msa_plan_create_scored", "msa_nw_align_scored", "msa_nw_align_batch_scored",
+    "msa_fit_align", "msa_fit_align_batch",
 ]

@@ -438,3 +438,66 @@ def nw_align_batch(As, Bs, gap_open=3, gap_extend=1, band=-1, traceback=True, ma
             r["cigar"] = cig.raw[coff[p]:coff[p + 1] - 1].decode()
         out.append(r)
     return out
+
+
+def _fit_scoring(seqs, match, mismatch, alphabet, matrix):
+    """_nw_scoring, with +1 / 0 over the symbols of ``seqs`` when none of the four arguments is given (the fit
+    entries always take an alphabet and a matrix)."""
+    scoring = _nw_scoring(seqs, match, mismatch, alphabet, matrix)
+    return _nw_scoring(seqs, 1, 0, None, None) if scoring is None else scoring
+
+
+def fit_align(query, ref, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
+              matrix=None):
+    """Fit ("glocal", "semi-global", "infix") alignment (build extension, msa_fit_align): ALL of ``query`` against
+    the substring of ``ref`` it fits best -> dict(score, beg, end[, cigar]), ``ref[beg:end]`` being that substring.
+
+    Reference symbols before ``beg`` and from ``end`` on are free; a gap of L costs (gap_open - gap_extend) +
+    gap_extend * L.  Of equally good alignments the one ending first in the reference is reported.  The CIGAR
+    (start -> end, I consumes the query, D the reference) consumes all of the query and ``end - beg`` reference
+    symbols; ``beg == end`` when the best alignment inserts the whole query.  ``traceback=False`` gives the score
+    and ``end`` only (``beg`` is None).  Scoring as for nw_align: ``match`` / ``mismatch``, or ``alphabet`` with
+    ``matrix``; with none given +1 / 0."""
+    A, B = _buf(query), _buf(ref)
+    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix)
+    sc = C.c_int32()
+    bj, ej = C.c_int64(), C.c_int64()
+    cap = 4 * (len(A) + len(B)) + 16
+    cig = C.create_string_buffer(cap) if traceback else None
+    LB.check(LB.lib().msa_fit_align(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open,
+                                    gap_extend, C.byref(sc), C.byref(bj), C.byref(ej), cig,
+                                    cap if traceback else 0), "msa_fit_align")
+    r = dict(score=sc.value, beg=bj.value if traceback else None, end=ej.value)
+    if traceback:
+        r["cigar"] = cig.value.decode()
+    return r
+
+
+def fit_align_batch(queries, refs, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None,
+                    alphabet=None, matrix=None):
+    """A batch of fit alignments (msa_fit_align_batch) -> a list of fit_align()'s dicts.
+
+    ``refs``: a list as long as ``queries``, or one bytes object every query is aligned against (uploaded once),
+    exactly like nw_align_batch's ``Bs``; scoring as for fit_align, over one alphabet for the whole call (``match``
+    / ``mismatch``: the distinct symbols of all queries, then all refs, in first-seen order)."""
+    if len(queries) == 0:
+        return []
+    A, B, a_off, m, b_off, n = _batch_in(queries, refs)
+    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix)
+    k = len(m)
+    sc = np.zeros(k, dtype=np.int32)
+    be = np.zeros((k, 2), dtype=np.int64)
+    coff = np.zeros(k + 1, dtype=np.int64)
+    cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
+    cig = C.create_string_buffer(cap) if traceback else None
+    LB.check(LB.lib().msa_fit_align_batch(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
+                                          alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend,
+                                          sc.ctypes.data_as(C.c_void_p), _i64p(be), cig, cap,
+                                          _i64p(coff) if traceback else None), "msa_fit_align_batch")
+    out = []
+    for p in range(k):
+        r = dict(score=int(sc[p]), beg=int(be[p, 0]) if traceback else None, end=int(be[p, 1]))
+        if traceback:
+            r["cigar"] = cig.raw[coff[p]:coff[p + 1] - 1].decode()
+        out.append(r)
+    return out

@@ -349,7 +349,7 @@ StreamPool& stream_pool() {
 int nc_of(int alg) {
   switch (alg) {
     case MSA_ALG_SWL: case MSA_ALG_SWL0: case MSA_ALG_SWLP: return 1;
-    case MSA_ALG_SWA: case MSA_ALG_NWA: case MSA_ALG_REF1: return 2;
+    case MSA_ALG_SWA: case MSA_ALG_NWA: case MSA_ALG_REF1: case MSA_ALG_FIT: return 2;
     default: return 3;
   }
 }
@@ -461,6 +461,11 @@ kfn_t pick_kernel(int alg, int out, int tp, bool sgl) {
       break;
     case MSA_ALG_PART:
       if (out == MSA_OUT_TAB) return kf<MSA_ALG_PART, MSA_OUT_TAB, 0>(sgl);
+      break;
+    case MSA_ALG_FIT:
+      // (instantiations of their own: the MSA_ALG_NWA kernels' code is unchanged)
+      if (out == MSA_OUT_NONE) return kf<MSA_ALG_FIT, MSA_OUT_NONE, 0>(sgl);
+      if (out == MSA_OUT_DIR) return kf<MSA_ALG_FIT, MSA_OUT_DIR, 0>(sgl);
       break;
   }
 #undef K3
@@ -701,7 +706,8 @@ int msa_plan_run(msa_plan* P, const uint8_t* dA, const uint8_t* dB, void* c0, vo
     }
     return MSA_OK;
   }
-  const int sw = (is_linear(P->main.kp.alg) || P->main.kp.alg == MSA_ALG_SWA) ? 1 : 0;
+  // (2: a fit plan's pair result is the first maximum of row m, from the meta of the stripe that holds it)
+  const int sw = (is_linear(P->main.kp.alg) || P->main.kp.alg == MSA_ALG_SWA) ? 1 : (P->main.kp.alg == MSA_ALG_FIT ? 2 : 0);
   const int np = (int)P->d.n_pairs;
   hipLaunchKernelGGL(reduce_pairs_kernel, dim3(np), dim3(64), 0, st, P->d_pairs, P->d_meta, np, sw,
                      P->d_res);
@@ -859,11 +865,13 @@ int msa_plan_traceback_gotoh(msa_plan* P, int64_t pair, int end_type, const uint
 int msa_plan_traceback_nw(msa_plan* P, int64_t pair, const uint8_t* dDir, uint8_t* d_ops, int64_t ops_cap,
                           int64_t* d_info, void* stream) {
   if (!P || !dDir || !d_ops || !d_info || ops_cap < 0 || pair < 0 || pair >= P->d.n_pairs) return MSA_ERR_ARG;
-  if (!nw_bytes(P)) return MSA_ERR_UNSUPPORTED;
+  const bool fit = fit_bytes(P);
+  if (!nw_bytes(P) && !fit) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   P->note_stream(st);
-  // stripe starts from the stripe meta (band geometry); the walk needs no end type and no PairResult
-  hipLaunchKernelGGL(traceback_kernel<TB_NW>, dim3(1), dim3(384), 0, st, dDir, P->d_pairs, P->d_meta,
+  // stripe starts from the stripe meta (band geometry); the walk needs no end type and no PairResult (a fit plan's
+  // walk, TB_FIT: the same walk from the run's end cell (m, end_j) in its PairResult)
+  hipLaunchKernelGGL((fit ? traceback_kernel<TB_FIT> : traceback_kernel<TB_NW>), dim3(1), dim3(384), 0, st, dDir, P->d_pairs, P->d_meta,
                      (const PairResult*)P->d_res, (int)pair, 0, 0, d_ops, (long long)ops_cap, (long long*)d_info, 0,
                      (const unsigned long long*)nullptr);
   HIPCHK(hipGetLastError());
@@ -880,11 +888,12 @@ int msa_plan_traceback_batch(msa_plan* P, const uint8_t* dDir, uint8_t* d_ops, c
   // (the SW walk starts at the fill's end cell: plans without track_end have none)
   const bool sw = P->d.alg == MSA_SW_AFFINE && P->main.kp.alg == MSA_ALG_SWA && P->d.cells == MSA_CELLS_DIR &&
                   P->d.track_end;
-  if (!nw && !sw) return MSA_ERR_UNSUPPORTED;
+  const bool fit = fit_bytes(P);  // (the global walk from each pair's end cell (m, end_j))
+  if (!nw && !sw && !fit) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   P->note_stream(st);
   const int np = (int)P->d.n_pairs;
-  hipLaunchKernelGGL((nw ? traceback_batch_kernel<TB_NW> : traceback_batch_kernel<TB_SW>),
+  hipLaunchKernelGGL((fit ? traceback_batch_kernel<TB_FIT> : nw ? traceback_batch_kernel<TB_NW> : traceback_batch_kernel<TB_SW>),
                      dim3((unsigned)((np + TBB_WPB - 1) / TBB_WPB)), dim3(64 * TBB_WPB), 0, st, dDir, P->d_pairs,
                      P->d_meta, (const PairResult*)P->d_res, np, d_ops, (const long long*)d_ops_off,
                      (long long*)d_info);

@@ -92,6 +92,9 @@ constexpr bool swlin(int alg) { return alg == MSA_ALG_SWL || alg == MSA_ALG_SWL0
 constexpr bool pk16(int alg) { return alg == MSA_ALG_SWLP; }
 template <> struct Tr<MSA_ALG_SWA> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_NWA> { static constexpr int NC = 2; };
+template <> struct Tr<MSA_ALG_FIT> { static constexpr int NC = 2; };
+// the banded Gotoh cell (MSA_ALG_NWA), or the same cell under the fit alignment's zero top border (MSA_ALG_FIT)
+constexpr bool nwa(int alg) { return alg == MSA_ALG_NWA || alg == MSA_ALG_FIT; }
 template <> struct Tr<MSA_ALG_REF> { static constexpr int NC = 3; };
 template <> struct Tr<MSA_ALG_REF1> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_PART> { static constexpr int NC = 3; };
@@ -190,7 +193,7 @@ struct KArgs {
   // two-pass SW single pair: the pass-2 blocks fold the pair result into this key themselves
   // (fl_block_result, msa_flow.hip) when set; else reduce_blocks_kernel runs after the launch
   unsigned long long* best_key;
-  // MSA_ALG_NWA: the plan's substitution table, one 8-byte profile per row code (byte b of entry a = the
+  // MSA_ALG_NWA, MSA_ALG_FIT: the plan's substitution table, one 8-byte profile per row code (byte b of entry a = the
   // score of row code a against column code b, in the launch's own space: msa_plan.inc, sub_table)
   const uint2* sub;
 };
@@ -212,6 +215,12 @@ __device__ __forceinline__ void border_top(const msa_kparams& kp, int c, int (&v
   } else if constexpr (ALG == MSA_ALG_SWA) {
     v[0] = c >= 0 ? 0 : MSA_NEG;  // H
     v[1] = MSA_NEG;               // F
+    v[2] = MSA_NEG;
+  } else if constexpr (ALG == MSA_ALG_FIT) {
+    // the reference's symbols before the aligned substring are free: H(0,c) = 0 on every column c >= 0 (columns
+    // past n are masked where they are read, as MSA_ALG_NWA's are); E = F = -inf
+    v[0] = c >= 0 ? 0 : MSA_NEG;
+    v[1] = MSA_NEG;
     v[2] = MSA_NEG;
   } else if constexpr (ALG == MSA_ALG_NWA) {
     if (r0 > 0) {
@@ -271,7 +280,7 @@ __device__ __forceinline__ void border_left(const msa_kparams& kp, int i, int (&
     v[0] = 0;        // H
     v[1] = MSA_NEG;  // E
     v[2] = MSA_NEG;  // F
-  } else if constexpr (ALG == MSA_ALG_NWA) {
+  } else if constexpr (nwa(ALG)) {  // (FIT: kp.band = -1)
     const bool inb = (kp.band < 0) || (i <= kp.band);
     v[0] = inb ? -kp.h - kp.gap_ext * i : MSA_NEG;  // H
     v[1] = MSA_NEG;                                 // T2 (E)
@@ -371,7 +380,7 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
     nS[1] = e;
     nS[2] = f;
     L.U[0] = upH;
-  } else if constexpr (ALG == MSA_ALG_NWA) {
+  } else if constexpr (nwa(ALG)) {
     const int upH = dpp_shr1(in[0], L.S[0]);
     const int upF = dpp_shr1(in[1], L.S[2]);
     const int t3 = imax(upH - kp.gap_open, upF - kp.gap_ext);
@@ -502,7 +511,7 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
   // carried values (what the lane below / next stripe needs)
   if constexpr (swlin(ALG)) {
     carry[0] = nS[0];
-  } else if constexpr (ALG == MSA_ALG_SWA || ALG == MSA_ALG_NWA || ALG == MSA_ALG_REF1) {
+  } else if constexpr (ALG == MSA_ALG_SWA || nwa(ALG) || ALG == MSA_ALG_REF1) {
     carry[0] = nS[0];
     carry[1] = nS[2];
   } else {
@@ -528,8 +537,10 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
 // final cell at t == tmax.  Cost: 2 compares + 5 selects per step, against ~13 for
 // the range masks -- and for a band the masked head phases are the chain's
 // critical path (stripe k+1 starts ~9 phases into stripe k).
-template <bool FIN>
-__device__ __forceinline__ void band_fix(LaneState<MSA_ALG_NWA>& L, int t, int (&carry)[3]) {
+// (MSA_ALG_FIT, no band: the same two edges are column 0 and column n + 1)
+template <bool FIN, int ALG>
+__device__ __forceinline__ void band_fix(LaneState<ALG>& L, int t, int (&carry)[3]) {
+  static_assert(nwa(ALG), "the Gotoh cell's state order");
   const bool fl = (t == L.tmin - 1);
 #pragma unroll
   for (int v = 0; v < 3; ++v) L.S[v] = fl ? L.LB[v] : L.S[v];
@@ -974,7 +985,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
       // row is taken by selects at the stripe's start (a load at a.sub[ac] would wait for ac here, in front of the
       // workgroup's barriers)
       uint2 tab[8] = {};
-      if constexpr (ALG == MSA_ALG_NWA) {
+      if constexpr (nwa(ALG)) {
 #pragma unroll
         for (int c = 0; c < 8; ++c) tab[c] = a.sub[c];
       }
@@ -992,7 +1003,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
 #pragma unroll
         for (int v = 0; v < 3; ++v) { L.LB[v] = lb[v]; L.S[v] = lb[v]; L.U[v] = MSA_NEG; L.fin[v] = 0; }
       }
-      L.best = 0;
+      L.best = (ALG == MSA_ALG_FIT) ? INT32_MIN : 0;  // (FIT: every H(m, j) is finite, > MSA_NEG)
       L.bt = -1;
       L.pb = (int)0x80008000u;
       const int gdiag = kp.gap_open * (64 * ks + 1 + sg.cs);  // SWL: g*(i+j) at step 0, same for all lanes
@@ -1015,7 +1026,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         }
       }
       // substitution profile of this row (codes 0..7)
-      if constexpr (ALG == MSA_ALG_NWA) {
+      if constexpr (nwa(ALG)) {
         L.plo = tab[0].x;
         L.phi = tab[0].y;
 #pragma unroll
@@ -1257,11 +1268,22 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
                   cr[1] = L.S[2];
                 }
               }
-            } else if constexpr (ALG == MSA_ALG_NWA && MASKED) {
+            } else if constexpr (nwa(ALG) && MASKED) {
               d = step<ALG, OUT, false, TRACKPOS, false>(kp, L, inv, s, t, ct, cr, hv[k]);
               band_fix<FIN>(L, t, cr);
             } else {
               d = step<ALG, OUT, MASKED, TRACKPOS, FIN>(kp, L, inv, s, t, ct, cr, hv[k]);
+            }
+            if constexpr (ALG == MSA_ALG_FIT && FIN) {
+              // the stripe of row m (every phase of it, the unmasked body too: FIN): a lane keeps the first
+              // maximum of its row's H over the row's own columns 1..n -- strict >, so the earliest step wins;
+              // a step on column <= 0 or > n (t outside [tmin, tmax]) never counts, and in an unmasked phase
+              // the lane of row m is inside its range by mask_lo / mask_hi.  One compare and two selects per
+              // step, in this stripe alone; only the lane of row m is read (stripe finalize).
+              const bool inr = !MASKED || (t >= L.tmin && t <= L.tmax);
+              const bool better = inr && L.S[0] > L.best;
+              L.best = better ? L.S[0] : L.best;
+              L.bt = better ? t : L.bt;
             }
 #pragma unroll
             for (int v = 0; v < NC; ++v) hist[v][k] = cr[v];
@@ -1384,7 +1406,8 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         run_range(qi, P, F_{}, T_{}, F_{});
       } else if (fin_stripe) {
         run_range(0, qa, T_{}, T_{}, T_{});
-        run_range(qa, qb, F_{}, F_{}, F_{});
+        if constexpr (ALG == MSA_ALG_FIT) run_range(qa, qb, F_{}, F_{}, T_{});  // (row m's maximum: every phase)
+        else run_range(qa, qb, F_{}, F_{}, F_{});
         run_range(qb, P, T_{}, T_{}, T_{});
       } else {
         // banded Gotoh, a full stripe away from the matrix borders: lane r's first step is
@@ -1481,6 +1504,11 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         }
       } else {
         if (L.i == m) {
+          if constexpr (ALG == MSA_ALG_FIT) {
+            md->best = L.best;
+            md->best_i = m;
+            md->best_j = sg.cs + L.bt - lane;
+          }
           md->fin[0] = L.fin[0];
           md->fin[1] = L.fin[1];
           md->fin[2] = L.fin[2];
@@ -1709,6 +1737,7 @@ __global__ __launch_bounds__(256) void chunk_add_kernel(int32_t* H, const int16_
 
 __global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* pairs, const msa_stripe_meta* meta,
                                                          int n_pairs, int sw, PairResult* out) {
+  // sw: 1 Smith-Waterman (the best cell of any stripe), 0 global (the final state at (m, n)), 2 fit alignment
   // one wave per pair: lanes stride over the pair's stripes (a serial loop of
   // dependent meta loads took ~27 us for a 157-stripe pair)
   const int p = blockIdx.x;
@@ -1720,7 +1749,7 @@ __global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* p
   r.status = 0;
   r.pad = 0;
   r.fin[0] = r.fin[1] = r.fin[2] = 0;
-  if (sw) {
+  if (sw == 1) {
     // first max in row-major order; the empty alignment (score 0 at (0,0))
     // wins unless some stripe has a positive best
     int b = 0, bi = 0, bj = 0;
@@ -1745,6 +1774,12 @@ __global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* p
     r.end_i = pd.m;
     r.end_j = pd.n;
     r.status = md.has_fin ? 0 : -1;
+    if (sw == 2) {
+      // fit alignment: the first maximum of row m, found by the stripe of row m (fin stays (H, E, F) at (m, n),
+      // which is not part of this algorithm's result)
+      r.score = md.best;
+      r.end_j = md.best_j;
+    }
   }
   if (lane == 0) out[p] = r;
 }

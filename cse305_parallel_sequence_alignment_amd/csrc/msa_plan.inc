@@ -153,6 +153,8 @@ struct Extents { int S = 0, P = 0; };  // most stripes / most 16-step layout blo
 bool nw_bytes(const msa_plan* P) {
   return (P->d.alg == MSA_NW_ALIGN || P->d.alg == MSA_NW_SCORED) && P->d.cells == MSA_CELLS_DIR;
 }
+// ... the fit alignment's (the same bytes; the walks start at each pair's end cell (m, end_j))
+bool fit_bytes(const msa_plan* P) { return P->d.alg == MSA_NW_FIT && P->d.cells == MSA_CELLS_DIR; }
 
 // ---- step 1: kernel algorithm and end-cell tracking mode --------------------------------------------
 int choose_algorithm(const msa_plan_desc* desc, int& kalg, int& tp) {
@@ -192,6 +194,15 @@ int choose_algorithm(const msa_plan_desc* desc, int& kalg, int& tp) {
       kalg = MSA_ALG_NWA;
       if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->gap_extend < 0 ||
           desc->gap_open < desc->gap_extend)
+        return MSA_ERR_UNSUPPORTED;
+      break;
+    case MSA_NW_FIT:
+      // MSA_NW_SCORED's cell under a zero top border, with the first maximum of row m as the result: a kernel
+      // algorithm of its own (new stripe_kernel instantiations).  No band (|i - j| <= band means nothing when the
+      // reference's ends are free), direction bytes or the score alone
+      kalg = MSA_ALG_FIT;
+      if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->gap_extend < 0 ||
+          desc->gap_open < desc->gap_extend || desc->band != -1)
         return MSA_ERR_UNSUPPORTED;
       break;
     case MSA_REF_GOTOH: {
@@ -247,7 +258,7 @@ int sub_abs_max(const int8_t* sub) {
   for (int k = 0; k < 64; ++k) s = std::max(s, std::abs((int)sub[k]));
   return s;
 }
-// `scored`: the table of an MSA_NW_SCORED plan (nullptr for every other plan)
+// `scored`: the table of an MSA_NW_SCORED or MSA_NW_FIT plan (nullptr for every other plan)
 int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t* scored) {
   for (int64_t p = 0; p < desc->n_pairs; ++p) {
     const int64_t m = desc->m[p], n = desc->n[p];
@@ -275,6 +286,9 @@ int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t*
       // chunk_add_kernel take for -inf (the walk reads bytes only), every drifted -inf in [-2^30 - 2^28, -2^30 + 2^28],
       // below that threshold, and everything inside int32.  (The chunk warm-up compares rows up to a constant and
       // falls back to the exact launch: negative scores change how often it converges, not what it computes.)
+      // MSA_NW_FIT (MSA_ALG_FIT, stripe_kernel only, unshifted) adds one source, its top border H(0, j) = 0: within
+      // the bound like the corner's 0.  Its paths, steps, left border and -inf are the unbanded MSA_ALG_NWA's, and
+      // what it forms beside the cells is a copy of one of them (the row-m maximum): the same inequality holds.
       const int64_t s = sub_abs_max(scored), g = kp.gap_ext, h = kp.h, G = kp.gap_open;
       if ((s + 2 * G + 2 * g) * (m + n + 256) + h >= (int64_t(1) << 28)) return MSA_ERR_UNSUPPORTED;
     }
@@ -398,8 +412,8 @@ PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp, int smax) {
   bool eq_m = true;
   for (int64_t p = 1; p < desc->n_pairs; ++p) eq_m = eq_m && desc->m[p] == desc->m[0];
   if (eq_m && batch_items(desc, kalg) < slots && stripes_of(desc->m[0]) >= 2 * MSA_WAVES_BATCH && band < 0 &&
-      desc->alg != MSA_NW_ALIGN && desc->alg != MSA_NW_SCORED)  // (a batch of global alignments with direction
-                                                                // bytes, or scored: whole pairs per workgroup)
+      desc->alg != MSA_NW_ALIGN && desc->alg != MSA_NW_SCORED &&  // (a batch of global alignments with direction
+      desc->alg != MSA_NW_FIT)                                    // bytes, scored or fit: whole pairs per workgroup)
     return PM_SPLIT;
   return PM_STRIPE;
 }
@@ -712,7 +726,7 @@ int alloc_buffers(msa_plan& P) {
   if (!P.alloc(&P.d_segs, sizeof(msa_pair_desc) * P.segs.size())) return MSA_ERR_HIP;
   HIPCHK(hipMemcpy(P.d_segs, P.segs.data(), sizeof(msa_pair_desc) * P.segs.size(), hipMemcpyHostToDevice));
   if (!P.alloc(&P.d_res, sizeof(PairResult) * np) || !P.alloc(&P.d_sum, 64)) return MSA_ERR_HIP;
-  if (P.main.kp.alg == MSA_ALG_NWA) {
+  if (P.main.kp.alg == MSA_ALG_NWA || P.main.kp.alg == MSA_ALG_FIT) {
     // the substitution table, one 8-byte profile per row code: band_kernel's bytes are S + 2g + h (its values are
     // shifted by g (i + j); wrapped to a byte as the kernel's own arithmetic did for the 1 / 0 plans), stripe_kernel's S
     const bool bandk = P.mode == PM_BAND || P.mode == PM_BAND_CHUNKED;
@@ -781,7 +795,7 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** out) { return msa_plan
 
 int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_plan** out) {
   if (!desc || !out || desc->n_pairs <= 0 || !desc->m || !desc->n || !desc->a_off || !desc->b_off) return MSA_ERR_ARG;
-  if (sub && desc->alg != MSA_NW_SCORED) return MSA_ERR_UNSUPPORTED;
+  if (sub && desc->alg != MSA_NW_SCORED && desc->alg != MSA_NW_FIT) return MSA_ERR_UNSUPPORTED;
   int rc = ensure_device();
   if (rc != MSA_OK) return rc;
   // (a plan without device buffers yet destroys cleanly: no streams, no blocks, null events)
@@ -802,8 +816,8 @@ int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_pla
   P->nc = nc_of(kalg);
   if (kalg == MSA_ALG_NWA && P->main.kp.h < 0) return MSA_ERR_UNSUPPORTED;
   // the substitution scores of the banded recurrence: MSA_NW_SCORED's table, or its match / mismatch; 1 / 0 for
-  // MSA_NW_BANDED and MSA_NW_ALIGN, whatever their description says
-  const bool scored = desc->alg == MSA_NW_SCORED;
+  // MSA_NW_BANDED and MSA_NW_ALIGN, whatever their description says; MSA_NW_FIT scores as MSA_NW_SCORED does
+  const bool scored = desc->alg == MSA_NW_SCORED || desc->alg == MSA_NW_FIT;
   int smax = 0;
   if (scored && !sub && (desc->match < -128 || desc->match > 127 || desc->mismatch < -128 || desc->mismatch > 127))
     return MSA_ERR_UNSUPPORTED;

@@ -1243,9 +1243,11 @@ struct NwScoring {
   }
 };
 
-// msa_nw_align (sc == nullptr) and msa_nw_align_scored
+// msa_nw_align (sc == nullptr), msa_nw_align_scored and msa_fit_align (fit_be != nullptr: an MSA_NW_FIT plan, no
+// band, the walk from (m, end_j); fit_be = {beg_j, end_j}, beg_j = -1 without a walk)
 int nw_align_one(const char* A0, size_t m, const char* B0, size_t n, const NwScoring* sc, int32_t gap_open,
-                 int32_t gap_extend, int64_t band_in, int32_t* score, char* cigar, size_t cigar_cap) {
+                 int32_t gap_extend, int64_t band_in, int32_t* score, char* cigar, size_t cigar_cap,
+                 int64_t* fit_be = nullptr) {
   if (!A0 || !B0 || m == 0 || n == 0 || m > (size_t(1) << 26) || n > (size_t(1) << 26) || band_in < -1)
     return MSA_ERR_ARG;
   if (gap_extend < 0 || gap_open < gap_extend) return MSA_ERR_UNSUPPORTED;
@@ -1272,7 +1274,7 @@ int nw_align_one(const char* A0, size_t m, const char* B0, size_t n, const NwSco
   msa_plan_desc d;
   std::memset(&d, 0, sizeof(d));
   // the score alone needs no direction bytes: the value plan of the same recurrence (a scored plan has both)
-  d.alg = sc ? MSA_NW_SCORED : (want_tb ? MSA_NW_ALIGN : MSA_NW_BANDED);
+  d.alg = fit_be ? MSA_NW_FIT : sc ? MSA_NW_SCORED : (want_tb ? MSA_NW_ALIGN : MSA_NW_BANDED);
   d.cells = want_tb ? MSA_CELLS_DIR : MSA_CELLS_NONE;
   d.match = 1;
   d.mismatch = 0;
@@ -1302,6 +1304,10 @@ int nw_align_one(const char* A0, size_t m, const char* B0, size_t n, const NwSco
   msa_pair_result res;
   if ((rc = msa_plan_results(pg.p, &res, sg.s)) != MSA_OK) return rc;
   if (score) *score = res.score;
+  if (fit_be) {
+    fit_be[0] = -1;
+    fit_be[1] = res.end_j;
+  }
   if (!want_tb) return MSA_OK;
   int64_t info[4];
   HIPCHK(hipMemcpyAsync(info, dInfo.p, sizeof(info), hipMemcpyDeviceToHost, sg.s));
@@ -1313,9 +1319,11 @@ int nw_align_one(const char* A0, size_t m, const char* B0, size_t n, const NwSco
     HIPCHK(hipStreamSynchronize(sg.s));
   }
   // the walk stopped on the matrix border at (i, j): the rest is one gap along it
+  // (a fit alignment: the reference's symbols before column j are free -- no 'D'; the aligned substring starts there)
   const int64_t bi = info[1] - 1, bj = info[2] - 1;
   if (bi > 0) ops.insert(ops.end(), (size_t)bi, 'I');
-  else if (bj > 0) ops.insert(ops.end(), (size_t)bj, 'D');
+  else if (bj > 0 && !fit_be) ops.insert(ops.end(), (size_t)bj, 'D');
+  if (fit_be) fit_be[0] = bj;
   // ops run from (m, n) back to (0, 0): run-length encode them reversed
   std::string c;
   for (int64_t k = (int64_t)ops.size() - 1; k >= 0;) {
@@ -1348,6 +1356,22 @@ int msa_nw_align_scored(const char* A0, size_t m, const char* B0, size_t n, cons
   return nw_align_one(A0, m, B0, n, &sc, gap_open, gap_extend, band, score, cigar, cigar_cap);
 }
 
+int msa_fit_align(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                  const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_j,
+                  int64_t* end_j, char* cigar, size_t cigar_cap) {
+  NwScoring sc;
+  int rc = sc.set(alphabet, n_sym, sub);
+  if (rc != MSA_OK) return rc;
+  int64_t be[2] = {-1, -1};
+  rc = nw_align_one(A0, m, B0, n, &sc, gap_open, gap_extend, -1, score, cigar, cigar_cap, be);
+  // (a cigar too small still has its score and span)
+  if (rc == MSA_OK || rc == MSA_ERR_CAPACITY) {
+    if (beg_j) *beg_j = be[0];
+    if (end_j) *end_j = be[1];
+  }
+  return rc;
+}
+
 }  // extern "C"
 
 // ---- batches of alignments with their CIGARs (msa_sw_align_batch, msa_nw_align_batch) ----------------------
@@ -1376,9 +1400,11 @@ void append_cigar(std::string& out, const std::string& ops) {
 // single-pair footprints fit a quarter of the device budget): admit, upload the chunk's code spans, one batch
 // plan, one run, one msa_plan_traceback_batch, fetch results, info and ops, build the CIGARs.
 // sc (nw only): the scored entry's alphabet and matrix instead of +1 / 0 over the call's own symbol map
+// fit_be (nw with sc only; msa_fit_align_batch): MSA_NW_FIT plans, no band, each walk from its pair's (m, end_j);
+// fit_be receives {beg_j, end_j} per pair, beg_j = -1 without walks
 int align_batch(bool nw, const BatchIn& in, const NwScoring* sc, int32_t match, int32_t mismatch, int32_t gap_open,
                 int32_t gap_extend, int64_t band_in, int32_t* score, int64_t* end_ij, int64_t* beg_ij, char* cigars,
-                size_t cigar_cap, int64_t* cigar_off) {
+                size_t cigar_cap, int64_t* cigar_off, int64_t* fit_be = nullptr) {
   if (!in.A || !in.B || !in.a_off || !in.m || !in.b_off || !in.n || in.np < 1 || (cigars && !cigar_off))
     return MSA_ERR_ARG;
   if (nw && band_in < -1) return MSA_ERR_ARG;
@@ -1466,7 +1492,7 @@ int align_batch(bool nw, const BatchIn& in, const NwScoring* sc, int32_t match, 
     std::memset(&d, 0, sizeof(d));
     if (nw) {
       // the scores alone need no direction bytes: the value plan of the same recurrence (a scored plan has both)
-      d.alg = sc ? MSA_NW_SCORED : (want_tb ? MSA_NW_ALIGN : MSA_NW_BANDED);
+      d.alg = fit_be ? MSA_NW_FIT : sc ? MSA_NW_SCORED : (want_tb ? MSA_NW_ALIGN : MSA_NW_BANDED);
       d.match = 1;
       d.mismatch = 0;
       d.start_type = -1;
@@ -1509,6 +1535,10 @@ int align_batch(bool nw, const BatchIn& in, const NwScoring* sc, int32_t match, 
         end_ij[2 * (p0 + k)] = res[(size_t)k].end_i;
         end_ij[2 * (p0 + k) + 1] = res[(size_t)k].end_j;
       }
+      if (fit_be) {
+        fit_be[2 * (p0 + k)] = -1;
+        fit_be[2 * (p0 + k) + 1] = res[(size_t)k].end_j;
+      }
     }
     if (want_tb) {
       std::vector<int64_t> info(8 * (size_t)K);
@@ -1523,8 +1553,10 @@ int align_batch(bool nw, const BatchIn& in, const NwScoring* sc, int32_t match, 
         if (nw) {
           // the walk stopped on the matrix border at (i, j): the rest is one gap along it
           const int64_t bi = inf[1] - 1, bj = inf[2] - 1;
+          // (a fit alignment: the reference's symbols before column j are free -- no 'D')
           if (bi > 0) o.append((size_t)bi, 'I');
-          else if (bj > 0) o.append((size_t)bj, 'D');
+          else if (bj > 0 && !fit_be) o.append((size_t)bj, 'D');
+          if (fit_be) fit_be[2 * (p0 + k)] = bj;
         } else if (beg_ij) {
           beg_ij[2 * (p0 + k)] = inf[1];
           beg_ij[2 * (p0 + k) + 1] = inf[2];
@@ -1578,6 +1610,20 @@ int msa_nw_align_batch_scored(const char* A, size_t a_len, const char* B, size_t
   const BatchIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
   return align_batch(true, in, &sc, 1, 0, gap_open, gap_extend, band, score, nullptr, nullptr, cigars, cigar_cap,
                      cigar_off);
+}
+
+int msa_fit_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                        const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                        const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                        int32_t gap_extend, int32_t* score, int64_t* beg_end, char* cigars, size_t cigar_cap,
+                        int64_t* cigar_off) {
+  NwScoring sc;
+  const int rc = sc.set(alphabet, n_sym, sub);
+  if (rc != MSA_OK) return rc;
+  if (!beg_end) return MSA_ERR_ARG;
+  const BatchIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  return align_batch(true, in, &sc, 1, 0, gap_open, gap_extend, -1, score, nullptr, nullptr, cigars, cigar_cap,
+                     cigar_off, beg_end);
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 // every pair of the plan.
 //
 // The bytes, the skewed stripe layout, the transitions and their tie order are msa_traceback.hip's (TB_SW and
-// TB_NW, one row per lane, stripe starts from the stripe meta).  What differs:
+// TB_NW, one row per lane, stripe starts from the stripe meta; TB_FIT: TB_NW from each pair's end cell).  What differs:
 //  * a wave stages its own groups.  It owns one LDS slot of TBB_GB consecutive 1 KiB blocks of one stripe,
 //    fills it by LDS-DMA (glds16x16, or glds16 with the last block repeated for a stripe of fewer blocks),
 //    waits with its own s_waitcnt vmcnt(0) and walks the slot with the run / window loop of the single
@@ -54,8 +54,9 @@ __global__ __launch_bounds__(64 * TBB_WPB) void traceback_batch_kernel(
     const uint8_t* __restrict__ dir, const msa_pair_desc* __restrict__ pairs, const msa_stripe_meta* __restrict__ meta,
     const PairResult* __restrict__ res, int n_pairs, uint8_t* __restrict__ ops_base,
     const long long* __restrict__ ops_off, long long* __restrict__ info) {
-  static_assert(KIND == TB_SW || KIND == TB_NW, "one row per lane, SW-affine bytes");
-  constexpr bool REF = KIND == TB_NW;  // a global walk: from (m, n) to the matrix border
+  static_assert(KIND == TB_SW || KIND == TB_NW || KIND == TB_FIT, "one row per lane, SW-affine bytes");
+  // a global walk: from (m, n) -- TB_FIT: from the pair's end cell (m, end_j) -- to the matrix border
+  constexpr bool REF = KIND == TB_NW || KIND == TB_FIT;
   constexpr int GB = TBB_GB, GT = 16 * GB, GBYTES = 1024 * GB;
   __shared__ __attribute__((aligned(16))) uint8_t stage_raw[TBB_GUARD + TBB_WPB * GBYTES];
   __shared__ int csl[TBB_WPB][TBB_CSN];
@@ -83,14 +84,14 @@ __global__ __launch_bounds__(64 * TBB_WPB) void traceback_batch_kernel(
   const long long t_begin = (long long)__builtin_amdgcn_s_memtime();
   int i, j, status = 0, n_switch = 0, n_grp = 0, o = 0;
   bool walk = true;
-  if constexpr (REF) {
+  if constexpr (KIND == TB_NW) {
     i = pd.m;
     j = pd.n;
   } else {
     const PairResult r0 = res[pair];
     i = (int)r0.end_i;
     j = (int)r0.end_j;
-    walk = r0.score > 0;
+    walk = KIND == TB_FIT || r0.score > 0;  // (a fit alignment exists whatever its score)
     // (an end cell outside the matrix: the plan has not run)
     if (r0.end_i < 0 || r0.end_i > pd.m || r0.end_j < 0 || r0.end_j > pd.n) {
       status = MSA_ERR_ARG;

@@ -133,7 +133,9 @@ __device__ __forceinline__ int ref_end_state(const int32_t (&fin)[3], int end_ty
 
 // Walk kinds: Smith-Waterman affine; the reference's Gotoh walk over table numbers (REF
 // fill) or over tags (REF1 fill, tag = 4 - table); the global walk over SW-affine bytes (MSA_NW_ALIGN).
-enum { TB_SW = 0, TB_REF = 1, TB_REF_TAG = 2, TB_NW = 3 };
+// TB_FIT (MSA_NW_FIT plans): TB_NW's walk -- words, state machine, stop rule -- started at the run's end cell
+// (m, end_j) from the pair's PairResult instead of (m, n).
+enum { TB_SW = 0, TB_REF = 1, TB_REF_TAG = 2, TB_NW = 3, TB_FIT = 4 };
 
 // The transition word of a cell (see the window comment in traceback_kernel): three 10-bit
 // fields, field s (bits 10s..) = 10 x the next state (30 = stop) | the lane step of leaving
@@ -157,7 +159,7 @@ __device__ __forceinline__ unsigned tb_word(unsigned dv) {
     // table numbers x = 1..3 (0: no predecessor): next state 10 (x - 1), or 30
     auto fld = [](unsigned step, unsigned x) { return (x ? 10u * (x - 1u) : 30u) | (step << 6); };
     return fld(9u, dv & 3u) | (fld(1u, (dv >> 2) & 3u) << 10) | (fld(8u, (dv >> 4) & 3u) << 20) | (1u << 31);
-  } else {  // TB_SW, TB_NW
+  } else {  // TB_SW, TB_NW, TB_FIT
     const unsigned fH = (unsigned)(TB_FH >> (16 * (dv & 3u))) & 0x3ffu;
     const unsigned fE = (1u << 6) | ((dv & 4u) ? 0u : 10u);
     const unsigned fF = (8u << 6) | ((dv & 8u) ? 0u : 20u);
@@ -211,7 +213,8 @@ constexpr int TB_SPIN_MAX = 1 << 24;
 
 // KIND TB_SW: Smith-Waterman affine walk; TB_REF / TB_REF_TAG: the reference's Gotoh walk
 // (end_type, h: find_alignment's end rule); TB_NW: the SW words from (m, n) in state H to the matrix
-// border (low bits 0 -- no predecessor, never written by a complete fill -- end it with MSA_ERR_NOMATCH).  RL = rows per lane of the layout: 1, or 2 for the
+// border (low bits 0 -- no predecessor, never written by a complete fill -- end it with MSA_ERR_NOMATCH); TB_FIT:
+// TB_NW from the pair's end cell (m, end_j) (MSA_ERR_ARG for one outside the matrix).  RL = rows per lane of the layout: 1, or 2 for the
 // two-rows-per-lane Gotoh flow fill (128-row stripes, lane r holds rows 2r+1 and 2r+2 at column
 // cs + t - r; a 16-step block is 2 KiB: the row-1 segments, then the row-2 segments).
 //
@@ -489,11 +492,19 @@ __global__ __launch_bounds__(384) void traceback_kernel(const uint8_t* __restric
     // (a two-pass SW plan whose pass-2 blocks folded the result into the best-cell key: no PairResult)
     const PairResult r0 = (!REF && best_key) ? best_key_decode(*best_key, pd.n) : res[pair];
     // plans hold m, n < 2^26
-    i = REF ? pd.m : (int)r0.end_i;
-    j = REF ? pd.n : (int)r0.end_j;
+    constexpr bool FROM_RES = KIND == TB_SW || KIND == TB_FIT;  // the walk starts at the run's end cell
+    i = FROM_RES ? (int)r0.end_i : pd.m;
+    j = FROM_RES ? (int)r0.end_j : pd.n;
+    if constexpr (KIND == TB_FIT) {
+      // (an end cell outside the matrix: the plan has not run -- the batch walk's rule)
+      if (r0.end_i < 0 || r0.end_i > pd.m || r0.end_j < 0 || r0.end_j > pd.n) {
+        status = MSA_ERR_ARG;
+        i = j = 0;
+      }
+    }
     // SW: 0 in H, 1 in E (horizontal gap), 2 in F (vertical gap); REF: 0, 1, 2 = T1, T2, T3
     int st = 0;
-    if constexpr (REF && KIND != TB_NW) st = ref_end_state(r0.fin, end_type, hpen);
+    if constexpr (KIND == TB_REF || KIND == TB_REF_TAG) st = ref_end_state(r0.fin, end_type, hpen);
     int nw = 0, rseq = 0, eseq = 0;
     auto record = [&](unsigned w) __attribute__((always_inline)) {
       if ((nw & (TB_RAW / 2 - 1)) == 0 && nw >= TB_RAW) {

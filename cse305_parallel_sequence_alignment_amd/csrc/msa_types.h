@@ -22,6 +22,9 @@ enum msa_alg {
                      // direction bytes: the tagged-max form of MSA_ALG_REF (msa_kernels.hip)
   MSA_ALG_SWLP = 7,  // MSA_ALG_SWL0 for TWO pairs per lane as packed int16 (batch, score only:
                      // pairs 2c and 2c+1 share rows/columns counts and the column sequence)
+  MSA_ALG_FIT = 8,   // MSA_ALG_NWA's cell (no band) under a zero top border, H(0, j) = 0: all of A against a
+                     // substring of B (MSA_NW_FIT plans).  The lane of row m keeps the first maximum of
+                     // H(m, 1..n): the stripe meta's best / best_i = m / best_j
 };
 
 // Per-cell outputs.
@@ -47,10 +50,10 @@ typedef struct msa_pair_desc {
 typedef struct msa_stripe_meta {
   int32_t cs;          // column processed by lane 0 at step 0 (lane r: cs + t - r)
   int32_t phases;      // phases the stripe ran
-  int32_t best;        // SW: best H in the stripe (INT32_MIN if none)
-  int32_t best_i;      // SW: row of the best (first max, row-major)
-  int32_t best_j;      // SW: column of the best
-  int32_t fin[3];      // global: state at (m, n) if this stripe holds row m
+  int32_t best;        // SW: best H in the stripe (INT32_MIN if none); FIT, the stripe of row m: max H(m, 1..n)
+  int32_t best_i;      // SW: row of the best (first max, row-major); FIT: m
+  int32_t best_j;      // SW: column of the best; FIT: the smallest column attaining it
+  int32_t fin[3];      // global: state at (m, n) if this stripe holds row m (FIT too: not part of its result)
   int32_t has_fin;
   int32_t pad[3];
 } msa_stripe_meta;

@@ -51,8 +51,11 @@ class Plan:
 
     def __init__(self, alg: int, cells: int, ms, ns, a_offs, b_offs, match=1, mismatch=0, gap_open=1,
                  gap_extend=1, start_type=-1, band=-1, track_end=False, single=None, sub=None):
-        """``sub`` (NW_SCORED only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code a against column
-        code b (msa_plan_create_scored); None scores ``match`` on the diagonal and ``mismatch`` elsewhere."""
+        """``sub`` (NW_SCORED and NW_FIT only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code a against
+        column code b (msa_plan_create_scored); None scores ``match`` on the diagonal and ``mismatch`` elsewhere.
+        An NW_FIT plan (all of A against a substring of B: ``band`` -1, CELLS_DIR or CELLS_NONE) reports in
+        ``results()`` the score and ``end = (m, end_j)``, the first column of row m's maximum; ``traceback_nw`` and
+        ``traceback_batch`` walk from there."""
         L = LB.lib()
         self.alg, self.cells = alg, cells
         self.ms = [int(x) for x in ms]
@@ -283,9 +286,17 @@ class Plan:
         inf = info.cpu().tolist()
         LB.check(int(inf[3]), "msa_plan_traceback_nw")
         i, j = int(inf[1]) - 1, int(inf[2]) - 1
-        o = bytes(ops[:inf[0]].cpu().numpy().tobytes()) + (b"I" * i if i > 0 else b"D" * max(j, 0))
+        o = bytes(ops[:inf[0]].cpu().numpy().tobytes()) + self._border_gap(i, j)
         return dict(ops=o, stop=(i, j), cigar=cigar_of(o),
                     stats=dict(switches=int(inf[4]), on_demand=int(inf[5]), ticks=int(inf[6]), requests=int(inf[7])))
+
+    def _border_gap(self, i: int, j: int) -> bytes:
+        """The ops a global walk that stopped on the matrix border at (i, j) still lacks: i x 'I' or j x 'D'.  An
+        NW_FIT plan's alignment starts at reference column j for free: only the 'I' gap (the query overhangs the
+        reference's start) is appended, and ``stop[1]`` is where the aligned substring begins."""
+        if i > 0:
+            return b"I" * i
+        return b"" if self.alg == LB.NW_FIT else b"D" * max(j, 0)
 
     @staticmethod
     def ops_layout(ms, ns) -> list:
@@ -343,9 +354,9 @@ class Plan:
             LB.check(int(inf[k, 3]), "msa_plan_traceback_batch")
             o = oh[off[k]:off[k] + int(inf[k, 0])].tobytes()
             stats = dict(switches=int(inf[k, 4]), staged=int(inf[k, 5]), ticks=int(inf[k, 6]))
-            if self.alg in (LB.NW_ALIGN, LB.NW_SCORED):
+            if self.alg in (LB.NW_ALIGN, LB.NW_SCORED, LB.NW_FIT):
                 i, j = int(inf[k, 1]) - 1, int(inf[k, 2]) - 1
-                o += b"I" * i if i > 0 else b"D" * max(j, 0)
+                o += self._border_gap(i, j)
                 out.append(dict(ops=o, stop=(i, j), cigar=cigar_of(o), stats=stats))
             else:
                 out.append(dict(ops=o, beg=(int(inf[k, 1]), int(inf[k, 2])), cigar=cigar_of(o), stats=stats))

@@ -41,6 +41,11 @@
  *                        the walks of a whole batch plan in one launch, and batches of local / global
  *                        alignments with their CIGARs from host pointers (build extension: one wave per
  *                        walk over the bytes msa_plan_traceback / msa_plan_traceback_nw walk)
+ *   msa_fit_align, msa_fit_align_batch
+ *                        fit alignment: the whole query against the substring of the reference it fits
+ *                        best, with the reference span and the CIGAR (build extension: MSA_NW_FIT plans --
+ *                        a zero top border, the first maximum of row m found inside the fill kernel, and
+ *                        the two global walks started at that cell)
  */
 #ifndef MSA_H
 #define MSA_H
@@ -226,10 +231,13 @@ typedef enum msa_alg_e {
   MSA_PARTIAL = 4,    /* partial.cpp forward Gotoh, int32 wrap */
   MSA_NW_ALIGN = 5,   /* MSA_NW_BANDED's recurrence with one direction byte per cell (MSA_CELLS_DIR only,
                          match = 1, mismatch = 0; walked by msa_plan_traceback_nw) */
-  MSA_NW_SCORED = 6   /* MSA_NW_ALIGN's recurrence, band rule, borders, tie order and direction byte with
+  MSA_NW_SCORED = 6,  /* MSA_NW_ALIGN's recurrence, band rule, borders, tie order and direction byte with
                          f(i,j) = S[code of A_i][code of B_j]: S from match / mismatch, or an 8 x 8 table
                          (msa_plan_create_scored); MSA_CELLS_DIR (walked by msa_plan_traceback_nw /
                          msa_plan_traceback_batch) or MSA_CELLS_NONE (the score only) */
+  MSA_NW_FIT = 7      /* fit ("glocal", "semi-global", "infix") alignment: all of A against a substring of B that
+                         the alignment chooses, MSA_NW_SCORED's cells under a zero top border; the contract is
+                         at msa_fit_align below.  band = -1, MSA_CELLS_DIR or MSA_CELLS_NONE */
 } msa_alg_e;
 
 typedef enum msa_out_e { MSA_CELLS_NONE = 0, MSA_CELLS_H = 1, MSA_CELLS_DIR = 2, MSA_CELLS_TAB = 3 } msa_out_e;
@@ -254,8 +262,9 @@ typedef struct msa_plan_desc {
 typedef struct msa_pair_result {
   int32_t score;
   int32_t status;
-  int64_t end_i, end_j;  /* SW: end cell; Gotoh: (m, n) */
-  int32_t fin[3];        /* Gotoh: state at (m, n) (T1,T2,T3 / H,E,F) */
+  int64_t end_i, end_j;  /* SW: end cell; Gotoh: (m, n); MSA_NW_FIT: (m, first column of row m's maximum) */
+  int32_t fin[3];        /* Gotoh: state at (m, n) (T1,T2,T3 / H,E,F); MSA_NW_FIT: the same cell's (H,E,F), which
+                            is not part of that algorithm's result */
   int32_t pad;
 } msa_pair_result;
 
@@ -270,7 +279,9 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** plan);
  * range of the int32 cells: with s = the largest |score|, g = gap_extend, G = gap_open,
  *     (s + 2 G + 2 g) (m + n + 256) + (G - g) < 2^28
  * for every pair (the derivation is at check_ranges, msa_plan.inc); anything else is MSA_ERR_UNSUPPORTED.  The
- * band rule and its MSA_ERR_ARG are MSA_NW_ALIGN's. */
+ * band rule and its MSA_ERR_ARG are MSA_NW_ALIGN's.  MSA_NW_FIT takes a table (or NULL: match / mismatch) in the
+ * same way and under the same inequality (its zero top border is within the bound); it is MSA_ERR_UNSUPPORTED
+ * with any band but -1 and with cells other than MSA_CELLS_DIR / MSA_CELLS_NONE. */
 int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_plan** plan);
 void msa_plan_destroy(msa_plan* plan);
 /* Elements (int32 for H/TAB planes, bytes for DIR) the per-cell output needs. */
@@ -371,7 +382,10 @@ int msa_plan_traceback_gotoh(msa_plan* plan, int64_t pair, int end_type, const u
  * i+1, j+1, status, stripes entered, groups staged on demand, ticks, waits} with (i, j) the border
  * cell where the walk stopped and status 0 or MSA_ERR_CAPACITY.  Asynchronous, one walk per call
  * (msa_plan_traceback_batch walks every pair of a batch plan in one launch).  MSA_ERR_UNSUPPORTED for any plan that is not MSA_NW_ALIGN
- * or MSA_NW_SCORED with direction bytes; msa_plan_traceback and msa_plan_traceback_gotoh reject both. */
+ * or MSA_NW_SCORED with direction bytes; msa_plan_traceback and msa_plan_traceback_gotoh reject both.
+ * An MSA_NW_FIT plan with direction bytes is walked too: the same walk, started at the pair's end cell (m, end_j)
+ * from the run's result (an end cell outside the matrix -- the plan has not run -- is status MSA_ERR_ARG); the
+ * caller appends only the i x 'I' border gap, and the stop column j is where the aligned substring begins. */
 int msa_plan_traceback_nw(msa_plan* plan, int64_t pair, const uint8_t* dDir, uint8_t* d_ops, int64_t ops_cap,
                           int64_t* d_info, void* stream);
 /* Every pair's traceback ON THE DEVICE in ONE launch (msa_tbatch.hip), after msa_plan_run on the same
@@ -379,7 +393,8 @@ int msa_plan_traceback_nw(msa_plan* plan, int64_t pair, const uint8_t* dDir, uin
  * its own ops (the single walkers above spend a six-wave workgroup on one long walk and take a launch
  * per pair).  Plans: MSA_SW_AFFINE with MSA_CELLS_DIR and track_end (msa_plan_traceback's walk, from each
  * pair's end cell; no walk for a score <= 0) or MSA_NW_ALIGN / MSA_NW_SCORED (msa_plan_traceback_nw's walk, from (m, n) to
- * the matrix border; the caller appends the border gap), laid out one row per lane with the stripe starts
+ * the matrix border; the caller appends the border gap; MSA_NW_FIT: that walk from each pair's (m, end_j)), laid
+ * out one row per lane with the stripe starts
  * in the stripe meta: the stripe kernel's batch, split-batch and single launches and the band kernel's.
  * MSA_ERR_UNSUPPORTED, before any launch, for the flow kernels' plans (msa_plan_launch_info mode 1: the
  * single walkers serve them) and for every other algorithm / cells combination (MSA_REF_GOTOH included);
@@ -471,6 +486,45 @@ int msa_nw_align_batch_scored(const char* A, size_t a_len, const char* B, size_t
                               const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
                               int32_t gap_extend, int64_t band, int32_t* score, char* cigars, size_t cigar_cap,
                               int64_t* cigar_off);
+
+/* Fit alignment (build extension: MSA_NW_FIT plans; other tools say "glocal", "semi-global" or "infix"): ALL of
+ * the query A against a SUBSTRING of the reference B that the alignment chooses; reference symbols before and
+ * after the substring are free.  The contract:
+ *   Inputs: A (m >= 1) and B (n >= 1) as codes in [0, 8), all eight usable; a score table S as for
+ *   MSA_NW_SCORED (8 x 8 int8, or match / mismatch); g = gap_extend >= 0, h = gap_open - gap_extend >= 0, a gap of
+ *   length L costs h + g L.
+ *     H(0, j) = 0  for 0 <= j <= n        E(0, j) = F(0, j) = -inf
+ *     H(i, 0) = F(i, 0) = -h - g i        E(i, 0) = -inf                (1 <= i <= m: as the global plan)
+ *     E, F, H of interior cells, the direction byte and every tie rule: msa_plan_traceback_nw's text above
+ *     score = max over 1 <= j <= n of H(m, j);   end_j = the SMALLEST such j (the first maximum along row m)
+ *   Column 0 is left out of the maximum: F(m, 1) >= H(0, 1) - h - g m = H(m, 0), so H(m, 1) >= H(m, 0) and the
+ *   optimum over 1..n is the optimum over 0..n.
+ *   The walk is msa_plan_traceback_nw's, started at (m, end_j) in state H; it stops as soon as i == 0 or j == 0,
+ *   at the stop cell (i, j).  If i > 0 (the query overhangs the reference's start) the caller appends i x 'I'; no
+ *   'D' is ever appended, and beg_j = j.  The alignment consumes all m symbols of A and B[beg_j, end_j) (0-based,
+ *   half open); the CIGAR (start -> end, run-length M/I/D, I consumes A) consumes exactly m and end_j - beg_j.
+ *   beg_j == end_j is legal: the best alignment inserts the whole query.
+ *   A plan reports PairResult{score, status, end_i = m, end_j}; fin[] holds (H, E, F) at (m, n) as a global plan's
+ *   does and is not part of this algorithm's result.
+ *   Out of scope, each MSA_ERR_UNSUPPORTED at plan creation: any band other than -1 (|i - j| <= band means nothing
+ *   here), cells other than MSA_CELLS_DIR / MSA_CELLS_NONE, free ends on A.  Such plans always run the stripe
+ *   kernel (msa_plan_launch_info mode 0), one pair or a batch.
+ * msa_fit_align / msa_fit_align_batch behave as msa_nw_align_scored / msa_nw_align_batch_scored (alphabet, matrix
+ * and range errors; admission against the device budget, here with the full m x n bytes; chunks of consecutive
+ * pairs within a quarter of the budget, each one upload, one plan, one msa_plan_run, one msa_plan_traceback_batch
+ * and two downloads; a reference shared by every pair -- all b_off equal -- uploaded once; MSA_ERR_CAPACITY, the
+ * batch with the needed size in cigar_off[n_pairs]; argument errors decided on the host before any device call),
+ * without a band argument.  *score, *beg_j, *end_j (each may be NULL) / score (n_pairs), beg_end (2 n_pairs,
+ * {beg_j, end_j} per pair, required).  cigar(s) == NULL: scores and end_j from plans without direction bytes,
+ * beg_j = -1. */
+int msa_fit_align(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                  const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_j,
+                  int64_t* end_j, char* cigar, size_t cigar_cap);
+int msa_fit_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                        const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                        const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                        int32_t gap_extend, int32_t* score, int64_t* beg_end /* 2 n_pairs: {beg_j, end_j} */,
+                        char* cigars, size_t cigar_cap, int64_t* cigar_off);
 
 #ifdef __cplusplus
 }
