@@ -13,6 +13,7 @@
 #include <condition_variable>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <string>
 #include <thread>
 #include <deque>
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "../../include/msa.h"
+#include "msa_hostutil.h"
 #include "msa_kernels.hip"
 #include "msa_flow.hip"
 #include "msa_cflow.hip"
@@ -567,27 +569,10 @@ int msa_device_count(int* count) {
 }
 
 int msa_encode_pair(const char* A0, size_t m, const char* B0, size_t n, uint8_t* ca, uint8_t* cb) {
-  int map[256];
-  for (int k = 0; k < 256; ++k) map[k] = -1;
-  int next = 0;
-  auto enc = [&](const char* s, size_t len, uint8_t* out) -> int {
-    for (size_t k = 0; k < len; ++k) {
-      const unsigned char c = (unsigned char)s[k];
-      if (map[c] < 0) {
-        if (next >= 8) return MSA_ERR_ALPHABET;
-        map[c] = next++;
-      }
-      out[k] = (uint8_t)map[c];
-    }
-    return MSA_OK;
-  };
   // DNA fast path: fixed codes so batches share one code map
-  const char* dna = "ACGT";
-  for (int k = 0; k < 4; ++k) map[(unsigned char)dna[k]] = k;
-  next = 4;
-  int rc = enc(A0, m, ca);
-  if (rc != MSA_OK) return rc;
-  return enc(B0, n, cb);
+  msa_host::SymbolMap map(8, "ACGT");
+  const int rc = map.encode(A0, m, ca);
+  return rc != MSA_OK ? rc : map.encode(B0, n, cb);
 }
 
 void msa_plan_destroy(msa_plan* P) {

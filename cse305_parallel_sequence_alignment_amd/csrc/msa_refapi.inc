@@ -1,65 +1,30 @@
-// msa_refapi.inc -- reference-compatible host-pointer entry points of the
-// C-ABI (included by msa_capi.hip after the plan machinery).
+// msa_refapi.inc -- the host-pointer entry points of the C-ABI (included by msa_capi.hip after the plan
+// machinery): host arrays in, host arrays out, every DP cell and every walk on the GPU.
 //
-//   msa_main_alignment    main_alignment.cpp:353-410 (+ :11-22, :32-55)
-//   msa_subproblem        subproblem_alignment.h:36-74, .cpp:329-355, :105-172
-//   msa_partial_tables    partial.cpp:13-79
-//   msa_partial_partition partial.cpp:81-163
-//   msa_sw_align          build extension (Smith-Waterman, configs C2/C5)
-//   msa_nw_align          build extension (banded global alignment with its CIGAR, config C3's recurrence)
+//   the reference's API (line numbers: the reference's sources)
+//     msa_subproblem                  subproblem_alignment.h:36-74, .cpp:329-355, :105-172
+//     msa_main_alignment              main_alignment.cpp:353-410 (+ :11-22, :32-55)
+//     msa_optimal_alignment           main_alignment.cpp:158-351
+//     msa_main_alignment_partitioned  main_alignment.cpp:365,372 (the partition step it leaves commented out)
+//     msa_non_parallel_tables         subproblem_alignment.cpp:401-421
+//     msa_partial_tables              partial.cpp:13-79
+//     msa_partial_partition           partial.cpp:81-163
+//     msa_partition_tables            partial.cpp:128-145 over the caller's tables
+//   build extensions: an alignment with its CIGAR, one pair or a batch (align_pairs below)
+//     msa_sw_align, msa_sw_align_batch                  Smith-Waterman
+//     msa_nw_align, msa_nw_align_batch                  banded global alignment, +1 / 0
+//     msa_nw_align_scored, msa_nw_align_batch_scored    ... under match / mismatch scores or an 8 x 8 matrix
+//     msa_fit_align, msa_fit_align_batch                all of A in a substring of B
+//   (msa_rowapi.inc: msa_subproblem_f64, msa_subproblem_row)
 //
-// Every DP cell is computed on the GPU (stripe_kernel) and find_alignment's
-// walk runs there too (traceback_kernel<TB_REF_TAG>, or <TB_REF>): the host encodes the inputs,
-// turns the walk's O(m+n) ops into the reference's align nodes and prints.
+// The host encodes the inputs, runs plans (stripe_kernel and the flow / band kernels behind msa_plan_run) and the
+// device walks (traceback_kernel, msa_plan_traceback_batch), and turns a walk's O(m + n) ops into the reference's
+// align nodes or a CIGAR.
 
 namespace {
 
-// A pooled device block (dev_pool, msa_capi.hip); returned when the owner goes
-// out of scope, after the owner synchronized the stream that used it.
-struct DevMem {
-  void* p = nullptr;
-  size_t bytes = 0;
-  ~DevMem() { dev_pool().put(p, bytes); }
-  int alloc(size_t b) {
-    bytes = b ? b : 16;
-    p = dev_pool().get(bytes);
-    return p ? MSA_OK : MSA_ERR_NOMEM;
-  }
-};
+using namespace msa_host;  // msa_hostutil.h: SymbolMap, cigar_of, complete_border, SinglePairDesc, ops_offsets
 
-// A pooled non-blocking stream.  Destructors run in reverse declaration order,
-// so a StreamGuard declared before the DevMem/PlanGuard objects that use it is
-// destroyed AFTER them: on its own it would let their blocks return to the pool
-// while the stream may still be using them.  Every call that declares one must
-// therefore also declare a StreamSync (below) after its last DevMem/PlanGuard.
-struct StreamGuard {
-  hipStream_t s = nullptr;
-  int acquire() {
-    s = stream_pool().get();
-    return s ? MSA_OK : MSA_ERR_HIP;
-  }
-  ~StreamGuard() {
-    if (s) {
-      (void)hipStreamSynchronize(s);
-      stream_pool().put(s);
-    }
-  }
-};
-
-// Declared after every DevMem / PlanGuard of a call: destroyed first, it waits
-// for the call's stream on every exit path (errors included) before any of
-// their blocks return to the pool.
-struct StreamSync {
-  hipStream_t s;
-  ~StreamSync() {
-    if (s) (void)hipStreamSynchronize(s);
-  }
-};
-
-struct PlanGuard {
-  msa_plan* p = nullptr;
-  ~PlanGuard() { msa_plan_destroy(p); }
-};
 
 // Device footprint of one call, for admission control (Admit, msa_capi.hip), estimated from m and n
 // before anything is allocated.  A two-pass flow plan with direction bytes holds the 1 B/cell plane
@@ -122,7 +87,7 @@ struct CachedPlan {
       msa_plan_destroy(p);
       return;
     }
-    // the caller's stream has synchronized (StreamSync runs first): nothing of this plan is in
+    // the caller's stream has synchronized (~DeviceCall's body runs first): nothing of this plan is in
     // flight, so an eviction must not wait on streams other callers may be using by then
     p->streams.clear();
     msa_plan* evict = nullptr;
@@ -137,6 +102,104 @@ struct CachedPlan {
     }
     msa_plan_destroy(evict);
   }
+};
+
+// The device resources of one host-pointer call, constructed after ensure_device() succeeded: its reservation
+// against the device budget (Admit; a footprint of 0 reserves nothing), a pooled non-blocking stream, pooled
+// blocks, plans.  The one rule all of them are under: a block, or a plan with its blocks, goes back to its pool
+// only after the stream that used it has been waited on, on every exit path, errors included -- or another thread
+// is handed memory the stream still writes to.  The member order below is that rule.  The destructor's body
+// waits for the stream; then the members go in reverse order: the cached plan returns to the plan cache (when the
+// call marked success; it is destroyed otherwise), the plans are destroyed, the blocks and then the stream return
+// to their pools, and the reservation, which covered all of them, is released last.
+class DeviceCall {
+ public:
+  explicit DeviceCall(size_t footprint) {
+    if (footprint) adm_.emplace(footprint);  // waits until the call fits the device budget
+    stream_.s = stream_pool().get();
+  }
+  ~DeviceCall() {
+    if (stream_.s) (void)hipStreamSynchronize(stream_.s);
+  }
+  DeviceCall(const DeviceCall&) = delete;
+  DeviceCall& operator=(const DeviceCall&) = delete;
+
+  int status() const { return stream_.s ? MSA_OK : MSA_ERR_HIP; }
+  hipStream_t stream() const { return stream_.s; }
+  // a pooled block; nullptr: MSA_ERR_NOMEM
+  void* alloc(size_t bytes) {
+    if (blocks_.n == kMaxBlocks) return nullptr;
+    bytes = bytes ? bytes : 16;
+    void* p = dev_pool().get(bytes);
+    if (p) blocks_.v[blocks_.n++] = {p, bytes};
+    return p;
+  }
+  // (stream-ordered: the host side of a download holds its bytes after the next sync())
+  int upload(void* dst, const void* src, size_t bytes) {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream_.s));
+    return MSA_OK;
+  }
+  int download(void* dst, const void* src, size_t bytes) {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream_.s));
+    return MSA_OK;
+  }
+  int clear(void* dst, size_t bytes) {
+    HIPCHK(hipMemsetAsync(dst, 0, bytes, stream_.s));
+    return MSA_OK;
+  }
+  int sync() {
+    HIPCHK(hipStreamSynchronize(stream_.s));
+    return MSA_OK;
+  }
+  // a plan of this call's own (sub: msa_plan_create_scored's table, or nullptr), destroyed with the call
+  int create_plan(const msa_plan_desc& d, const int8_t* sub, msa_plan** out) {
+    if (plans_.n == kMaxPlans) return MSA_ERR_NOMEM;
+    const int rc = msa_plan_create_scored(&d, sub, out);
+    if (rc == MSA_OK) plans_.v[plans_.n++] = *out;
+    return rc;
+  }
+  // the idle plan of this shape from the plan cache, or a new one; it goes (back) to the cache if succeeded()
+  int cached_plan(const PlanKey& k, const msa_plan_desc& d, msa_plan** out) {
+    const int rc = cached_.acquire(k, d);
+    *out = cached_.p;
+    return rc;
+  }
+  void succeeded() { cached_.ok = true; }
+  // A device walk's ops (end -> start), once its info words {n_ops, i + 1, j + 1, status, ...} are on the host:
+  // the walk's status if it failed, else info[0] bytes of d_ops (waits for them).
+  int fetch_ops(const int64_t* info, const void* d_ops, std::vector<char>& ops) {
+    if (info[3] != 0) return (int)info[3];
+    ops.resize((size_t)info[0]);
+    if (info[0] == 0) return MSA_OK;
+    const int rc = download(ops.data(), d_ops, ops.size());
+    return rc != MSA_OK ? rc : sync();
+  }
+
+ private:
+  static constexpr int kMaxBlocks = 16, kMaxPlans = 2;
+  struct Stream {
+    hipStream_t s = nullptr;
+    ~Stream() { stream_pool().put(s); }
+  };
+  struct Blocks {
+    std::pair<void*, size_t> v[kMaxBlocks];
+    int n = 0;
+    ~Blocks() {
+      for (int k = n; k-- > 0;) dev_pool().put(v[k].first, v[k].second);
+    }
+  };
+  struct Plans {
+    msa_plan* v[kMaxPlans];
+    int n = 0;
+    ~Plans() {
+      for (int k = n; k-- > 0;) msa_plan_destroy(v[k]);
+    }
+  };
+  std::optional<Admit> adm_;
+  Stream stream_;
+  Blocks blocks_;
+  Plans plans_;
+  CachedPlan cached_;
 };
 
 // DevPool's out-of-memory path: destroy the current device's idle cached plans (their blocks return to
@@ -196,54 +259,39 @@ int run_one(int alg, int cells, const uint8_t* ca, int64_t m, const uint8_t* cb,
             int gap_open, int gap_ext, int start_type, int band, int track_end, OnePair& out) {
   int rc = ensure_device();
   if (rc != MSA_OK) return rc;
-  Admit adm(footprint_planes(m, n, (cells == MSA_CELLS_TAB) ? 3 : (cells == MSA_CELLS_NONE ? 0 : 1),
-                             (cells == MSA_CELLS_DIR) ? 1 : 4));
-  StreamGuard sg;
-  if ((rc = sg.acquire()) != MSA_OK) return rc;
-  DevMem dA, dB, c[3];
-  PlanGuard pg;
-  StreamSync sync{sg.s};
-  if ((rc = dA.alloc(m)) != MSA_OK || (rc = dB.alloc(n)) != MSA_OK) return rc;
-  HIPCHK(hipMemcpyAsync(dA.p, ca, m, hipMemcpyHostToDevice, sg.s));
-  HIPCHK(hipMemcpyAsync(dB.p, cb, n, hipMemcpyHostToDevice, sg.s));
-  int64_t zero = 0;
-  msa_plan_desc d;
-  std::memset(&d, 0, sizeof(d));
-  d.alg = alg;
-  d.cells = cells;
-  d.match = match;
-  d.mismatch = mismatch;
-  d.gap_open = gap_open;
-  d.gap_extend = gap_ext;
-  d.start_type = start_type;
-  d.band = band;
-  d.track_end = track_end;
-  d.single = 1;
-  d.n_pairs = 1;
-  d.m = &m;
-  d.n = &n;
-  d.a_off = &zero;
-  d.b_off = &zero;
-  if ((rc = msa_plan_create(&d, &pg.p)) != MSA_OK) return rc;
-  int64_t elems = 0;
-  msa_plan_cells_size(pg.p, &elems);
   const int nplanes = (cells == MSA_CELLS_TAB) ? 3 : (cells == MSA_CELLS_NONE ? 0 : 1);
   const size_t esz = (cells == MSA_CELLS_DIR) ? 1 : 4;
+  DeviceCall dc(footprint_planes(m, n, nplanes, (int)esz));
+  if ((rc = dc.status()) != MSA_OK) return rc;
+  void *dA = dc.alloc(m), *dB = dc.alloc(n), *c[3] = {nullptr, nullptr, nullptr};
+  if (!dA || !dB) return MSA_ERR_NOMEM;
+  if ((rc = dc.upload(dA, ca, m)) != MSA_OK || (rc = dc.upload(dB, cb, n)) != MSA_OK) return rc;
+  SinglePairDesc sd(alg, cells, m, n);
+  sd.d.match = match;
+  sd.d.mismatch = mismatch;
+  sd.d.gap_open = gap_open;
+  sd.d.gap_extend = gap_ext;
+  sd.d.start_type = start_type;
+  sd.d.band = band;
+  sd.d.track_end = track_end;
+  msa_plan* P = nullptr;
+  if ((rc = dc.create_plan(sd.d, nullptr, &P)) != MSA_OK) return rc;
+  int64_t elems = 0;
+  msa_plan_cells_size(P, &elems);
   for (int k = 0; k < nplanes; ++k)
-    if ((rc = c[k].alloc((size_t)elems * esz)) != MSA_OK) return rc;
-  if ((rc = msa_plan_run(pg.p, (const uint8_t*)dA.p, (const uint8_t*)dB.p, c[0].p, c[1].p, c[2].p, sg.s)) != MSA_OK)
+    if (!(c[k] = dc.alloc((size_t)elems * esz))) return MSA_ERR_NOMEM;
+  if ((rc = msa_plan_run(P, (const uint8_t*)dA, (const uint8_t*)dB, c[0], c[1], c[2], dc.stream())) != MSA_OK)
     return rc;
-  if ((rc = msa_plan_results(pg.p, &out.res, sg.s)) != MSA_OK) return rc;
-  out.S = msa_plan_stripes(pg.p);
+  if ((rc = msa_plan_results(P, &out.res, dc.stream())) != MSA_OK) return rc;
+  out.S = msa_plan_stripes(P);
   out.meta.resize((size_t)out.S * 12);
-  if ((rc = msa_plan_stripe_meta(pg.p, out.meta.data(), out.S, sg.s)) != MSA_OK) return rc;
-  out.pmax = pg.p->pairs[0].pmax;
+  if ((rc = msa_plan_stripe_meta(P, out.meta.data(), out.S, dc.stream())) != MSA_OK) return rc;
+  out.pmax = P->pairs[0].pmax;
   for (int k = 0; k < nplanes; ++k) {
     out.planes[k].resize((size_t)elems);
-    HIPCHK(hipMemcpyAsync(out.planes[k].data(), c[k].p, (size_t)elems * esz, hipMemcpyDeviceToHost, sg.s));
+    if ((rc = dc.download(out.planes[k].data(), c[k], (size_t)elems * esz)) != MSA_OK) return rc;
   }
-  HIPCHK(hipStreamSynchronize(sg.s));
-  return MSA_OK;
+  return dc.sync();
 }
 
 // One reference-Gotoh fill (subproblem_alignment.cpp:329-355) and its
@@ -257,53 +305,36 @@ int run_ref_walk(const uint8_t* ca, int64_t m, const uint8_t* cb, int64_t n, int
                  int start_type, int end_type, RefWalk& out) {
   int rc = ensure_device();
   if (rc != MSA_OK) return rc;
-  Admit adm(footprint_dir(m, n));  // waits until the call fits the device budget
-  StreamGuard sg;
-  if ((rc = sg.acquire()) != MSA_OK) return rc;
-  DevMem dA, dB, dDir, dOps, dInfo;
-  CachedPlan pg;
-  StreamSync sync{sg.s};
-  if ((rc = dA.alloc(m)) != MSA_OK || (rc = dB.alloc(n)) != MSA_OK) return rc;
-  HIPCHK(hipMemcpyAsync(dA.p, ca, m, hipMemcpyHostToDevice, sg.s));
-  HIPCHK(hipMemcpyAsync(dB.p, cb, n, hipMemcpyHostToDevice, sg.s));
-  int64_t zero = 0;
-  msa_plan_desc d;
-  std::memset(&d, 0, sizeof(d));
-  d.alg = MSA_REF_GOTOH;
-  d.cells = MSA_CELLS_DIR;
-  d.match = 1;
-  d.mismatch = 0;
-  d.gap_open = gap_open;
-  d.gap_extend = gap_ext;
-  d.start_type = start_type;
-  d.band = -1;
-  d.single = 1;
-  d.n_pairs = 1;
-  d.m = &m;
-  d.n = &n;
-  d.a_off = &zero;
-  d.b_off = &zero;
+  DeviceCall dc(footprint_dir(m, n));
+  if ((rc = dc.status()) != MSA_OK) return rc;
+  void *dA = dc.alloc(m), *dB = dc.alloc(n);
+  if (!dA || !dB) return MSA_ERR_NOMEM;
+  if ((rc = dc.upload(dA, ca, m)) != MSA_OK || (rc = dc.upload(dB, cb, n)) != MSA_OK) return rc;
+  SinglePairDesc sd(MSA_REF_GOTOH, MSA_CELLS_DIR, m, n);
+  sd.d.match = 1;
+  sd.d.mismatch = 0;
+  sd.d.gap_open = gap_open;
+  sd.d.gap_extend = gap_ext;
+  sd.d.start_type = start_type;
   int dev = 0;
   HIPCHK(hipGetDevice(&dev));
-  if ((rc = pg.acquire(PlanKey{dev, m, n, gap_open, gap_ext, start_type}, d)) != MSA_OK) return rc;
+  msa_plan* P = nullptr;
+  if ((rc = dc.cached_plan(PlanKey{dev, m, n, gap_open, gap_ext, start_type}, sd.d, &P)) != MSA_OK) return rc;
   int64_t elems = 0;
-  msa_plan_cells_size(pg.p, &elems);
+  msa_plan_cells_size(P, &elems);
   const int64_t cap = m + n + 2;
-  if ((rc = dDir.alloc((size_t)elems)) || (rc = dOps.alloc((size_t)cap)) || (rc = dInfo.alloc(64))) return rc;
-  if ((rc = msa_plan_run(pg.p, (const uint8_t*)dA.p, (const uint8_t*)dB.p, dDir.p, nullptr, nullptr, sg.s))) return rc;
-  if ((rc = msa_plan_traceback_gotoh(pg.p, 0, end_type, (const uint8_t*)dDir.p, (uint8_t*)dOps.p, cap,
-                                     (int64_t*)dInfo.p, sg.s)))
+  void *dDir, *dOps, *dInfo;
+  if (!(dDir = dc.alloc((size_t)elems)) || !(dOps = dc.alloc((size_t)cap)) || !(dInfo = dc.alloc(64)))
+    return MSA_ERR_NOMEM;
+  if ((rc = msa_plan_run(P, (const uint8_t*)dA, (const uint8_t*)dB, dDir, nullptr, nullptr, dc.stream()))) return rc;
+  if ((rc = msa_plan_traceback_gotoh(P, 0, end_type, (const uint8_t*)dDir, (uint8_t*)dOps, cap, (int64_t*)dInfo,
+                                     dc.stream())))
     return rc;
   int64_t info[8];
-  HIPCHK(hipMemcpyAsync(info, dInfo.p, sizeof(info), hipMemcpyDeviceToHost, sg.s));
-  if ((rc = msa_plan_results(pg.p, &out.res, sg.s)) != MSA_OK) return rc;  // (synchronizes the stream)
-  if (info[3] != 0) return (int)info[3];
-  out.ops.resize((size_t)info[0]);
-  if (info[0] > 0) {
-    HIPCHK(hipMemcpyAsync(out.ops.data(), dOps.p, (size_t)info[0], hipMemcpyDeviceToHost, sg.s));
-    HIPCHK(hipStreamSynchronize(sg.s));
-  }
-  pg.ok = true;
+  if ((rc = dc.download(info, dInfo, sizeof(info))) != MSA_OK) return rc;
+  if ((rc = msa_plan_results(P, &out.res, dc.stream())) != MSA_OK) return rc;  // (synchronizes the stream)
+  if ((rc = dc.fetch_ops(info, dOps, out.ops)) != MSA_OK) return rc;
+  dc.succeeded();
   return MSA_OK;
 }
 
@@ -1004,60 +1035,48 @@ int msa_partial_partition(const char* A0, const char* B0, size_t m_in, size_t n_
   if ((rc = msa_encode_pair(A0, m, B0, n, ca.data(), cb.data())) != MSA_OK) return rc;
   for (int64_t k = 0; k < m; ++k) ra[k] = ca[m - 1 - k];
   for (int64_t k = 0; k < n; ++k) rb[k] = cb[n - 1 - k];
-  Admit adm(2 * footprint_planes(m, n, 3, 4));  // forward + reverse tables
-  StreamGuard sg;
-  if ((rc = sg.acquire()) != MSA_OK) return rc;
-  DevMem dA, dB, dRA, dRB, F[3], R[3], keys;
-  PlanGuard pf, pr;
-  StreamSync sync{sg.s};
-  if ((rc = dA.alloc(m)) || (rc = dB.alloc(n)) || (rc = dRA.alloc(m)) || (rc = dRB.alloc(n))) return rc;
-  HIPCHK(hipMemcpyAsync(dA.p, ca.data(), m, hipMemcpyHostToDevice, sg.s));
-  HIPCHK(hipMemcpyAsync(dB.p, cb.data(), n, hipMemcpyHostToDevice, sg.s));
-  HIPCHK(hipMemcpyAsync(dRA.p, ra.data(), m, hipMemcpyHostToDevice, sg.s));
-  HIPCHK(hipMemcpyAsync(dRB.p, rb.data(), n, hipMemcpyHostToDevice, sg.s));
-  int64_t zero = 0, mm = m, nn = n;
-  msa_plan_desc d;
-  std::memset(&d, 0, sizeof(d));
-  d.alg = MSA_PARTIAL;
-  d.cells = MSA_CELLS_TAB;
-  d.match = 0;
-  d.mismatch = 1;
-  d.gap_open = GH;
-  d.gap_extend = G;
-  d.band = -1;
-  d.single = 1;
-  d.n_pairs = 1;
-  d.m = &mm;
-  d.n = &nn;
-  d.a_off = &zero;
-  d.b_off = &zero;
-  d.start_type = start_type;
-  if ((rc = msa_plan_create(&d, &pf.p)) != MSA_OK) return rc;
-  d.start_type = end_type;
-  if ((rc = msa_plan_create(&d, &pr.p)) != MSA_OK) return rc;
+  DeviceCall dc(2 * footprint_planes(m, n, 3, 4));  // forward + reverse tables
+  if ((rc = dc.status()) != MSA_OK) return rc;
+  void *dA, *dB, *dRA, *dRB, *F[3], *R[3];
+  if (!(dA = dc.alloc(m)) || !(dB = dc.alloc(n)) || !(dRA = dc.alloc(m)) || !(dRB = dc.alloc(n)))
+    return MSA_ERR_NOMEM;
+  if ((rc = dc.upload(dA, ca.data(), m)) || (rc = dc.upload(dB, cb.data(), n)) ||
+      (rc = dc.upload(dRA, ra.data(), m)) || (rc = dc.upload(dRB, rb.data(), n)))
+    return rc;
+  SinglePairDesc sd(MSA_PARTIAL, MSA_CELLS_TAB, m, n);
+  sd.d.match = 0;
+  sd.d.mismatch = 1;
+  sd.d.gap_open = GH;
+  sd.d.gap_extend = G;
+  msa_plan *pf = nullptr, *pr = nullptr;
+  sd.d.start_type = start_type;
+  if ((rc = dc.create_plan(sd.d, nullptr, &pf)) != MSA_OK) return rc;
+  sd.d.start_type = end_type;
+  if ((rc = dc.create_plan(sd.d, nullptr, &pr)) != MSA_OK) return rc;
   int64_t elems = 0;
-  msa_plan_cells_size(pf.p, &elems);
+  msa_plan_cells_size(pf, &elems);
   for (int v = 0; v < 3; ++v)
-    if ((rc = F[v].alloc((size_t)elems * 4)) || (rc = R[v].alloc((size_t)elems * 4))) return rc;
-  if ((rc = keys.alloc(sizeof(unsigned long long) * 2 * (p + 1)))) return rc;
-  HIPCHK(hipMemsetAsync(keys.p, 0, sizeof(unsigned long long) * 2 * (p + 1), sg.s));
-  if ((rc = msa_plan_run(pf.p, (const uint8_t*)dA.p, (const uint8_t*)dB.p, F[0].p, F[1].p, F[2].p, sg.s))) return rc;
-  if ((rc = msa_plan_run(pr.p, (const uint8_t*)dRA.p, (const uint8_t*)dRB.p, R[0].p, R[1].p, R[2].p, sg.s))) return rc;
+    if (!(F[v] = dc.alloc((size_t)elems * 4)) || !(R[v] = dc.alloc((size_t)elems * 4))) return MSA_ERR_NOMEM;
+  std::vector<unsigned long long> hk(2 * (p + 1));
+  const size_t key_bytes = sizeof(unsigned long long) * hk.size();
+  void* keys = dc.alloc(key_bytes);
+  if (!keys) return MSA_ERR_NOMEM;
+  if ((rc = dc.clear(keys, key_bytes)) != MSA_OK) return rc;
+  if ((rc = msa_plan_run(pf, (const uint8_t*)dA, (const uint8_t*)dB, F[0], F[1], F[2], dc.stream()))) return rc;
+  if ((rc = msa_plan_run(pr, (const uint8_t*)dRA, (const uint8_t*)dRB, R[0], R[1], R[2], dc.stream()))) return rc;
   if (p > 1) {
-    const PartSkew tabs{(const int32_t*)F[0].p, (const int32_t*)F[1].p, (const int32_t*)F[2].p,
-                        (const int32_t*)R[0].p, (const int32_t*)R[1].p, (const int32_t*)R[2].p,
-                        pf.p->d_pairs, pr.p->d_pairs, pf.p->d_meta, pr.p->d_meta};
-    hipLaunchKernelGGL(partition_kernel<PartSkew>, dim3(2048), dim3(256), 0, sg.s, tabs, (int)m, (int)n, (int)p, HH,
-                       (unsigned long long*)keys.p);
+    const PartSkew tabs{(const int32_t*)F[0], (const int32_t*)F[1], (const int32_t*)F[2],
+                        (const int32_t*)R[0], (const int32_t*)R[1], (const int32_t*)R[2],
+                        pf->d_pairs, pr->d_pairs, pf->d_meta, pr->d_meta};
+    hipLaunchKernelGGL(partition_kernel<PartSkew>, dim3(2048), dim3(256), 0, dc.stream(), tabs, (int)m, (int)n, (int)p,
+                       HH, (unsigned long long*)keys);
     HIPCHK(hipGetLastError());
   }
-  std::vector<unsigned long long> hk(2 * (p + 1));
-  HIPCHK(hipMemcpyAsync(hk.data(), keys.p, sizeof(unsigned long long) * hk.size(), hipMemcpyDeviceToHost, sg.s));
-  HIPCHK(hipStreamSynchronize(sg.s));
+  if ((rc = dc.download(hk.data(), keys, key_bytes)) != MSA_OK || (rc = dc.sync()) != MSA_OK) return rc;
   {
     int e1 = 0, e2 = 0;
-    HIPCHK(hipMemcpy(&e1, pf.p->d_err, sizeof(e1), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&e2, pr.p->d_err, sizeof(e2), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&e1, pf->d_err, sizeof(e1), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&e2, pr->d_err, sizeof(e2), hipMemcpyDeviceToHost));
     if (e1 || e2) return MSA_ERR_TIMEOUT;
   }
   return partition_from_keys(hk, m, n, p, out, cap, n_out);
@@ -1075,123 +1094,37 @@ int msa_partition_tables(const int32_t* T1, const int32_t* T2, const int32_t* T3
   std::vector<unsigned long long> hk(2 * (p + 1), 0ull);
   if (p > 1 && m > 0 && n > 0) {
     const size_t ef = (size_t)(m + 1) * (n + 1), er = (size_t)(m + 2) * (n + 2);
-    Admit adm(3 * 4 * (ef + er));
-    StreamGuard sg;
-    if ((rc = sg.acquire()) != MSA_OK) return rc;
-    StreamSync sync{sg.s};
-    DevMem F[3], R[3], keys;
+    DeviceCall dc(3 * 4 * (ef + er));
+    if ((rc = dc.status()) != MSA_OK) return rc;
+    void *F[3], *R[3];
     const int32_t* hf[3] = {T1, T2, T3};
     const int32_t* hr[3] = {R1, R2, R3};
     for (int v = 0; v < 3; ++v) {
-      if ((rc = F[v].alloc(4 * ef)) || (rc = R[v].alloc(4 * er))) return rc;
-      HIPCHK(hipMemcpyAsync(F[v].p, hf[v], 4 * ef, hipMemcpyHostToDevice, sg.s));
-      HIPCHK(hipMemcpyAsync(R[v].p, hr[v], 4 * er, hipMemcpyHostToDevice, sg.s));
+      if (!(F[v] = dc.alloc(4 * ef)) || !(R[v] = dc.alloc(4 * er))) return MSA_ERR_NOMEM;
+      if ((rc = dc.upload(F[v], hf[v], 4 * ef)) || (rc = dc.upload(R[v], hr[v], 4 * er))) return rc;
     }
-    if ((rc = keys.alloc(sizeof(unsigned long long) * hk.size()))) return rc;
-    HIPCHK(hipMemsetAsync(keys.p, 0, sizeof(unsigned long long) * hk.size(), sg.s));
-    const PartRowMajor tabs{(const int32_t*)F[0].p, (const int32_t*)F[1].p, (const int32_t*)F[2].p,
-                            (const int32_t*)R[0].p, (const int32_t*)R[1].p, (const int32_t*)R[2].p};
-    hipLaunchKernelGGL(partition_kernel<PartRowMajor>, dim3(2048), dim3(256), 0, sg.s, tabs, (int)m, (int)n, (int)p,
-                       HH, (unsigned long long*)keys.p);
+    const size_t key_bytes = sizeof(unsigned long long) * hk.size();
+    void* keys = dc.alloc(key_bytes);
+    if (!keys) return MSA_ERR_NOMEM;
+    if ((rc = dc.clear(keys, key_bytes)) != MSA_OK) return rc;
+    const PartRowMajor tabs{(const int32_t*)F[0], (const int32_t*)F[1], (const int32_t*)F[2],
+                            (const int32_t*)R[0], (const int32_t*)R[1], (const int32_t*)R[2]};
+    hipLaunchKernelGGL(partition_kernel<PartRowMajor>, dim3(2048), dim3(256), 0, dc.stream(), tabs, (int)m, (int)n,
+                       (int)p, HH, (unsigned long long*)keys);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hk.data(), keys.p, sizeof(unsigned long long) * hk.size(), hipMemcpyDeviceToHost, sg.s));
-    HIPCHK(hipStreamSynchronize(sg.s));
+    if ((rc = dc.download(hk.data(), keys, key_bytes)) != MSA_OK || (rc = dc.sync()) != MSA_OK) return rc;
   }
   return partition_from_keys(hk, m, n, p, out, cap, n_out);
 }
 
-int msa_sw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t match, int32_t mismatch,
-                 int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_i, int64_t* end_j,
-                 int64_t* beg_i, int64_t* beg_j, char* cigar, size_t cigar_cap) {
-  if (!A0 || !B0 || m == 0 || n == 0) return MSA_ERR_ARG;
-  if (match < -128 || match > 127 || mismatch < -128 || mismatch > 127 || gap_open < 0 || gap_extend < 0)
-    return MSA_ERR_UNSUPPORTED;
-  std::vector<uint8_t> ca(m), cb(n);
-  int rc = msa_encode_pair(A0, m, B0, n, ca.data(), cb.data());
-  if (rc != MSA_OK) return rc;
-  // code 7 is the SW kernels' out-of-matrix sentinel: at most 7 distinct symbols
-  for (uint8_t c : ca) if (c >= 7) return MSA_ERR_ALPHABET;
-  for (uint8_t c : cb) if (c >= 7) return MSA_ERR_ALPHABET;
-  const bool want_tb = cigar || beg_i || beg_j;
-  if ((rc = ensure_device()) != MSA_OK) return rc;
-  Admit adm(want_tb ? footprint_dir((int64_t)m, (int64_t)n) : footprint_planes((int64_t)m, (int64_t)n, 0, 1));
-  StreamGuard sg;
-  if ((rc = sg.acquire()) != MSA_OK) return rc;
-  DevMem dA, dB, dDir, dOps, dInfo;
-  PlanGuard pg;
-  StreamSync sync{sg.s};
-  if ((rc = dA.alloc(m)) || (rc = dB.alloc(n))) return rc;
-  HIPCHK(hipMemcpyAsync(dA.p, ca.data(), m, hipMemcpyHostToDevice, sg.s));
-  HIPCHK(hipMemcpyAsync(dB.p, cb.data(), n, hipMemcpyHostToDevice, sg.s));
-  int64_t zero = 0, mm = (int64_t)m, nn = (int64_t)n;
-  msa_plan_desc d;
-  std::memset(&d, 0, sizeof(d));
-  d.alg = MSA_SW_AFFINE;
-  d.cells = want_tb ? MSA_CELLS_DIR : MSA_CELLS_NONE;
-  d.match = match;
-  d.mismatch = mismatch;
-  d.gap_open = gap_open;
-  d.gap_extend = gap_extend;
-  d.band = -1;
-  d.track_end = 1;
-  d.single = 1;
-  d.n_pairs = 1;
-  d.m = &mm;
-  d.n = &nn;
-  d.a_off = &zero;
-  d.b_off = &zero;
-  if ((rc = msa_plan_create(&d, &pg.p)) != MSA_OK) return rc;
-  const int64_t ops_cap = (int64_t)(m + n + 2);
-  if (want_tb) {
-    int64_t elems = 0;
-    msa_plan_cells_size(pg.p, &elems);
-    if ((rc = dDir.alloc((size_t)elems)) || (rc = dOps.alloc((size_t)ops_cap)) || (rc = dInfo.alloc(64))) return rc;
-  }
-  if ((rc = msa_plan_run(pg.p, (const uint8_t*)dA.p, (const uint8_t*)dB.p, dDir.p, nullptr, nullptr, sg.s)))
-    return rc;
-  // traceback on the device (msa_traceback.hip): only the ops come back, not the m*n bytes
-  if (want_tb &&
-      (rc = msa_plan_traceback(pg.p, 0, (const uint8_t*)dDir.p, (uint8_t*)dOps.p, ops_cap, (int64_t*)dInfo.p, sg.s)))
-    return rc;
-  msa_pair_result res;
-  if ((rc = msa_plan_results(pg.p, &res, sg.s)) != MSA_OK) return rc;
-  if (score) *score = res.score;
-  if (end_i) *end_i = res.end_i;
-  if (end_j) *end_j = res.end_j;
-  if (!want_tb) return MSA_OK;
-  int64_t info[4];
-  HIPCHK(hipMemcpyAsync(info, dInfo.p, sizeof(info), hipMemcpyDeviceToHost, sg.s));
-  HIPCHK(hipStreamSynchronize(sg.s));
-  if (info[3] != 0) return (int)info[3];
-  std::vector<char> ops((size_t)info[0]);
-  if (info[0] > 0) {
-    HIPCHK(hipMemcpyAsync(ops.data(), dOps.p, (size_t)info[0], hipMemcpyDeviceToHost, sg.s));
-    HIPCHK(hipStreamSynchronize(sg.s));
-  }
-  if (beg_i) *beg_i = info[1];
-  if (beg_j) *beg_j = info[2];
-  if (cigar) {
-    // ops run from the end cell back to the start: run-length encode them reversed
-    std::string c;
-    for (int64_t k = (int64_t)ops.size() - 1; k >= 0;) {
-      const char op = ops[(size_t)k];
-      int64_t run = 0;
-      while (k >= 0 && ops[(size_t)k] == op) { run++; k--; }
-      c += std::to_string(run);
-      c.push_back(op);
-    }
-    if (c.size() + 1 > cigar_cap) return MSA_ERR_CAPACITY;
-    std::memcpy(cigar, c.c_str(), c.size() + 1);
-  }
-  return MSA_OK;
-}
-
 }  // extern "C"
 
+// ---- alignments with their CIGARs: one pair (msa_*_align) or a batch (msa_*_align_batch) ----------------------
 namespace {
 
-// Device footprint of one msa_nw_align call: the plan's cells (1 B per cell of the skewed band layout -- the
-// stripes' own phase counts, as lay_out_pairs sizes them -- or none for a score-only call), its granule slots (two
+// Device footprint of one global alignment (footprint_dir / footprint_planes above are a local one's): the plan's
+// cells (1 B per cell of the skewed band layout -- the stripes' own phase counts, as lay_out_pairs sizes them -- or
+// none for a score-only call), its granule slots (two
 // per item of 4 stripes, n + margins granules each; a chunked band plan has up to (warm-up + chunk) / 4 + 1 items
 // per chunk), the 16 code copies, the ops and the pooled size classes' slack.  A banded pair therefore reserves
 // ~(2 band + 64) B per row, not the full matrix.
@@ -1213,128 +1146,260 @@ size_t footprint_nw(int64_t m, int64_t n, int band, bool dir) {
          3 * (size_t)(m + n) + (size_t(24) << 20);
 }
 
-// The scoring of a scored global alignment entry (msa_nw_align_scored, msa_nw_align_batch_scored): the caller's
-// alphabet as a symbol -> code map (a symbol's code is its index) and its n_sym x n_sym matrix as the plan's 8 x 8
-// table.  The unscored entries pass no NwScoring: +1 / 0 over a symbol map of the call's own.
-struct NwScoring {
-  int map[256];
+// What a kind of alignment is, as data: everything in which the entries below differ.
+enum GapRule { GAPS_LOCAL, GAPS_GLOBAL };  // gap costs >= 0 and scores in int8 | 0 <= gap_extend <= gap_open
+enum Footprint { FOOT_MATRIX, FOOT_BAND };  // footprint_dir / footprint_planes | footprint_nw
+struct AlignSpec {
+  int status;               // MSA_ERR_ARG: the caller's alphabet or matrix is no scoring
+  int alg_walk, alg_score;  // the plan with direction bytes, and the value plan of the same recurrence without
+  int match, mismatch, start_type, track_end;  // the plan description's
+  bool scored;              // tab is msa_plan_create_scored's 8 x 8 table (else match / mismatch score)
   int8_t tab[64];
-  // MSA_ERR_ARG for a NULL alphabet or matrix, n_sym outside 1..8 or a duplicate symbol
-  int set(const char* alphabet, size_t n_sym, const int8_t* sub) {
-    if (!alphabet || !sub || n_sym < 1 || n_sym > 8) return MSA_ERR_ARG;
-    std::fill(map, map + 256, -1);
-    std::fill(tab, tab + 64, (int8_t)0);
-    for (size_t a = 0; a < n_sym; ++a) {
-      int& code = map[(unsigned char)alphabet[a]];
-      if (code >= 0) return MSA_ERR_ARG;
-      code = (int)a;
-      for (size_t b = 0; b < n_sym; ++b) tab[8 * a + b] = sub[n_sym * a + b];
-    }
-    return MSA_OK;
-  }
-  // MSA_ERR_ALPHABET for a symbol outside the alphabet
-  int encode(const char* s, size_t len, uint8_t* out) const {
-    for (size_t k = 0; k < len; ++k) {
-      const int code = map[(unsigned char)s[k]];
-      if (code < 0) return MSA_ERR_ALPHABET;
-      out[k] = (uint8_t)code;
-    }
-    return MSA_OK;
-  }
+  SymbolMap symbols;        // first-seen with the kind's code limit, or the caller's alphabet as a fixed map
+  GapRule gaps;
+  bool banded;              // a band is accepted
+  Footprint footprint;
+  // the walk of a single-pair plan: msa_plan_traceback or msa_plan_traceback_nw
+  int (*walk)(msa_plan*, int64_t, const uint8_t*, uint8_t*, int64_t, int64_t*, void*);
+  Border border;            // how the walk's ops become the whole alignment
+  bool walk_for_beg;        // the walk is wanted for the start cell too, not only for a CIGAR
 };
 
-// msa_nw_align (sc == nullptr), msa_nw_align_scored and msa_fit_align (fit_be != nullptr: an MSA_NW_FIT plan, no
-// band, the walk from (m, end_j); fit_be = {beg_j, end_j}, beg_j = -1 without a walk)
-int nw_align_one(const char* A0, size_t m, const char* B0, size_t n, const NwScoring* sc, int32_t gap_open,
-                 int32_t gap_extend, int64_t band_in, int32_t* score, char* cigar, size_t cigar_cap,
-                 int64_t* fit_be = nullptr) {
-  if (!A0 || !B0 || m == 0 || n == 0 || m > (size_t(1) << 26) || n > (size_t(1) << 26) || band_in < -1)
-    return MSA_ERR_ARG;
-  if (gap_extend < 0 || gap_open < gap_extend) return MSA_ERR_UNSUPPORTED;
-  const int64_t mm = (int64_t)m, nn = (int64_t)n;
-  if (band_in >= 0 && std::llabs(mm - nn) > band_in) return MSA_ERR_ARG;
-  // (a band that holds every cell is no band)
-  const int band = (band_in < 0 || band_in >= std::max(mm, nn)) ? -1 : (int)band_in;
-  std::vector<uint8_t> ca(m), cb(n);
-  int rc = sc ? sc->encode(A0, m, ca.data()) : msa_encode_pair(A0, m, B0, n, ca.data(), cb.data());
-  if (rc == MSA_OK && sc) rc = sc->encode(B0, n, cb.data());
-  if (rc != MSA_OK) return rc;
-  const bool want_tb = cigar != nullptr;
-  if ((rc = ensure_device()) != MSA_OK) return rc;
-  Admit adm(footprint_nw(mm, nn, band, want_tb));
-  StreamGuard sg;
-  if ((rc = sg.acquire()) != MSA_OK) return rc;
-  DevMem dA, dB, dDir, dOps, dInfo;
-  PlanGuard pg;
-  StreamSync sync{sg.s};
-  if ((rc = dA.alloc(m)) || (rc = dB.alloc(n))) return rc;
-  HIPCHK(hipMemcpyAsync(dA.p, ca.data(), m, hipMemcpyHostToDevice, sg.s));
-  HIPCHK(hipMemcpyAsync(dB.p, cb.data(), n, hipMemcpyHostToDevice, sg.s));
-  int64_t zero = 0;
+// Smith-Waterman: code 7 is the kernels' out-of-matrix sentinel, so 7 codes
+AlignSpec spec_sw(int match, int mismatch, const char* preset) {
+  return AlignSpec{MSA_OK, MSA_SW_AFFINE, MSA_SW_AFFINE, match, mismatch, 0, 1, false, {}, SymbolMap(7, preset),
+                   GAPS_LOCAL, false, FOOT_MATRIX, msa_plan_traceback, BORDER_NONE, true};
+}
+// global, +1 / 0 over the call's own symbols
+AlignSpec spec_nw(const char* preset) {
+  return AlignSpec{MSA_OK, MSA_NW_ALIGN, MSA_NW_BANDED, 1, 0, -1, 0, false, {}, SymbolMap(8, preset),
+                   GAPS_GLOBAL, true, FOOT_BAND, msa_plan_traceback_nw, BORDER_GLOBAL, false};
+}
+// global under the caller's alphabet -- a symbol's code is its index -- and its n_sym x n_sym matrix;
+// status MSA_ERR_ARG for a NULL alphabet or matrix, n_sym outside 1..8 or a duplicate symbol
+AlignSpec spec_scored(const char* alphabet, size_t n_sym, const int8_t* sub) {
+  AlignSpec s = spec_nw("");
+  s.alg_walk = s.alg_score = MSA_NW_SCORED;
+  s.scored = true;
+  if (!alphabet || !sub || n_sym < 1 || n_sym > 8) s.status = MSA_ERR_ARG;
+  for (size_t a = 0; s.status == MSA_OK && a < n_sym; ++a) {
+    if (!s.symbols.add(alphabet[a])) s.status = MSA_ERR_ARG;
+    for (size_t b = 0; b < n_sym; ++b) s.tab[8 * a + b] = sub[n_sym * a + b];
+  }
+  s.symbols.fix();
+  return s;
+}
+// ... and with free ends on B: all of A in a substring of B
+AlignSpec spec_fit(const char* alphabet, size_t n_sym, const int8_t* sub) {
+  AlignSpec s = spec_scored(alphabet, n_sym, sub);
+  s.alg_walk = s.alg_score = MSA_NW_FIT;
+  s.banded = false;
+  s.border = BORDER_FIT;
+  return s;
+}
+
+// The pairs of a call: pair p is A[a_off[p] .. + m[p]) against B[b_off[p] .. + n[p]).
+struct AlignIn {
+  const char *A, *B;
+  size_t a_len, b_len;
+  int64_t np;
+  const int64_t *a_off, *m, *b_off, *n;
+};
+// ... of a single entry: one pair, the whole of A0 against the whole of B0 (owns what `in` points to)
+struct OnePairIn {
+  int64_t m, n, zero = 0;
+  AlignIn in;
+  OnePairIn(const char* A0, size_t m_, const char* B0, size_t n_)
+      : m((int64_t)m_), n((int64_t)n_), in{A0, B0, m_, n_, 1, &zero, &m, &zero, &n} {}
+  OnePairIn(const OnePairIn&) = delete;
+};
+// Where a pair's two coordinates go: [2 p] and [2 p + 1] of a batch entry's array, a single entry's two pointers
+// (p = 0), or nowhere.
+struct PairOut {
+  int64_t *i = nullptr, *j = nullptr;
+  PairOut() = default;
+  PairOut(int64_t* i_, int64_t* j_) : i(i_), j(j_) {}
+  explicit PairOut(int64_t* ij) : i(ij), j(ij ? ij + 1 : nullptr) {}
+  void put(int64_t p, int64_t vi, int64_t vj) const {
+    if (i) i[2 * p] = vi;
+    if (j) j[2 * p] = vj;
+  }
+};
+struct AlignOut {
+  int32_t* score;
+  PairOut end, beg;  // local: the end cell, the start cell
+  PairOut span;      // fit: {beg_j, end_j}, beg_j = -1 without a walk
+  char* cigars;      // the CIGARs back to back, each with its NUL; cigar_off[np + 1]
+  size_t cigar_cap;
+  int64_t* cigar_off;
+};
+struct GapBand {
+  int32_t gap_open, gap_extend;
+  int band;
+};
+
+// Pairs [p0, p1) of a call as one plan on one stream: admit `bytes`, upload the range's code spans (pairs' offsets
+// relative to them: coinciding ranges are sent once), create the plan, run it, walk it, fetch the results, each
+// walk's info and ops, complete the ops along the border and append the CIGARs to `all`.  single = 1: a plan for
+// one pair spread over many workgroups (the flow / band kernels where they apply), walked by the single walker;
+// 0: a batch plan, one workgroup per pair, every pair walked in one msa_plan_traceback_batch launch.
+int align_range(const AlignSpec& spec, int single, const GapBand& gb, bool want_tb, const uint8_t* ca,
+                const uint8_t* cb, const AlignIn& in, int64_t p0, int64_t p1, size_t bytes, const AlignOut& out,
+                std::string& all) {
+  const int64_t K = p1 - p0;
+  int64_t a_lo = INT64_MAX, a_hi = 0, b_lo = INT64_MAX, b_hi = 0;
+  for (int64_t p = p0; p < p1; ++p) {
+    a_lo = std::min(a_lo, in.a_off[p]);
+    a_hi = std::max(a_hi, in.a_off[p] + in.m[p]);
+    b_lo = std::min(b_lo, in.b_off[p]);
+    b_hi = std::max(b_hi, in.b_off[p] + in.n[p]);
+  }
+  std::vector<int64_t> ao((size_t)K), bo((size_t)K);
+  for (int64_t k = 0; k < K; ++k) {
+    ao[(size_t)k] = in.a_off[p0 + k] - a_lo;
+    bo[(size_t)k] = in.b_off[p0 + k] - b_lo;
+  }
+  const std::vector<int64_t> off = ops_offsets(in.m + p0, in.n + p0, K);
+  const int64_t ops_cap = single ? in.m[p0] + in.n[p0] + 2 : off[(size_t)K];
+  int rc;
+  DeviceCall dc(bytes);
+  if ((rc = dc.status()) != MSA_OK) return rc;
+  void *dA = dc.alloc((size_t)(a_hi - a_lo)), *dB = dc.alloc((size_t)(b_hi - b_lo));
+  if (!dA || !dB) return MSA_ERR_NOMEM;
+  if ((rc = dc.upload(dA, ca + a_lo, (size_t)(a_hi - a_lo))) || (rc = dc.upload(dB, cb + b_lo, (size_t)(b_hi - b_lo))))
+    return rc;
   msa_plan_desc d;
   std::memset(&d, 0, sizeof(d));
-  // the score alone needs no direction bytes: the value plan of the same recurrence (a scored plan has both)
-  d.alg = fit_be ? MSA_NW_FIT : sc ? MSA_NW_SCORED : (want_tb ? MSA_NW_ALIGN : MSA_NW_BANDED);
+  d.alg = want_tb ? spec.alg_walk : spec.alg_score;
   d.cells = want_tb ? MSA_CELLS_DIR : MSA_CELLS_NONE;
-  d.match = 1;
-  d.mismatch = 0;
-  d.gap_open = gap_open;
-  d.gap_extend = gap_extend;
-  d.start_type = -1;
-  d.band = band;
-  d.single = 1;
-  d.n_pairs = 1;
-  d.m = &mm;
-  d.n = &nn;
-  d.a_off = &zero;
-  d.b_off = &zero;
-  if ((rc = msa_plan_create_scored(&d, sc ? sc->tab : nullptr, &pg.p)) != MSA_OK) return rc;
-  const int64_t ops_cap = mm + nn + 2;
+  d.match = spec.match;
+  d.mismatch = spec.mismatch;
+  d.gap_open = gb.gap_open;
+  d.gap_extend = gb.gap_extend;
+  d.start_type = spec.start_type;
+  d.band = gb.band;
+  d.track_end = spec.track_end;
+  d.single = single;
+  d.n_pairs = K;
+  d.m = in.m + p0;
+  d.n = in.n + p0;
+  d.a_off = ao.data();
+  d.b_off = bo.data();
+  msa_plan* P = nullptr;
+  if ((rc = dc.create_plan(d, spec.scored ? spec.tab : nullptr, &P)) != MSA_OK) return rc;
+  void *dDir = nullptr, *dOps = nullptr, *dOff = nullptr, *dInfo = nullptr;
+  const hipStream_t st = dc.stream();
   if (want_tb) {
     int64_t elems = 0;
-    msa_plan_cells_size(pg.p, &elems);
-    if ((rc = dDir.alloc((size_t)elems)) || (rc = dOps.alloc((size_t)ops_cap)) || (rc = dInfo.alloc(64))) return rc;
+    msa_plan_cells_size(P, &elems);
+    if (!(dDir = dc.alloc((size_t)elems)) || !(dOps = dc.alloc((size_t)ops_cap)) ||
+        (!single && !(dOff = dc.alloc(sizeof(int64_t) * (size_t)(K + 1)))) || !(dInfo = dc.alloc(64 * (size_t)K)))
+      return MSA_ERR_NOMEM;
+    if (!single && (rc = dc.upload(dOff, off.data(), sizeof(int64_t) * (size_t)(K + 1)))) return rc;
   }
-  if ((rc = msa_plan_run(pg.p, (const uint8_t*)dA.p, (const uint8_t*)dB.p, dDir.p, nullptr, nullptr, sg.s)))
-    return rc;
-  // the walk on the device: only the ops come back, not the band's bytes
-  if (want_tb &&
-      (rc = msa_plan_traceback_nw(pg.p, 0, (const uint8_t*)dDir.p, (uint8_t*)dOps.p, ops_cap, (int64_t*)dInfo.p, sg.s)))
-    return rc;
-  msa_pair_result res;
-  if ((rc = msa_plan_results(pg.p, &res, sg.s)) != MSA_OK) return rc;
-  if (score) *score = res.score;
-  if (fit_be) {
-    fit_be[0] = -1;
-    fit_be[1] = res.end_j;
+  if ((rc = msa_plan_run(P, (const uint8_t*)dA, (const uint8_t*)dB, dDir, nullptr, nullptr, st))) return rc;
+  // the walks on the device: only the ops come back, not the direction bytes
+  if (want_tb) {
+    if (!single)
+      rc = msa_plan_traceback_batch(P, (const uint8_t*)dDir, (uint8_t*)dOps, (const int64_t*)dOff, (int64_t*)dInfo, st);
+    else
+      rc = spec.walk(P, 0, (const uint8_t*)dDir, (uint8_t*)dOps, ops_cap, (int64_t*)dInfo, st);
+    if (rc != MSA_OK) return rc;
+  }
+  std::vector<msa_pair_result> res((size_t)K);
+  if ((rc = msa_plan_results(P, res.data(), st)) != MSA_OK) return rc;
+  // (the scores, end cells and span ends are the caller's whatever becomes of the walks)
+  for (int64_t k = 0; k < K; ++k) {
+    if (out.score) out.score[p0 + k] = res[(size_t)k].score;
+    out.end.put(p0 + k, res[(size_t)k].end_i, res[(size_t)k].end_j);
+    out.span.put(p0 + k, -1, res[(size_t)k].end_j);
   }
   if (!want_tb) return MSA_OK;
-  int64_t info[4];
-  HIPCHK(hipMemcpyAsync(info, dInfo.p, sizeof(info), hipMemcpyDeviceToHost, sg.s));
-  HIPCHK(hipStreamSynchronize(sg.s));
-  if (info[3] != 0) return (int)info[3];
-  std::vector<char> ops((size_t)info[0]);
-  if (info[0] > 0) {
-    HIPCHK(hipMemcpyAsync(ops.data(), dOps.p, (size_t)info[0], hipMemcpyDeviceToHost, sg.s));
-    HIPCHK(hipStreamSynchronize(sg.s));
+  std::vector<int64_t> info(8 * (size_t)K);
+  std::vector<char> ops;
+  if (single) {  // four info words, then as many ops as the walk made
+    if ((rc = dc.download(info.data(), dInfo, 4 * sizeof(int64_t))) || (rc = dc.sync()) ||
+        (rc = dc.fetch_ops(info.data(), dOps, ops)))
+      return rc;
+  } else {
+    ops.resize((size_t)off[(size_t)K]);
+    if ((rc = dc.download(info.data(), dInfo, 64 * (size_t)K)) || (rc = dc.download(ops.data(), dOps, ops.size())) ||
+        (rc = dc.sync()))
+      return rc;
   }
-  // the walk stopped on the matrix border at (i, j): the rest is one gap along it
-  // (a fit alignment: the reference's symbols before column j are free -- no 'D'; the aligned substring starts there)
-  const int64_t bi = info[1] - 1, bj = info[2] - 1;
-  if (bi > 0) ops.insert(ops.end(), (size_t)bi, 'I');
-  else if (bj > 0 && !fit_be) ops.insert(ops.end(), (size_t)bj, 'D');
-  if (fit_be) fit_be[0] = bj;
-  // ops run from (m, n) back to (0, 0): run-length encode them reversed
-  std::string c;
-  for (int64_t k = (int64_t)ops.size() - 1; k >= 0;) {
-    const char op = ops[(size_t)k];
-    int64_t run = 0;
-    while (k >= 0 && ops[(size_t)k] == op) { run++; k--; }
-    c += std::to_string(run);
-    c.push_back(op);
+  for (int64_t k = 0; k < K; ++k) {
+    const int64_t* inf = &info[8 * (size_t)k];
+    if (inf[3] != 0) return (int)inf[3];  // (a batch: the first failing pair's walk status)
+    std::string o(ops.data() + off[(size_t)k], (size_t)inf[0]);
+    const int64_t beg_j = complete_border(o, inf[1] - 1, inf[2] - 1, spec.border);
+    if (spec.border == BORDER_FIT) out.span.put(p0 + k, beg_j, res[(size_t)k].end_j);
+    if (spec.walk_for_beg) out.beg.put(p0 + k, inf[1], inf[2]);
+    if (out.cigars) {
+      out.cigar_off[p0 + k] = (int64_t)all.size();
+      all += cigar_of(o.data(), o.size());
+      all.push_back('\0');
+    }
   }
-  if (c.size() + 1 > cigar_cap) return MSA_ERR_CAPACITY;
-  std::memcpy(cigar, c.c_str(), c.size() + 1);
+  return MSA_OK;
+}
+
+const int64_t kPairLimit = int64_t(1) << 26;  // rows / columns of a pair (msa_sw_align has no limit of its own)
+
+// Every alignment entry: check the arguments (MSA_ERR_ARG; size_lim bounds m and n), the gap rule
+// (MSA_ERR_UNSUPPORTED), the band against the lengths (MSA_ERR_ARG), encode with one symbol map for the call, A
+// then B (MSA_ERR_ALPHABET), and only then ask for the device; then align_range chunk by chunk -- consecutive pairs
+// whose summed single-pair footprints fit a quarter of the device budget, at most 2^20 of them -- and hand out the
+// CIGARs.
+int align_pairs(AlignSpec spec, int single, const AlignIn& in, int64_t size_lim, int32_t gap_open,
+                int32_t gap_extend, int64_t band_in, const AlignOut& out) {
+  if (spec.status != MSA_OK) return spec.status;
+  if (!in.A || !in.B || !in.a_off || !in.m || !in.b_off || !in.n || in.np < 1 || (out.cigars && !out.cigar_off) ||
+      band_in < -1)
+    return MSA_ERR_ARG;
+  int64_t span_max = 0;
+  for (int64_t p = 0; p < in.np; ++p) {
+    const int64_t m = in.m[p], n = in.n[p], ao = in.a_off[p], bo = in.b_off[p];
+    if (m < 1 || n < 1 || m > size_lim || n > size_lim || ao < 0 || bo < 0 ||
+        (uint64_t)ao + (uint64_t)m > in.a_len || (uint64_t)bo + (uint64_t)n > in.b_len)
+      return MSA_ERR_ARG;
+    span_max = std::max(span_max, std::max(m, n));
+  }
+  if (spec.gaps == GAPS_LOCAL ? (spec.match < -128 || spec.match > 127 || spec.mismatch < -128 || spec.mismatch > 127 ||
+                                 gap_open < 0 || gap_extend < 0)
+                              : (gap_extend < 0 || gap_open < gap_extend))
+    return MSA_ERR_UNSUPPORTED;
+  if (!spec.banded) band_in = -1;
+  if (band_in >= 0)
+    for (int64_t p = 0; p < in.np; ++p)
+      if (std::llabs(in.m[p] - in.n[p]) > band_in) return MSA_ERR_ARG;
+  // (a band that holds every cell of every pair is no band)
+  const GapBand gb{gap_open, gap_extend, (band_in < 0 || band_in >= span_max) ? -1 : (int)band_in};
+  std::vector<uint8_t> ca(in.a_len), cb(in.b_len);
+  int rc = spec.symbols.encode(in.A, in.a_len, ca.data());
+  if (rc == MSA_OK) rc = spec.symbols.encode(in.B, in.b_len, cb.data());
+  if (rc != MSA_OK) return rc;
+  if ((rc = ensure_device()) != MSA_OK) return rc;
+  const bool want_tb = out.cigars || (spec.walk_for_beg && (out.beg.i || out.beg.j));
+  auto fp = [&](int64_t p) -> size_t {
+    if (spec.footprint == FOOT_BAND) return footprint_nw(in.m[p], in.n[p], gb.band, want_tb);
+    return want_tb ? footprint_dir(in.m[p], in.n[p]) : footprint_planes(in.m[p], in.n[p], 0, 1);
+  };
+  int64_t binfo[5];
+  admission().info(current_device(), binfo);
+  const size_t quarter = (size_t)binfo[0] / 4;
+  std::string all;  // the CIGARs, back to back
+  for (int64_t p0 = 0, p1; p0 < in.np; p0 = p1) {
+    size_t bytes = fp(p0);
+    p1 = p0 + 1;
+    while (p1 < in.np && p1 - p0 < (int64_t(1) << 20) && bytes + fp(p1) <= quarter) bytes += fp(p1++);
+    if ((rc = align_range(spec, single, gb, want_tb, ca.data(), cb.data(), in, p0, p1, bytes, out, all)) != MSA_OK)
+      return rc;
+  }
+  if (out.cigars) {
+    out.cigar_off[in.np] = (int64_t)all.size();
+    if (all.size() > out.cigar_cap) return MSA_ERR_CAPACITY;
+    std::memcpy(out.cigars, all.data(), all.size());
+  }
   return MSA_OK;
 }
 
@@ -1342,28 +1407,39 @@ int nw_align_one(const char* A0, size_t m, const char* B0, size_t n, const NwSco
 
 extern "C" {
 
+int msa_sw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t match, int32_t mismatch,
+                 int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_i, int64_t* end_j,
+                 int64_t* beg_i, int64_t* beg_j, char* cigar, size_t cigar_cap) {
+  const OnePairIn one(A0, m, B0, n);
+  int64_t coff[2];
+  const AlignOut out{score, PairOut(end_i, end_j), PairOut(beg_i, beg_j), PairOut(), cigar, cigar_cap, coff};
+  return align_pairs(spec_sw(match, mismatch, "ACGT"), 1, one.in, INT64_MAX, gap_open, gap_extend, -1, out);
+}
+
 int msa_nw_align(const char* A0, size_t m, const char* B0, size_t n, int32_t gap_open, int32_t gap_extend,
                  int64_t band, int32_t* score, char* cigar, size_t cigar_cap) {
-  return nw_align_one(A0, m, B0, n, nullptr, gap_open, gap_extend, band, score, cigar, cigar_cap);
+  const OnePairIn one(A0, m, B0, n);
+  int64_t coff[2];
+  const AlignOut out{score, PairOut(), PairOut(), PairOut(), cigar, cigar_cap, coff};
+  return align_pairs(spec_nw("ACGT"), 1, one.in, kPairLimit, gap_open, gap_extend, band, out);
 }
 
 int msa_nw_align_scored(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
                         const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band, int32_t* score,
                         char* cigar, size_t cigar_cap) {
-  NwScoring sc;
-  const int rc = sc.set(alphabet, n_sym, sub);
-  if (rc != MSA_OK) return rc;
-  return nw_align_one(A0, m, B0, n, &sc, gap_open, gap_extend, band, score, cigar, cigar_cap);
+  const OnePairIn one(A0, m, B0, n);
+  int64_t coff[2];
+  const AlignOut out{score, PairOut(), PairOut(), PairOut(), cigar, cigar_cap, coff};
+  return align_pairs(spec_scored(alphabet, n_sym, sub), 1, one.in, kPairLimit, gap_open, gap_extend, band, out);
 }
 
 int msa_fit_align(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
                   const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_j,
                   int64_t* end_j, char* cigar, size_t cigar_cap) {
-  NwScoring sc;
-  int rc = sc.set(alphabet, n_sym, sub);
-  if (rc != MSA_OK) return rc;
-  int64_t be[2] = {-1, -1};
-  rc = nw_align_one(A0, m, B0, n, &sc, gap_open, gap_extend, -1, score, cigar, cigar_cap, be);
+  const OnePairIn one(A0, m, B0, n);
+  int64_t coff[2], be[2] = {-1, -1};
+  const AlignOut out{score, PairOut(), PairOut(), PairOut(be), cigar, cigar_cap, coff};
+  const int rc = align_pairs(spec_fit(alphabet, n_sym, sub), 1, one.in, kPairLimit, gap_open, gap_extend, -1, out);
   // (a cigar too small still has its score and span)
   if (rc == MSA_OK || rc == MSA_ERR_CAPACITY) {
     if (beg_j) *beg_j = be[0];
@@ -1372,231 +1448,22 @@ int msa_fit_align(const char* A0, size_t m, const char* B0, size_t n, const char
   return rc;
 }
 
-}  // extern "C"
-
-// ---- batches of alignments with their CIGARs (msa_sw_align_batch, msa_nw_align_batch) ----------------------
-namespace {
-
-struct BatchIn {
-  const char *A, *B;
-  size_t a_len, b_len;
-  int64_t np;
-  const int64_t *a_off, *m, *b_off, *n;
-};
-
-// run-length string (start -> end) of ops given end -> start, NUL included, appended to `out`
-void append_cigar(std::string& out, const std::string& ops) {
-  for (int64_t k = (int64_t)ops.size() - 1; k >= 0;) {
-    const char op = ops[(size_t)k];
-    int64_t run = 0;
-    while (k >= 0 && ops[(size_t)k] == op) { run++; k--; }
-    out += std::to_string(run);
-    out.push_back(op);
-  }
-  out.push_back('\0');
-}
-
-// Both entries: validate, encode with one symbol map, then chunk by chunk (consecutive pairs whose summed
-// single-pair footprints fit a quarter of the device budget): admit, upload the chunk's code spans, one batch
-// plan, one run, one msa_plan_traceback_batch, fetch results, info and ops, build the CIGARs.
-// sc (nw only): the scored entry's alphabet and matrix instead of +1 / 0 over the call's own symbol map
-// fit_be (nw with sc only; msa_fit_align_batch): MSA_NW_FIT plans, no band, each walk from its pair's (m, end_j);
-// fit_be receives {beg_j, end_j} per pair, beg_j = -1 without walks
-int align_batch(bool nw, const BatchIn& in, const NwScoring* sc, int32_t match, int32_t mismatch, int32_t gap_open,
-                int32_t gap_extend, int64_t band_in, int32_t* score, int64_t* end_ij, int64_t* beg_ij, char* cigars,
-                size_t cigar_cap, int64_t* cigar_off, int64_t* fit_be = nullptr) {
-  if (!in.A || !in.B || !in.a_off || !in.m || !in.b_off || !in.n || in.np < 1 || (cigars && !cigar_off))
-    return MSA_ERR_ARG;
-  if (nw && band_in < -1) return MSA_ERR_ARG;
-  const int64_t lim = int64_t(1) << 26;
-  int64_t span_max = 0;
-  for (int64_t p = 0; p < in.np; ++p) {
-    const int64_t m = in.m[p], n = in.n[p], ao = in.a_off[p], bo = in.b_off[p];
-    if (m < 1 || n < 1 || m > lim || n > lim || ao < 0 || bo < 0 || (uint64_t)ao + (uint64_t)m > in.a_len ||
-        (uint64_t)bo + (uint64_t)n > in.b_len)
-      return MSA_ERR_ARG;
-    span_max = std::max(span_max, std::max(m, n));
-  }
-  if (nw) {
-    if (gap_extend < 0 || gap_open < gap_extend) return MSA_ERR_UNSUPPORTED;
-    if (band_in >= 0)
-      for (int64_t p = 0; p < in.np; ++p)
-        if (std::llabs(in.m[p] - in.n[p]) > band_in) return MSA_ERR_ARG;
-  } else if (match < -128 || match > 127 || mismatch < -128 || mismatch > 127 || gap_open < 0 || gap_extend < 0) {
-    return MSA_ERR_UNSUPPORTED;
-  }
-  // (a band that holds every cell of every pair is no band)
-  const int band = (!nw || band_in < 0 || band_in >= span_max) ? -1 : (int)band_in;
-  // one code map for the call, first-seen order over A then B (code 7 is the SW kernels' sentinel)
-  std::vector<uint8_t> ca(in.a_len), cb(in.b_len);
-  {
-    int map[256], next = 0;
-    const int max_codes = nw ? 8 : 7;
-    std::fill(map, map + 256, -1);
-    auto enc = [&](const char* s, size_t len, uint8_t* out) -> int {
-      for (size_t k = 0; k < len; ++k) {
-        const unsigned char c = (unsigned char)s[k];
-        if (map[c] < 0) {
-          if (next >= max_codes) return MSA_ERR_ALPHABET;
-          map[c] = next++;
-        }
-        out[k] = (uint8_t)map[c];
-      }
-      return MSA_OK;
-    };
-    int rc = sc ? sc->encode(in.A, in.a_len, ca.data()) : enc(in.A, in.a_len, ca.data());
-    if (rc == MSA_OK) rc = sc ? sc->encode(in.B, in.b_len, cb.data()) : enc(in.B, in.b_len, cb.data());
-    if (rc != MSA_OK) return rc;
-  }
-  const bool want_tb = cigars != nullptr || (!nw && beg_ij != nullptr);
-  int rc = ensure_device();
-  if (rc != MSA_OK) return rc;
-  auto fp = [&](int64_t p) -> size_t {
-    if (nw) return footprint_nw(in.m[p], in.n[p], band, want_tb);
-    return want_tb ? footprint_dir(in.m[p], in.n[p]) : footprint_planes(in.m[p], in.n[p], 0, 1);
-  };
-  int64_t binfo[5];
-  admission().info(current_device(), binfo);
-  const size_t quarter = (size_t)binfo[0] / 4;
-  std::string all;  // the CIGARs, back to back
-  for (int64_t p0 = 0; p0 < in.np;) {
-    size_t bytes = fp(p0);
-    int64_t p1 = p0 + 1;
-    while (p1 < in.np && p1 - p0 < (int64_t(1) << 20) && bytes + fp(p1) <= quarter) bytes += fp(p1++);
-    const int64_t K = p1 - p0;
-    // the chunk's code spans and its pairs relative to them
-    int64_t a_lo = INT64_MAX, a_hi = 0, b_lo = INT64_MAX, b_hi = 0;
-    for (int64_t p = p0; p < p1; ++p) {
-      a_lo = std::min(a_lo, in.a_off[p]);
-      a_hi = std::max(a_hi, in.a_off[p] + in.m[p]);
-      b_lo = std::min(b_lo, in.b_off[p]);
-      b_hi = std::max(b_hi, in.b_off[p] + in.n[p]);
-    }
-    std::vector<int64_t> ms(in.m + p0, in.m + p1), ns(in.n + p0, in.n + p1), ao((size_t)K), bo((size_t)K),
-        off((size_t)K + 1, 0);
-    for (int64_t k = 0; k < K; ++k) {
-      ao[(size_t)k] = in.a_off[p0 + k] - a_lo;
-      bo[(size_t)k] = in.b_off[p0 + k] - b_lo;
-      off[(size_t)k + 1] = off[(size_t)k] + ((ms[(size_t)k] + ns[(size_t)k] + 2 + 15) & ~int64_t(15));
-    }
-    Admit adm(bytes);  // waits until the chunk fits the device budget
-    StreamGuard sg;
-    if ((rc = sg.acquire()) != MSA_OK) return rc;
-    DevMem dA, dB, dDir, dOps, dOff, dInfo;
-    PlanGuard pg;
-    StreamSync sync{sg.s};
-    if ((rc = dA.alloc((size_t)(a_hi - a_lo))) || (rc = dB.alloc((size_t)(b_hi - b_lo)))) return rc;
-    HIPCHK(hipMemcpyAsync(dA.p, ca.data() + a_lo, (size_t)(a_hi - a_lo), hipMemcpyHostToDevice, sg.s));
-    HIPCHK(hipMemcpyAsync(dB.p, cb.data() + b_lo, (size_t)(b_hi - b_lo), hipMemcpyHostToDevice, sg.s));
-    msa_plan_desc d;
-    std::memset(&d, 0, sizeof(d));
-    if (nw) {
-      // the scores alone need no direction bytes: the value plan of the same recurrence (a scored plan has both)
-      d.alg = fit_be ? MSA_NW_FIT : sc ? MSA_NW_SCORED : (want_tb ? MSA_NW_ALIGN : MSA_NW_BANDED);
-      d.match = 1;
-      d.mismatch = 0;
-      d.start_type = -1;
-    } else {
-      d.alg = MSA_SW_AFFINE;
-      d.match = match;
-      d.mismatch = mismatch;
-      d.track_end = 1;
-    }
-    d.cells = want_tb ? MSA_CELLS_DIR : MSA_CELLS_NONE;
-    d.gap_open = gap_open;
-    d.gap_extend = gap_extend;
-    d.band = band;
-    d.single = 0;
-    d.n_pairs = K;
-    d.m = ms.data();
-    d.n = ns.data();
-    d.a_off = ao.data();
-    d.b_off = bo.data();
-    if ((rc = msa_plan_create_scored(&d, sc ? sc->tab : nullptr, &pg.p)) != MSA_OK) return rc;
-    if (want_tb) {
-      int64_t elems = 0;
-      msa_plan_cells_size(pg.p, &elems);
-      if ((rc = dDir.alloc((size_t)elems)) || (rc = dOps.alloc((size_t)off[(size_t)K])) ||
-          (rc = dOff.alloc(sizeof(int64_t) * (size_t)(K + 1))) || (rc = dInfo.alloc(64 * (size_t)K)))
-        return rc;
-      HIPCHK(hipMemcpyAsync(dOff.p, off.data(), sizeof(int64_t) * (size_t)(K + 1), hipMemcpyHostToDevice, sg.s));
-    }
-    if ((rc = msa_plan_run(pg.p, (const uint8_t*)dA.p, (const uint8_t*)dB.p, dDir.p, nullptr, nullptr, sg.s)))
-      return rc;
-    // every walk of the chunk in one launch: only the ops come back, not the direction bytes
-    if (want_tb && (rc = msa_plan_traceback_batch(pg.p, (const uint8_t*)dDir.p, (uint8_t*)dOps.p,
-                                                  (const int64_t*)dOff.p, (int64_t*)dInfo.p, sg.s)))
-      return rc;
-    std::vector<msa_pair_result> res((size_t)K);
-    if ((rc = msa_plan_results(pg.p, res.data(), sg.s)) != MSA_OK) return rc;
-    for (int64_t k = 0; k < K; ++k) {
-      if (score) score[p0 + k] = res[(size_t)k].score;
-      if (end_ij) {
-        end_ij[2 * (p0 + k)] = res[(size_t)k].end_i;
-        end_ij[2 * (p0 + k) + 1] = res[(size_t)k].end_j;
-      }
-      if (fit_be) {
-        fit_be[2 * (p0 + k)] = -1;
-        fit_be[2 * (p0 + k) + 1] = res[(size_t)k].end_j;
-      }
-    }
-    if (want_tb) {
-      std::vector<int64_t> info(8 * (size_t)K);
-      std::vector<char> ops((size_t)off[(size_t)K]);
-      HIPCHK(hipMemcpyAsync(info.data(), dInfo.p, 64 * (size_t)K, hipMemcpyDeviceToHost, sg.s));
-      HIPCHK(hipMemcpyAsync(ops.data(), dOps.p, ops.size(), hipMemcpyDeviceToHost, sg.s));
-      HIPCHK(hipStreamSynchronize(sg.s));
-      for (int64_t k = 0; k < K; ++k) {
-        const int64_t* inf = &info[8 * (size_t)k];
-        if (inf[3] != 0) return (int)inf[3];
-        std::string o(ops.data() + off[(size_t)k], (size_t)inf[0]);
-        if (nw) {
-          // the walk stopped on the matrix border at (i, j): the rest is one gap along it
-          const int64_t bi = inf[1] - 1, bj = inf[2] - 1;
-          // (a fit alignment: the reference's symbols before column j are free -- no 'D')
-          if (bi > 0) o.append((size_t)bi, 'I');
-          else if (bj > 0 && !fit_be) o.append((size_t)bj, 'D');
-          if (fit_be) fit_be[2 * (p0 + k)] = bj;
-        } else if (beg_ij) {
-          beg_ij[2 * (p0 + k)] = inf[1];
-          beg_ij[2 * (p0 + k) + 1] = inf[2];
-        }
-        if (cigars) {
-          cigar_off[p0 + k] = (int64_t)all.size();
-          append_cigar(all, o);
-        }
-      }
-    }
-    p0 = p1;
-  }
-  if (cigars) {
-    cigar_off[in.np] = (int64_t)all.size();
-    if (all.size() > cigar_cap) return MSA_ERR_CAPACITY;
-    std::memcpy(cigars, all.data(), all.size());
-  }
-  return MSA_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int msa_sw_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
                        const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n, int32_t match,
                        int32_t mismatch, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_ij,
                        int64_t* beg_ij, char* cigars, size_t cigar_cap, int64_t* cigar_off) {
-  const BatchIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
-  return align_batch(false, in, nullptr, match, mismatch, gap_open, gap_extend, -1, score, end_ij, beg_ij, cigars,
-                     cigar_cap, cigar_off);
+  const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  const AlignOut out{score, PairOut(end_ij), PairOut(beg_ij), PairOut(), cigars, cigar_cap, cigar_off};
+  return align_pairs(spec_sw(match, mismatch, ""), 0, in, kPairLimit, gap_open, gap_extend, -1, out);
 }
 
 int msa_nw_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
                        const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
                        int32_t gap_open, int32_t gap_extend, int64_t band, int32_t* score, char* cigars,
                        size_t cigar_cap, int64_t* cigar_off) {
-  const BatchIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
-  return align_batch(true, in, nullptr, 1, 0, gap_open, gap_extend, band, score, nullptr, nullptr, cigars, cigar_cap,
-                     cigar_off);
+  const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  const AlignOut out{score, PairOut(), PairOut(), PairOut(), cigars, cigar_cap, cigar_off};
+  return align_pairs(spec_nw(""), 0, in, kPairLimit, gap_open, gap_extend, band, out);
 }
 
 int msa_nw_align_batch_scored(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
@@ -1604,12 +1471,9 @@ int msa_nw_align_batch_scored(const char* A, size_t a_len, const char* B, size_t
                               const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
                               int32_t gap_extend, int64_t band, int32_t* score, char* cigars, size_t cigar_cap,
                               int64_t* cigar_off) {
-  NwScoring sc;
-  const int rc = sc.set(alphabet, n_sym, sub);
-  if (rc != MSA_OK) return rc;
-  const BatchIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
-  return align_batch(true, in, &sc, 1, 0, gap_open, gap_extend, band, score, nullptr, nullptr, cigars, cigar_cap,
-                     cigar_off);
+  const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  const AlignOut out{score, PairOut(), PairOut(), PairOut(), cigars, cigar_cap, cigar_off};
+  return align_pairs(spec_scored(alphabet, n_sym, sub), 0, in, kPairLimit, gap_open, gap_extend, band, out);
 }
 
 int msa_fit_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
@@ -1617,13 +1481,10 @@ int msa_fit_align_batch(const char* A, size_t a_len, const char* B, size_t b_len
                         const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
                         int32_t gap_extend, int32_t* score, int64_t* beg_end, char* cigars, size_t cigar_cap,
                         int64_t* cigar_off) {
-  NwScoring sc;
-  const int rc = sc.set(alphabet, n_sym, sub);
-  if (rc != MSA_OK) return rc;
   if (!beg_end) return MSA_ERR_ARG;
-  const BatchIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
-  return align_batch(true, in, &sc, 1, 0, gap_open, gap_extend, -1, score, nullptr, nullptr, cigars, cigar_cap,
-                     cigar_off, beg_end);
+  const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  const AlignOut out{score, PairOut(), PairOut(), PairOut(beg_end), cigars, cigar_cap, cigar_off};
+  return align_pairs(spec_fit(alphabet, n_sym, sub), 0, in, kPairLimit, gap_open, gap_extend, -1, out);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // msa_rowapi.inc -- C-ABI over rowsweep_kernel (msa_rowsweep.hip): the
 // reference's double-precision tables for any g, h, and its per-row / per-range
 // steps for the source-compatible `class Subproblem` (subproblem_alignment.h).
-// Included by msa_capi.hip after msa_refapi.inc (uses DevMem / StreamGuard).
+// Included by msa_capi.hip after msa_refapi.inc (uses DeviceCall; neither entry reserves a footprint).
 
 extern "C" {
 
@@ -20,48 +20,45 @@ int msa_subproblem_f64(const char* A1, const char* B1, size_t m_in, size_t n_in,
   const size_t idA = inv ? idB_in : idA_in, idB = inv ? idA_in : idB_in;
   if (invert) *invert = inv ? 1 : 0;
   const size_t W = n + 1, cells = (m + 1) * W;
-  StreamGuard sg;
-  if ((rc = sg.acquire()) != MSA_OK) return rc;
-  DevMem dA, dB, dT[3], dv;
-  StreamSync sync{sg.s};
-  if ((rc = dA.alloc(m + 1)) || (rc = dB.alloc(n + 1)) || (rc = dv.alloc(sizeof(double) * W))) return rc;
+  DeviceCall dc(0);
+  if ((rc = dc.status()) != MSA_OK) return rc;
+  void *dA, *dB, *dv, *dT[3];
+  if (!(dA = dc.alloc(m + 1)) || !(dB = dc.alloc(n + 1)) || !(dv = dc.alloc(sizeof(double) * W))) return MSA_ERR_NOMEM;
   for (auto& t : dT)
-    if ((rc = t.alloc(sizeof(double) * cells))) return rc;
+    if (!(t = dc.alloc(sizeof(double) * cells))) return MSA_ERR_NOMEM;
   // A[k] = reference A[id_A + k], B[j] = reference B[id_B + j] (f, subproblem_alignment.h:83-88)
-  HIPCHK(hipMemcpyAsync(dA.p, A + idA, m + 1, hipMemcpyHostToDevice, sg.s));
-  HIPCHK(hipMemcpyAsync(dB.p, B + idB, n + 1, hipMemcpyHostToDevice, sg.s));
+  if ((rc = dc.upload(dA, A + idA, m + 1)) || (rc = dc.upload(dB, B + idB, n + 1))) return rc;
   RowArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.T1 = (double*)dT[0].p;
-  a.T2 = (double*)dT[1].p;
-  a.T3 = (double*)dT[2].p;
+  a.T1 = (double*)dT[0];
+  a.T2 = (double*)dT[1];
+  a.T3 = (double*)dT[2];
   a.W = (long long)W;
   a.n = (long long)n;
-  a.A = (const char*)dA.p;
-  a.B = (const char*)dB.p;
+  a.A = (const char*)dA;
+  a.B = (const char*)dB;
   a.g = g;
   a.h = h;
   a.start_type = start_type;
-  a.vec = (double*)dv.p;
+  a.vec = (double*)dv;
   a.part = ROW_ZERO;  // compute_tables (:329-332): row 0, then rows 1..m in order
   a.i0 = 0;
   a.i1 = 1;
   a.slot0 = 0;
-  hipLaunchKernelGGL(rowsweep_kernel, dim3(1), dim3(RS_THREADS), 0, sg.s, a);
+  hipLaunchKernelGGL(rowsweep_kernel, dim3(1), dim3(RS_THREADS), 0, dc.stream(), a);
   HIPCHK(hipGetLastError());
   if (m > 0) {
     a.part = ROW_FULL | (mode == MSA_F64_NON_PARALLEL ? ROW_SEQ : 0);
     a.i0 = 1;
     a.i1 = (long long)m + 1;
     a.slot0 = 1;
-    hipLaunchKernelGGL(rowsweep_kernel, dim3(1), dim3(RS_THREADS), 0, sg.s, a);
+    hipLaunchKernelGGL(rowsweep_kernel, dim3(1), dim3(RS_THREADS), 0, dc.stream(), a);
     HIPCHK(hipGetLastError());
   }
   double* outs[3] = {T1, T2, T3};
   for (int v = 0; v < 3; ++v)
-    HIPCHK(hipMemcpyAsync(outs[v], dT[v].p, sizeof(double) * cells, hipMemcpyDeviceToHost, sg.s));
-  HIPCHK(hipStreamSynchronize(sg.s));
-  return MSA_OK;
+    if ((rc = dc.download(outs[v], dT[v], sizeof(double) * cells))) return rc;
+  return dc.sync();
 }
 
 int msa_subproblem_row(int part, const char* A1, const char* B1, size_t idA, size_t idB, size_t n, size_t i,
@@ -79,42 +76,40 @@ int msa_subproblem_row(int part, const char* A1, const char* B1, size_t idA, siz
   int rc = ensure_device();
   if (rc != MSA_OK) return rc;
   const size_t W = n + 1;
-  StreamGuard sg;
-  if ((rc = sg.acquire()) != MSA_OK) return rc;
-  DevMem dA, dB, dT[3], dv;
-  StreamSync sync{sg.s};
-  if ((rc = dA.alloc(1)) || (rc = dB.alloc(W)) || (rc = dv.alloc(sizeof(double) * W))) return rc;
+  DeviceCall dc(0);
+  if ((rc = dc.status()) != MSA_OK) return rc;
+  void *dA, *dB, *dv, *dT[3];
+  if (!(dA = dc.alloc(1)) || !(dB = dc.alloc(W)) || !(dv = dc.alloc(sizeof(double) * W))) return MSA_ERR_NOMEM;
   for (auto& t : dT)
-    if ((rc = t.alloc(sizeof(double) * 2 * W))) return rc;  // slot 0 = row i-1, slot 1 = row i
-  HIPCHK(hipMemcpyAsync(dA.p, A1 + idA + i, 1, hipMemcpyHostToDevice, sg.s));
-  HIPCHK(hipMemcpyAsync(dB.p, B1 + idB, W, hipMemcpyHostToDevice, sg.s));
+    if (!(t = dc.alloc(sizeof(double) * 2 * W))) return MSA_ERR_NOMEM;  // slot 0 = row i-1, slot 1 = row i
+  if ((rc = dc.upload(dA, A1 + idA + i, 1)) || (rc = dc.upload(dB, B1 + idB, W))) return rc;
   const double* ups[3] = {up1, up2, up3};
   double* curs[3] = {cur1, cur2, cur3};
   for (int v = 0; v < 3; ++v) {
-    if (needs_up) HIPCHK(hipMemcpyAsync(dT[v].p, ups[v], sizeof(double) * W, hipMemcpyHostToDevice, sg.s));
-    HIPCHK(hipMemcpyAsync((double*)dT[v].p + W, curs[v], sizeof(double) * W, hipMemcpyHostToDevice, sg.s));
+    if (needs_up && (rc = dc.upload(dT[v], ups[v], sizeof(double) * W))) return rc;
+    if ((rc = dc.upload((double*)dT[v] + W, curs[v], sizeof(double) * W))) return rc;
   }
-  if (vec) HIPCHK(hipMemcpyAsync(dv.p, vec, sizeof(double) * W, hipMemcpyHostToDevice, sg.s));
+  if (vec && (rc = dc.upload(dv, vec, sizeof(double) * W))) return rc;
   RowArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.T1 = (double*)dT[0].p;
-  a.T2 = (double*)dT[1].p;
-  a.T3 = (double*)dT[2].p;
+  a.T1 = (double*)dT[0];
+  a.T2 = (double*)dT[1];
+  a.T3 = (double*)dT[2];
   a.W = (long long)W;
   a.n = (long long)n;
   a.i0 = (long long)i;
   a.i1 = (long long)i + 1;
   a.slot0 = 1;
-  a.A = (const char*)dA.p - (long long)i;  // only A[i] is read
-  a.B = (const char*)dB.p;
+  a.A = (const char*)dA - (long long)i;  // only A[i] is read
+  a.B = (const char*)dB;
   a.g = g;
   a.h = h;
   a.start_type = start_type;
   a.part = part;
   a.start = (long long)start;
   a.end = (long long)end;
-  a.vec = (double*)dv.p;
-  hipLaunchKernelGGL(rowsweep_kernel, dim3(1), dim3(RS_THREADS), 0, sg.s, a);
+  a.vec = (double*)dv;
+  hipLaunchKernelGGL(rowsweep_kernel, dim3(1), dim3(RS_THREADS), 0, dc.stream(), a);
   HIPCHK(hipGetLastError());
   // copy back only what the part wrote: the reference runs MapThread bodies on
   // disjoint column ranges of one row from several threads at once (:294-325)
@@ -124,13 +119,12 @@ int msa_subproblem_row(int part, const char* A1, const char* B1, size_t idA, siz
                          part != MSA_ROW_OMEGA && part != MSA_ROW_13,
                          part != MSA_ROW_OMEGA && part != MSA_ROW_T2};
   for (int v = 0; v < 3; ++v)
-    if (wrote[v] && c1 > c0)
-      HIPCHK(hipMemcpyAsync(curs[v] + c0, (double*)dT[v].p + W + c0, sizeof(double) * (c1 - c0),
-                            hipMemcpyDeviceToHost, sg.s));
-  if (part == MSA_ROW_OMEGA && c1 > c0)
-    HIPCHK(hipMemcpyAsync(vec + c0, (double*)dv.p + c0, sizeof(double) * (c1 - c0), hipMemcpyDeviceToHost, sg.s));
-  HIPCHK(hipStreamSynchronize(sg.s));
-  return MSA_OK;
+    if (wrote[v] && c1 > c0 &&
+        (rc = dc.download(curs[v] + c0, (double*)dT[v] + W + c0, sizeof(double) * (c1 - c0))))
+      return rc;
+  if (part == MSA_ROW_OMEGA && c1 > c0 && (rc = dc.download(vec + c0, (double*)dv + c0, sizeof(double) * (c1 - c0))))
+    return rc;
+  return dc.sync();
 }
 
 }  // extern "C"

@@ -244,6 +244,16 @@ def test_cpp_scheduler_helpers_and_score_on_host():
         assert r.stdout == "SCORE 0\nEND_CASE\nSCORE 1\nEND_CASE\nSCORE 1\nEND_CASE\n", drv.name
 
 
+def test_cpp_host_helpers_under_sanitizers():
+    """csrc/msa_hostutil.h (symbol maps, CIGAR strings, the border gap, plan descriptions, the ops layout) through
+    tests/cpp/hostutil_driver, a stand-alone program built with -fsanitize=address,undefined: its own expected
+    values, and no sanitizer report."""
+    import subprocess
+
+    r = subprocess.run([str(_cpp_driver("hostutil_driver"))], capture_output=True, text=True, timeout=60)
+    assert (r.returncode, r.stdout, r.stderr) == (0, "OK\n", "")
+
+
 def _similarity_reference_loop(s1: bytes, s2: bytes, T: int) -> float:
     """pull_data.cpp:97-125 transcribed as loops (chunking, remainder on chunk T-1, / max length)."""
     L = min(len(s1), len(s2))
