@@ -97,6 +97,7 @@ def lib() -> C.CDLL:
                                                  C.POINTER(sz)]
     L.msa_plan_create.argtypes = [C.POINTER(PlanDesc), C.POINTER(P)]
     L.msa_plan_create_scored.argtypes = [C.POINTER(PlanDesc), P, C.POINTER(P)]
+    L.msa_plan_create_scored32.argtypes = [C.POINTER(PlanDesc), P, C.POINTER(P)]
     L.msa_plan_destroy.argtypes = [P]
     L.msa_plan_destroy.restype = None
     L.msa_plan_cells_size.argtypes = [P, C.POINTER(i64)]
@@ -130,6 +131,11 @@ def lib() -> C.CDLL:
     L.msa_fit_align.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), P,
                                 sz]
     L.msa_fit_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, P, P, P, sz, P]
+    # the *32 entries: their 8-symbol twins' signatures
+    L.msa_nw_align_scored32.argtypes = L.msa_nw_align_scored.argtypes
+    L.msa_nw_align_batch_scored32.argtypes = L.msa_nw_align_batch_scored.argtypes
+    L.msa_fit_align32.argtypes = L.msa_fit_align.argtypes
+    L.msa_fit_align_batch32.argtypes = L.msa_fit_align_batch.argtypes
     _lib = L.lib
     return _lib
 
@@ -158,4 +164,6 @@ EXPORTED = [
     "msa_plan_traceback_batch", "msa_sw_align_batch", "msa_nw_align_batch",
     "msa_plan_create_scored", "msa_nw_align_scored", "msa_nw_align_batch_scored",
     "msa_fit_align", "msa_fit_align_batch",
+    "msa_plan_create_scored32", "msa_nw_align_scored32", "msa_nw_align_batch_scored32",
+    "msa_fit_align32", "msa_fit_align_batch32",
 ]

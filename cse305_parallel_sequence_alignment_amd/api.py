@@ -282,13 +282,28 @@ def sw_align(A, B, match=1, mismatch=0, gap_open=1, gap_extend=1, traceback=True
     return r
 
 
-def _nw_scoring(seqs, match, mismatch, alphabet, matrix):
+def _entry(name: str, max_symbols: int) -> str:
+    """The library entry of a matrix-scored call: ``name`` itself, or its twin for up to 32 symbols."""
+    if max_symbols not in (8, 32):
+        raise ValueError("max_symbols must be 8 or 32")
+    if max_symbols == 8:
+        return name
+    return {"msa_nw_align_scored": "msa_nw_align_scored32", "msa_nw_align_batch_scored": "msa_nw_align_batch_scored32",
+            "msa_fit_align": "msa_fit_align32", "msa_fit_align_batch": "msa_fit_align_batch32"}[name]
+
+
+def _nw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols=8):
     """The scoring of nw_align / nw_align_batch: None when none of the four arguments is given (+1 / 0), else
     (alphabet bytes, n_sym x n_sym int8 matrix, row = A's symbol).  ``match`` / ``mismatch`` (the other defaults to
-    1 / 0): the alphabet is the distinct symbols of ``seqs`` in first-seen order (more than 8: MsaError with the
-    ALPHABET status).  ``matrix`` needs ``alphabet`` and excludes ``match`` / ``mismatch`` (ValueError)."""
+    1 / 0): the alphabet is the distinct symbols of ``seqs`` in first-seen order (more than ``max_symbols``, 8 or 32:
+    MsaError with the ALPHABET status).  ``matrix`` needs ``alphabet`` and excludes ``match`` / ``mismatch``
+    (ValueError).  With ``max_symbols=32`` and none of the four given, +1 / 0 over the symbols of ``seqs`` (the
+    32-symbol entries always take an alphabet and a matrix)."""
+    _entry("msa_nw_align_scored", max_symbols)  # (the ValueError of any other max_symbols)
     if match is None and mismatch is None and alphabet is None and matrix is None:
-        return None
+        if max_symbols == 8:
+            return None
+        match, mismatch = 1, 0
     if matrix is not None:
         if match is not None or mismatch is not None:
             raise ValueError("give either matrix (with alphabet) or match / mismatch, not both")
@@ -305,7 +320,7 @@ def _nw_scoring(seqs, match, mismatch, alphabet, matrix):
     if alphabet is not None:
         raise ValueError("alphabet comes with matrix")
     seen = dict.fromkeys(b"".join(seqs))  # first-seen order
-    if len(seen) > 8:
+    if len(seen) > max_symbols:
         raise LB.MsaError(-2, "nw_align")
     ma, mi = (1 if match is None else int(match)), (0 if mismatch is None else int(mismatch))
     if not (-128 <= ma <= 127 and -128 <= mi <= 127):
@@ -317,7 +332,7 @@ def _nw_scoring(seqs, match, mismatch, alphabet, matrix):
 
 
 def nw_align(A, B, gap_open=3, gap_extend=1, band=-1, traceback=True, match=None, mismatch=None, alphabet=None,
-             matrix=None):
+             matrix=None, max_symbols=8):
     """Global (Gotoh) alignment (build extension) -> dict(score, cigar).
 
     +1 on equal symbols, 0 otherwise; a gap of L costs (gap_open - gap_extend) + gap_extend * L.  ``band`` >= 0
@@ -328,9 +343,13 @@ def nw_align(A, B, gap_open=3, gap_extend=1, band=-1, traceback=True, match=None
     Other scores (msa_nw_align_scored): ``match`` and / or ``mismatch`` (the other stays 1 / 0) over the symbols
     of A and B, at most 8; or ``alphabet`` (up to 8 distinct bytes) with ``matrix``, len(alphabet) x len(alphabet)
     scores in [-128, 127], ``matrix[a][b]`` = alphabet[a] in A against alphabet[b] in B (it need not be
-    symmetric).  With none of the four given, today's +1 / 0 call runs."""
+    symmetric).  With none of the four given, today's +1 / 0 call runs.
+
+    ``max_symbols=32`` (msa_nw_align_scored32; any value but 8 or 32 is a ValueError): proteins, IUPAC DNA --
+    ``alphabet`` may hold up to 32 bytes, ``match`` / ``mismatch`` take up to 32 distinct symbols, and with none of
+    the four given the call scores +1 / 0 over the symbols of A and B."""
     A, B = _buf(A), _buf(B)
-    scoring = _nw_scoring((A, B), match, mismatch, alphabet, matrix)
+    scoring = _nw_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
     sc = C.c_int32()
     cap = 4 * (len(A) + len(B)) + 16
     cig = C.create_string_buffer(cap) if traceback else None
@@ -339,9 +358,9 @@ def nw_align(A, B, gap_open=3, gap_extend=1, band=-1, traceback=True, match=None
                                        cap if traceback else 0), "msa_nw_align")
     else:
         alpha, S = scoring
-        LB.check(LB.lib().msa_nw_align_scored(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p),
-                                              gap_open, gap_extend, band, C.byref(sc), cig,
-                                              cap if traceback else 0), "msa_nw_align_scored")
+        name = _entry("msa_nw_align_scored", max_symbols)
+        LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p),
+                                         gap_open, gap_extend, band, C.byref(sc), cig, cap if traceback else 0), name)
     r = dict(score=sc.value)
     if traceback:
         r["cigar"] = cig.value.decode()
@@ -404,17 +423,19 @@ def sw_align_batch(As, Bs, match=1, mismatch=0, gap_open=1, gap_extend=1, traceb
 
 
 def nw_align_batch(As, Bs, gap_open=3, gap_extend=1, band=-1, traceback=True, match=None, mismatch=None,
-                   alphabet=None, matrix=None):
+                   alphabet=None, matrix=None, max_symbols=8):
     """A batch of global (Gotoh) alignments (msa_nw_align_batch) -> a list of nw_align()'s dicts.
 
     ``Bs`` as for sw_align_batch; scoring and ``band`` as for nw_align (the band holds for every pair).  One
     symbol map serves the whole call: at most 8 distinct symbols in all of As and Bs together.  ``match`` /
     ``mismatch`` / ``alphabet`` / ``matrix`` as for nw_align (msa_nw_align_batch_scored); the alphabet of ``match`` /
-    ``mismatch`` is the distinct symbols of all As, then all Bs, in first-seen order."""
+    ``mismatch`` is the distinct symbols of all As, then all Bs, in first-seen order.  ``max_symbols=32`` as for
+    nw_align (msa_nw_align_batch_scored32): up to 32 distinct symbols in the whole call."""
+    _entry("msa_nw_align_batch_scored", max_symbols)
     if len(As) == 0:
         return []
     A, B, a_off, m, b_off, n = _batch_in(As, Bs)
-    scoring = _nw_scoring((A, B), match, mismatch, alphabet, matrix)
+    scoring = _nw_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
     k = len(m)
     sc = np.zeros(k, dtype=np.int32)
     coff = np.zeros(k + 1, dtype=np.int64)
@@ -426,11 +447,11 @@ def nw_align_batch(As, Bs, gap_open=3, gap_extend=1, band=-1, traceback=True, ma
                                              cig, cap, _i64p(coff) if traceback else None), "msa_nw_align_batch")
     else:
         alpha, S = scoring
-        LB.check(LB.lib().msa_nw_align_batch_scored(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off),
-                                                    _i64p(n), alpha, len(alpha), S.ctypes.data_as(C.c_void_p),
-                                                    gap_open, gap_extend, band, sc.ctypes.data_as(C.c_void_p), cig,
-                                                    cap, _i64p(coff) if traceback else None),
-                 "msa_nw_align_batch_scored")
+        name = _entry("msa_nw_align_batch_scored", max_symbols)
+        LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
+                                         alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend, band,
+                                         sc.ctypes.data_as(C.c_void_p), cig, cap,
+                                         _i64p(coff) if traceback else None), name)
     out = []
     for p in range(k):
         r = dict(score=int(sc[p]))
@@ -440,15 +461,15 @@ def nw_align_batch(As, Bs, gap_open=3, gap_extend=1, band=-1, traceback=True, ma
     return out
 
 
-def _fit_scoring(seqs, match, mismatch, alphabet, matrix):
+def _fit_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols=8):
     """_nw_scoring, with +1 / 0 over the symbols of ``seqs`` when none of the four arguments is given (the fit
     entries always take an alphabet and a matrix)."""
-    scoring = _nw_scoring(seqs, match, mismatch, alphabet, matrix)
-    return _nw_scoring(seqs, 1, 0, None, None) if scoring is None else scoring
+    scoring = _nw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols)
+    return _nw_scoring(seqs, 1, 0, None, None, max_symbols) if scoring is None else scoring
 
 
 def fit_align(query, ref, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
-              matrix=None):
+              matrix=None, max_symbols=8):
     """Fit ("glocal", "semi-global", "infix") alignment (build extension, msa_fit_align): ALL of ``query`` against
     the substring of ``ref`` it fits best -> dict(score, beg, end[, cigar]), ``ref[beg:end]`` being that substring.
 
@@ -457,16 +478,17 @@ def fit_align(query, ref, gap_open=3, gap_extend=1, traceback=True, match=None, 
     (start -> end, I consumes the query, D the reference) consumes all of the query and ``end - beg`` reference
     symbols; ``beg == end`` when the best alignment inserts the whole query.  ``traceback=False`` gives the score
     and ``end`` only (``beg`` is None).  Scoring as for nw_align: ``match`` / ``mismatch``, or ``alphabet`` with
-    ``matrix``; with none given +1 / 0."""
+    ``matrix``; with none given +1 / 0.  ``max_symbols=32`` (msa_fit_align32): up to 32 symbols, as for nw_align."""
     A, B = _buf(query), _buf(ref)
-    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix)
+    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
+    name = _entry("msa_fit_align", max_symbols)
     sc = C.c_int32()
     bj, ej = C.c_int64(), C.c_int64()
     cap = 4 * (len(A) + len(B)) + 16
     cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(LB.lib().msa_fit_align(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open,
-                                    gap_extend, C.byref(sc), C.byref(bj), C.byref(ej), cig,
-                                    cap if traceback else 0), "msa_fit_align")
+    LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open,
+                                     gap_extend, C.byref(sc), C.byref(bj), C.byref(ej), cig,
+                                     cap if traceback else 0), name)
     r = dict(score=sc.value, beg=bj.value if traceback else None, end=ej.value)
     if traceback:
         r["cigar"] = cig.value.decode()
@@ -474,26 +496,28 @@ def fit_align(query, ref, gap_open=3, gap_extend=1, traceback=True, match=None, 
 
 
 def fit_align_batch(queries, refs, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None,
-                    alphabet=None, matrix=None):
+                    alphabet=None, matrix=None, max_symbols=8):
     """A batch of fit alignments (msa_fit_align_batch) -> a list of fit_align()'s dicts.
 
     ``refs``: a list as long as ``queries``, or one bytes object every query is aligned against (uploaded once),
     exactly like nw_align_batch's ``Bs``; scoring as for fit_align, over one alphabet for the whole call (``match``
-    / ``mismatch``: the distinct symbols of all queries, then all refs, in first-seen order)."""
+    / ``mismatch``: the distinct symbols of all queries, then all refs, in first-seen order).  ``max_symbols=32``
+    (msa_fit_align_batch32): up to 32 symbols in the whole call."""
+    name = _entry("msa_fit_align_batch", max_symbols)
     if len(queries) == 0:
         return []
     A, B, a_off, m, b_off, n = _batch_in(queries, refs)
-    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix)
+    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
     k = len(m)
     sc = np.zeros(k, dtype=np.int32)
     be = np.zeros((k, 2), dtype=np.int64)
     coff = np.zeros(k + 1, dtype=np.int64)
     cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
     cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(LB.lib().msa_fit_align_batch(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
-                                          alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend,
-                                          sc.ctypes.data_as(C.c_void_p), _i64p(be), cig, cap,
-                                          _i64p(coff) if traceback else None), "msa_fit_align_batch")
+    LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
+                                     alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend,
+                                     sc.ctypes.data_as(C.c_void_p), _i64p(be), cig, cap,
+                                     _i64p(coff) if traceback else None), name)
     out = []
     for p in range(k):
         r = dict(score=int(sc[p]), beg=int(be[p, 0]) if traceback else None, end=int(be[p, 1]))

@@ -351,7 +351,8 @@ StreamPool& stream_pool() {
 int nc_of(int alg) {
   switch (alg) {
     case MSA_ALG_SWL: case MSA_ALG_SWL0: case MSA_ALG_SWLP: return 1;
-    case MSA_ALG_SWA: case MSA_ALG_NWA: case MSA_ALG_REF1: case MSA_ALG_FIT: return 2;
+    case MSA_ALG_SWA: case MSA_ALG_NWA: case MSA_ALG_REF1: case MSA_ALG_FIT: case MSA_ALG_NWA32: case MSA_ALG_FIT32:
+      return 2;
     default: return 3;
   }
 }
@@ -468,6 +469,15 @@ kfn_t pick_kernel(int alg, int out, int tp, bool sgl) {
       // (instantiations of their own: the MSA_ALG_NWA kernels' code is unchanged)
       if (out == MSA_OUT_NONE) return kf<MSA_ALG_FIT, MSA_OUT_NONE, 0>(sgl);
       if (out == MSA_OUT_DIR) return kf<MSA_ALG_FIT, MSA_OUT_DIR, 0>(sgl);
+      break;
+    // 5-bit codes under a 32 x 32 table (msa_plan_create_scored32): instantiations of their own again
+    case MSA_ALG_NWA32:
+      if (out == MSA_OUT_NONE) return kf<MSA_ALG_NWA32, MSA_OUT_NONE, 0>(sgl);
+      if (out == MSA_OUT_DIR) return kf<MSA_ALG_NWA32, MSA_OUT_DIR, 0>(sgl);
+      break;
+    case MSA_ALG_FIT32:
+      if (out == MSA_OUT_NONE) return kf<MSA_ALG_FIT32, MSA_OUT_NONE, 0>(sgl);
+      if (out == MSA_OUT_DIR) return kf<MSA_ALG_FIT32, MSA_OUT_DIR, 0>(sgl);
       break;
   }
 #undef K3
@@ -646,7 +656,8 @@ int msa_plan_run(msa_plan* P, const uint8_t* dA, const uint8_t* dB, void* c0, vo
     const int64_t words = MSA_NCOPY * (P->cod_copy / 4) / std::max<int64_t>(1, (int64_t)P->segs.size());
     const unsigned gx = (unsigned)std::min<int64_t>(1024, std::max<int64_t>(64, words / 512));
     hipLaunchKernelGGL(stage_codes_kernel, dim3(gx, (unsigned)P->segs.size()), dim3(256), 0, st, dB, P->d_segs,
-                       (int)P->segs.size(), P->d_cod, (long long)P->cod_copy, virt, P->d_ticket);
+                       (int)P->segs.size(), P->d_cod, (long long)P->cod_copy, virt, wide(P->main.kp.alg) ? 31u : 7u,
+                       P->d_ticket);
     HIPCHK(hipGetLastError());
   }
   const bool ev = P->timing;  // timing events are instrumentation: msa_plan_set_timing
@@ -692,7 +703,7 @@ int msa_plan_run(msa_plan* P, const uint8_t* dA, const uint8_t* dB, void* c0, vo
     return MSA_OK;
   }
   // (2: a fit plan's pair result is the first maximum of row m, from the meta of the stripe that holds it)
-  const int sw = (is_linear(P->main.kp.alg) || P->main.kp.alg == MSA_ALG_SWA) ? 1 : (P->main.kp.alg == MSA_ALG_FIT ? 2 : 0);
+  const int sw = (is_linear(P->main.kp.alg) || P->main.kp.alg == MSA_ALG_SWA) ? 1 : (fitk(P->main.kp.alg) ? 2 : 0);
   const int np = (int)P->d.n_pairs;
   hipLaunchKernelGGL(reduce_pairs_kernel, dim3(np), dim3(64), 0, st, P->d_pairs, P->d_meta, np, sw,
                      P->d_res);
@@ -772,7 +783,7 @@ int msa_plan_format_info(const msa_plan* P, int32_t* out4) {
   out4[0] = alg == MSA_ALG_SWLP ? 1 : (alg == MSA_ALG_REF1 ? 2 : 0);
   out4[1] = P->tp;
   out4[2] = P->h16 ? 1 : 0;
-  out4[3] = 0;
+  out4[3] = wide(alg) ? 1 : 0;
   return MSA_OK;
 }
 

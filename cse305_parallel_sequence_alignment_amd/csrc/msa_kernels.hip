@@ -93,8 +93,15 @@ constexpr bool pk16(int alg) { return alg == MSA_ALG_SWLP; }
 template <> struct Tr<MSA_ALG_SWA> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_NWA> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_FIT> { static constexpr int NC = 2; };
-// the banded Gotoh cell (MSA_ALG_NWA), or the same cell under the fit alignment's zero top border (MSA_ALG_FIT)
-constexpr bool nwa(int alg) { return alg == MSA_ALG_NWA || alg == MSA_ALG_FIT; }
+template <> struct Tr<MSA_ALG_NWA32> { static constexpr int NC = 2; };
+template <> struct Tr<MSA_ALG_FIT32> { static constexpr int NC = 2; };
+// 5-bit codes: the lane's profile is a 32-byte row of the plan's 32 x 32 table (score4_wide)
+constexpr bool wide(int alg) { return alg == MSA_ALG_NWA32 || alg == MSA_ALG_FIT32; }
+// the banded Gotoh cell under the global borders (nwg), the same cell under the fit alignment's zero top border
+// (fitk), either (nwa) -- over 3-bit or 5-bit codes
+constexpr bool nwg(int alg) { return alg == MSA_ALG_NWA || alg == MSA_ALG_NWA32; }
+constexpr bool fitk(int alg) { return alg == MSA_ALG_FIT || alg == MSA_ALG_FIT32; }
+constexpr bool nwa(int alg) { return nwg(alg) || fitk(alg); }
 template <> struct Tr<MSA_ALG_REF> { static constexpr int NC = 3; };
 template <> struct Tr<MSA_ALG_REF1> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_PART> { static constexpr int NC = 3; };
@@ -194,7 +201,8 @@ struct KArgs {
   // (fl_block_result, msa_flow.hip) when set; else reduce_blocks_kernel runs after the launch
   unsigned long long* best_key;
   // MSA_ALG_NWA, MSA_ALG_FIT: the plan's substitution table, one 8-byte profile per row code (byte b of entry a = the
-  // score of row code a against column code b, in the launch's own space: msa_plan.inc, sub_table)
+  // score of row code a against column code b, in the launch's own space: msa_plan.inc, sub_table).
+  // MSA_ALG_NWA32, MSA_ALG_FIT32: 1,024 raw scores, byte 32 a + b
   const uint2* sub;
 };
 #ifndef MSA_H16_PAIRED
@@ -216,13 +224,13 @@ __device__ __forceinline__ void border_top(const msa_kparams& kp, int c, int (&v
     v[0] = c >= 0 ? 0 : MSA_NEG;  // H
     v[1] = MSA_NEG;               // F
     v[2] = MSA_NEG;
-  } else if constexpr (ALG == MSA_ALG_FIT) {
+  } else if constexpr (fitk(ALG)) {
     // the reference's symbols before the aligned substring are free: H(0,c) = 0 on every column c >= 0 (columns
     // past n are masked where they are read, as MSA_ALG_NWA's are); E = F = -inf
     v[0] = c >= 0 ? 0 : MSA_NEG;
     v[1] = MSA_NEG;
     v[2] = MSA_NEG;
-  } else if constexpr (ALG == MSA_ALG_NWA) {
+  } else if constexpr (nwg(ALG)) {
     if (r0 > 0) {
       const int d = c > r0 ? c - r0 : r0 - c;
       v[0] = (d <= kp.band) ? -kp.h - kp.gap_ext * d : MSA_NEG;
@@ -317,6 +325,7 @@ struct LaneState {
   int pb;        // SWLP: max over the current phase's steps k of G - g k (both pairs, int16)
   int fin[3];
   unsigned plo, phi;  // substitution profile (8 int8 scores by column code)
+  unsigned pw[wide(ALG) ? 8 : 1];  // 5-bit codes: the profile, 32 int8 scores by column code (plo / phi unused)
   int i;              // DP row
 };
 
@@ -574,6 +583,19 @@ __device__ __forceinline__ void ntstore(int4* p, int4 v) {
   __builtin_nontemporal_store(x, reinterpret_cast<msa_v4i*>(p));
 }
 
+// Four scores of one row of a 32 x 32 table: p = the row's 32 int8 scores (dword d = column codes 4d..4d+3), cw = four
+// 5-bit column codes, one per byte; byte k of the result = the score against code k of cw.  A v_perm_b32 selects among
+// 8 bytes, so: the candidate of each 8-code group by the codes' low three bits (4 perms), then bit 3 picks inside each
+// pair of groups and bit 4 between the pairs (3 perms; selector byte k = k, + 4 for the upper source).
+__device__ __forceinline__ unsigned score4_wide(const unsigned (&p)[8], unsigned cw) {
+  const unsigned lo3 = cw & 0x07070707u;
+  const unsigned q0 = __builtin_amdgcn_perm(p[1], p[0], lo3), q1 = __builtin_amdgcn_perm(p[3], p[2], lo3);
+  const unsigned q2 = __builtin_amdgcn_perm(p[5], p[4], lo3), q3 = __builtin_amdgcn_perm(p[7], p[6], lo3);
+  const unsigned sa = 0x03020100u | ((cw >> 1) & 0x04040404u);
+  const unsigned sb = 0x03020100u | ((cw >> 2) & 0x04040404u);
+  return __builtin_amdgcn_perm(__builtin_amdgcn_perm(q3, q2, sa), __builtin_amdgcn_perm(q1, q0, sa), sb);
+}
+
 enum Src { SRC_BORDER = 0, SRC_RING = 1, SRC_ROW = 2, SRC_GLOBAL = 3 };
 enum Snk { SNK_NONE = 0, SNK_RING = 1, SNK_ROW = 2, SNK_GLOBAL = 3 };
 
@@ -675,6 +697,15 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
   constexpr bool LDSCODE = SGL;
   constexpr int CRW = MSA_CRING / 4 + 16;  // dwords per copy
   unsigned* cring = reinterpret_cast<unsigned*>(rowbuf + NC * kp.lds_row_words);
+  // 5-bit codes: the plan's 32 x 32 table (1 KiB, 256 dwords) behind everything else, copied once per workgroup
+  // (visible after the first ticket barrier; no item overwrites it).  A lane reads its row from here at its
+  // stripe's start with two ds_read_b128.  A per-lane global load at a.sub + 32 ac would need the row code first:
+  // two HBM latencies in a row in front of the workgroup's barriers at every round of stripes, or on the stripe's
+  // start if issued behind them; 32 rows are too many for the 8-code kernels' uniform loads and select chain.
+  unsigned* subl = cring + (LDSCODE ? 4 * CRW : 0);
+  if constexpr (wide(ALG)) {
+    if (threadIdx.x < 256) subl[threadIdx.x] = reinterpret_cast<const unsigned*>(a.sub)[threadIdx.x];
+  }
 
   for (;;) {
     // ---- ticket ----
@@ -978,14 +1009,15 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
       // (on the critical path of the wavefront if it waited for the stripe start)
       const int ks = k0 + cur;  // pair-local stripe index
       const int row_i = 64 * ks + lane + 1;
-      const unsigned ac = (row_i <= m) ? (a.A[pd.a_off + row_i - 1] & 7u) : 0u;
+      constexpr unsigned CMASK = wide(ALG) ? 31u : 7u;
+      const unsigned ac = (row_i <= m) ? (a.A[pd.a_off + row_i - 1] & CMASK) : 0u;
       const unsigned ac2 = (pk16(ALG) && row_i <= m) ? (a.A[pd2.a_off + row_i - 1] & 7u) : 0u;
       // banded Gotoh: the row's profile is row ac of the plan's table.  The whole 64-byte table is loaded here at
       // wave-uniform addresses, independent of the row code's load and like it ahead of the idle phases; the lane's
       // row is taken by selects at the stripe's start (a load at a.sub[ac] would wait for ac here, in front of the
       // workgroup's barriers)
       uint2 tab[8] = {};
-      if constexpr (nwa(ALG)) {
+      if constexpr (nwa(ALG) && !wide(ALG)) {
 #pragma unroll
         for (int c = 0; c < 8; ++c) tab[c] = a.sub[c];
       }
@@ -1003,7 +1035,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
 #pragma unroll
         for (int v = 0; v < 3; ++v) { L.LB[v] = lb[v]; L.S[v] = lb[v]; L.U[v] = MSA_NEG; L.fin[v] = 0; }
       }
-      L.best = (ALG == MSA_ALG_FIT) ? INT32_MIN : 0;  // (FIT: every H(m, j) is finite, > MSA_NEG)
+      L.best = fitk(ALG) ? INT32_MIN : 0;  // (FIT: every H(m, j) is finite, > MSA_NEG)
       L.bt = -1;
       L.pb = (int)0x80008000u;
       const int gdiag = kp.gap_open * (64 * ks + 1 + sg.cs);  // SWL: g*(i+j) at step 0, same for all lanes
@@ -1025,8 +1057,14 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
           L.U[0] = pk2(L.U[0]);
         }
       }
-      // substitution profile of this row (codes 0..7)
-      if constexpr (nwa(ALG)) {
+      // substitution profile of this row (codes 0..7; 5-bit codes: 0..31, row ac of the LDS table)
+      if constexpr (wide(ALG)) {
+        const uint4* prow = reinterpret_cast<const uint4*>(subl + 8 * ac);
+        const uint4 p0 = prow[0], p1 = prow[1];
+        L.pw[0] = p0.x; L.pw[1] = p0.y; L.pw[2] = p0.z; L.pw[3] = p0.w;
+        L.pw[4] = p1.x; L.pw[5] = p1.y; L.pw[6] = p1.z; L.pw[7] = p1.w;
+        L.plo = L.phi = L.plo2 = L.phi2 = 0;
+      } else if constexpr (nwa(ALG)) {
         L.plo = tab[0].x;
         L.phi = tab[0].y;
 #pragma unroll
@@ -1227,7 +1265,9 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         int4* t3row = reinterpret_cast<int4*>(a.outT3 + obase) + (size_t)((KS / 4) * q) * 64 + lane;
 #pragma unroll
         for (int u = 0; u < KS / 4; ++u) {
-          const unsigned s4 = __builtin_amdgcn_perm(L.phi, L.plo, cw[u]);
+          unsigned s4;
+          if constexpr (wide(ALG)) s4 = score4_wide(L.pw, cw[u]);
+          else s4 = __builtin_amdgcn_perm(L.phi, L.plo, cw[u]);
           const unsigned s4b = pk16(ALG) ? __builtin_amdgcn_perm(L.phi2, L.plo2, cw[u]) : 0u;
           unsigned dq = 0;
 #pragma unroll
@@ -1244,7 +1284,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
             int ct = pk16(ALG) ? gkp[k] : gdiag + kp.gap_open * t;
             if constexpr (swlin(ALG) && !pk16(ALG)) asm("" : "+s"(ct));  // one SGPR feeds both the floor and H
             unsigned d;
-            if constexpr (ALG == MSA_ALG_NWA && MMODE >= 2) {
+            if constexpr (nwg(ALG) && MMODE >= 2) {
               d = step<ALG, OUT, false, TRACKPOS, false>(kp, L, inv, s, t, ct, cr, hv[k]);
               // one lane per two steps sits on the band's edge: its index is wave-uniform
               constexpr int PAR = MMODE & 1;
@@ -1274,7 +1314,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
             } else {
               d = step<ALG, OUT, MASKED, TRACKPOS, FIN>(kp, L, inv, s, t, ct, cr, hv[k]);
             }
-            if constexpr (ALG == MSA_ALG_FIT && FIN) {
+            if constexpr (fitk(ALG) && FIN) {
               // the stripe of row m (every phase of it, the unmasked body too: FIN): a lane keeps the first
               // maximum of its row's H over the row's own columns 1..n -- strict >, so the earliest step wins;
               // a step on column <= 0 or > n (t outside [tmin, tmax]) never counts, and in an unmasked phase
@@ -1406,7 +1446,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         run_range(qi, P, F_{}, T_{}, F_{});
       } else if (fin_stripe) {
         run_range(0, qa, T_{}, T_{}, T_{});
-        if constexpr (ALG == MSA_ALG_FIT) run_range(qa, qb, F_{}, F_{}, T_{});  // (row m's maximum: every phase)
+        if constexpr (fitk(ALG)) run_range(qa, qb, F_{}, F_{}, T_{});  // (row m's maximum: every phase)
         else run_range(qa, qb, F_{}, F_{}, F_{});
         run_range(qb, P, T_{}, T_{}, T_{});
       } else {
@@ -1418,7 +1458,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         // and every other stripe, band_fix.
         bool regular = false;
         int A0 = 0, C0 = 0;
-        if constexpr (ALG == MSA_ALG_NWA) {
+        if constexpr (nwg(ALG)) {
           const int i0 = 64 * ks + 1;
           regular = uni(kp.band >= 64 && i0 + 63 <= m && i0 - kp.band > 1 && i0 + 63 + kp.band < n);
           A0 = uni(jlo_of(i0, kp.band) - sg.cs);
@@ -1504,7 +1544,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         }
       } else {
         if (L.i == m) {
-          if constexpr (ALG == MSA_ALG_FIT) {
+          if constexpr (fitk(ALG)) {
             md->best = L.best;
             md->best_i = m;
             md->best_j = sg.cs + L.bt - lane;
@@ -1526,10 +1566,10 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
 
 // ---------------------------------------------------------------------------
 // Column codes -> MSA_NCOPY byte-shifted, padded copies (one thread per output dword):
-// copy c, byte x of pair p = code of column x + c - CPAD + 1 (virt outside [1, n]).
+// copy c, byte x of pair p = code of column x + c - CPAD + 1 (virt outside [1, n]); mask: 7, or 31 for 5-bit codes.
 // ---------------------------------------------------------------------------
 __global__ void stage_codes_kernel(const uint8_t* B, const msa_pair_desc* pairs, int n_pairs, uint8_t* cod,
-                                   long long cod_copy, unsigned virt, int* ticket) {
+                                   long long cod_copy, unsigned virt, unsigned mask, int* ticket) {
   // the run's ticket counters and error word start at 0 (this launch precedes the DP kernel)
   if (ticket && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < MSA_NTICKET) ticket[threadIdx.x] = 0;
   const int p = blockIdx.y;
@@ -1542,7 +1582,7 @@ __global__ void stage_codes_kernel(const uint8_t* B, const msa_pair_desc* pairs,
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       const int col = x + b + c - MSA_CPAD + 1;
-      const unsigned code = (col >= 1 && col <= pd.n) ? (B[pd.b_off + col - 1] & 7u) : virt;
+      const unsigned code = (col >= 1 && col <= pd.n) ? (B[pd.b_off + col - 1] & mask) : virt;
       word |= code << (8 * b);
     }
     *reinterpret_cast<unsigned*>(cod + (size_t)c * cod_copy + pd.cod_off + x) = word;

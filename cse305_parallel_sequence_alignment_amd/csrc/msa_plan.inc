@@ -122,7 +122,8 @@ struct msa_plan {
   int16_t* d_h16 = nullptr;
   // MSA_ALG_NWA: the substitution scores S[8 a + b] (row code a, column code b; 1 / 0 unless MSA_NW_SCORED) and
   // their device table, one 8-byte profile per row code in the launch's space (alloc_buffers)
-  int8_t sub[64] = {};
+  // MSA_ALG_NWA32, MSA_ALG_FIT32 (msa_plan_create_scored32): S[32 a + b], uploaded as it is (1,024 bytes)
+  int8_t sub[1024] = {};
   uint2* d_sub = nullptr;
 
   bool chunked() const { return mode == PM_CHUNKED || mode == PM_BAND_CHUNKED; }
@@ -157,7 +158,8 @@ bool nw_bytes(const msa_plan* P) {
 bool fit_bytes(const msa_plan* P) { return P->d.alg == MSA_NW_FIT && P->d.cells == MSA_CELLS_DIR; }
 
 // ---- step 1: kernel algorithm and end-cell tracking mode --------------------------------------------
-int choose_algorithm(const msa_plan_desc* desc, int& kalg, int& tp) {
+// wide32: a 32 x 32 table over 5-bit codes (msa_plan_create_scored32: MSA_NW_SCORED and MSA_NW_FIT only)
+int choose_algorithm(const msa_plan_desc* desc, bool wide32, int& kalg, int& tp) {
   const int out_mode = desc->cells;
   switch (desc->alg) {
     case MSA_SW_LINEAR:
@@ -191,7 +193,7 @@ int choose_algorithm(const msa_plan_desc* desc, int& kalg, int& tp) {
     case MSA_NW_SCORED:
       // MSA_NW_ALIGN with f = S[row code][column code] (the plan's table: plan_create), direction bytes or the
       // score alone; the table's and the gaps' sizes are check_ranges'
-      kalg = MSA_ALG_NWA;
+      kalg = wide32 ? MSA_ALG_NWA32 : MSA_ALG_NWA;
       if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->gap_extend < 0 ||
           desc->gap_open < desc->gap_extend)
         return MSA_ERR_UNSUPPORTED;
@@ -200,7 +202,7 @@ int choose_algorithm(const msa_plan_desc* desc, int& kalg, int& tp) {
       // MSA_NW_SCORED's cell under a zero top border, with the first maximum of row m as the result: a kernel
       // algorithm of its own (new stripe_kernel instantiations).  No band (|i - j| <= band means nothing when the
       // reference's ends are free), direction bytes or the score alone
-      kalg = MSA_ALG_FIT;
+      kalg = wide32 ? MSA_ALG_FIT32 : MSA_ALG_FIT;
       if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->gap_extend < 0 ||
           desc->gap_open < desc->gap_extend || desc->band != -1)
         return MSA_ERR_UNSUPPORTED;
@@ -245,7 +247,7 @@ msa_kparams base_kparams(const msa_plan_desc* desc, int kalg) {
   if (is_linear(kalg)) kp.gap_open = kp.gap_ext = desc->gap_extend;
   kp.h = desc->gap_open - desc->gap_extend;
   kp.start_type = desc->start_type;
-  kp.band = (kalg == MSA_ALG_NWA) ? desc->band : -1;
+  kp.band = nwg(kalg) ? desc->band : -1;
   kp.single = desc->single ? 1 : 0;
   kp.n_pairs = (int)desc->n_pairs;
   return kp;
@@ -253,12 +255,13 @@ msa_kparams base_kparams(const msa_plan_desc* desc, int kalg) {
 
 // ---- step 2: every pair's sizes and scores are inside what the kernels' number formats hold ---------
 // the largest |score| of a substitution table
-int sub_abs_max(const int8_t* sub) {
+int sub_abs_max(const int8_t* sub, int count) {
   int s = 0;
-  for (int k = 0; k < 64; ++k) s = std::max(s, std::abs((int)sub[k]));
+  for (int k = 0; k < count; ++k) s = std::max(s, std::abs((int)sub[k]));
   return s;
 }
-// `scored`: the table of an MSA_NW_SCORED or MSA_NW_FIT plan (nullptr for every other plan)
+// `scored`: the table of an MSA_NW_SCORED or MSA_NW_FIT plan (nullptr for every other plan), 64 scores or, for the
+// 32-code kernels, 1,024
 int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t* scored) {
   for (int64_t p = 0; p < desc->n_pairs; ++p) {
     const int64_t m = desc->m[p], n = desc->n[p];
@@ -289,7 +292,9 @@ int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t*
       // MSA_NW_FIT (MSA_ALG_FIT, stripe_kernel only, unshifted) adds one source, its top border H(0, j) = 0: within
       // the bound like the corner's 0.  Its paths, steps, left border and -inf are the unbanded MSA_ALG_NWA's, and
       // what it forms beside the cells is a copy of one of them (the row-m maximum): the same inequality holds.
-      const int64_t s = sub_abs_max(scored), g = kp.gap_ext, h = kp.h, G = kp.gap_open;
+      // The 32-code kernels (MSA_ALG_NWA32, MSA_ALG_FIT32: stripe_kernel, unshifted, raw S) differ in where a step's
+      // S comes from, not in what a step is: the same inequality with s over the 1,024 scores.
+      const int64_t s = sub_abs_max(scored, wide(kp.alg) ? 1024 : 64), g = kp.gap_ext, h = kp.h, G = kp.gap_open;
       if ((s + 2 * G + 2 * g) * (m + n + 256) + h >= (int64_t(1) << 28)) return MSA_ERR_UNSUPPORTED;
     }
     if (is_linear(kp.alg)) {
@@ -347,6 +352,8 @@ int band_chunk() {
 // smax: the largest score of an MSA_NW_SCORED plan's table (unused by every other plan)
 PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp, int smax) {
   const int out_mode = desc->cells;
+  // 5-bit codes: stripe_kernel alone has the 32-code lookup -- a single pair (any band: the exact masked launch), a batch
+  if (wide(kalg)) return PM_STRIPE;
   const int band = (kalg == MSA_ALG_NWA) ? desc->band : -1;
   if (desc->single) {
     // flow kernels: one SW-linear pair (8 byte-shifted LDS code rings), or one SW-affine / reference-Gotoh (start
@@ -510,10 +517,11 @@ int size_grid(Launch& l, int per_cu) {
 
 // stripe_kernel's wrap row buffer entries per carried value (batch mode)
 int row_words(const Extents& ex) { return ((ex.P * MSA_K + MSA_ROWOFF + 32) + 15) & ~15; }
-// stripe_kernel's LDS: schedule, link rings, row buffer, and for a single pair the code ring
+// stripe_kernel's LDS: schedule, link rings, row buffer, for a single pair the code ring, and for 5-bit codes the
+// 32 x 32 table
 size_t stripe_lds_bytes(const msa_kparams& kp, int W, int nc) {
   return 4 * (16 + (size_t)kp.sched_cap * 8 + (size_t)(2 * W + 1) * nc * MSA_RING + (size_t)nc * kp.lds_row_words +
-              (kp.single == 1 ? (size_t)4 * (MSA_CRING / 4 + 16) : 0));
+              (kp.single == 1 ? (size_t)4 * (MSA_CRING / 4 + 16) : 0) + (wide(kp.alg) ? 256 : 0));
 }
 
 // PM_STRIPE, PM_SPLIT: stripe_kernel over a batch's pairs (one workgroup walks a pair's whole stripe chain,
@@ -726,7 +734,11 @@ int alloc_buffers(msa_plan& P) {
   if (!P.alloc(&P.d_segs, sizeof(msa_pair_desc) * P.segs.size())) return MSA_ERR_HIP;
   HIPCHK(hipMemcpy(P.d_segs, P.segs.data(), sizeof(msa_pair_desc) * P.segs.size(), hipMemcpyHostToDevice));
   if (!P.alloc(&P.d_res, sizeof(PairResult) * np) || !P.alloc(&P.d_sum, 64)) return MSA_ERR_HIP;
-  if (P.main.kp.alg == MSA_ALG_NWA || P.main.kp.alg == MSA_ALG_FIT) {
+  if (wide(P.main.kp.alg)) {
+    // the 32 x 32 table as it is: stripe_kernel's bytes are the raw S (each workgroup copies it to LDS)
+    if (!P.alloc(&P.d_sub, sizeof(P.sub))) return MSA_ERR_HIP;
+    HIPCHK(hipMemcpy(P.d_sub, P.sub, sizeof(P.sub), hipMemcpyHostToDevice));
+  } else if (P.main.kp.alg == MSA_ALG_NWA || P.main.kp.alg == MSA_ALG_FIT) {
     // the substitution table, one 8-byte profile per row code: band_kernel's bytes are S + 2g + h (its values are
     // shifted by g (i + j); wrapped to a byte as the kernel's own arithmetic did for the 1 / 0 plans), stripe_kernel's S
     const bool bandk = P.mode == PM_BAND || P.mode == PM_BAND_CHUNKED;
@@ -791,9 +803,21 @@ int alloc_buffers(msa_plan& P) {
 }  // namespace
 
 // ---- the C entry points (C linkage by their declarations in msa.h; msa_plan_destroy: msa_capi.hip) ------
-int msa_plan_create(const msa_plan_desc* desc, msa_plan** out) { return msa_plan_create_scored(desc, nullptr, out); }
+static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32, msa_plan** out);
+
+int msa_plan_create(const msa_plan_desc* desc, msa_plan** out) { return plan_create(desc, nullptr, false, out); }
 
 int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_plan** out) {
+  return plan_create(desc, sub, false, out);
+}
+
+int msa_plan_create_scored32(const msa_plan_desc* desc, const int8_t* sub32, msa_plan** out) {
+  if (!sub32) return MSA_ERR_ARG;
+  return plan_create(desc, sub32, true, out);
+}
+
+// sub: 64 scores S[8 a + b] or nullptr, or with wide32 1,024 scores S[32 a + b]
+static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32, msa_plan** out) {
   if (!desc || !out || desc->n_pairs <= 0 || !desc->m || !desc->n || !desc->a_off || !desc->b_off) return MSA_ERR_ARG;
   if (sub && desc->alg != MSA_NW_SCORED && desc->alg != MSA_NW_FIT) return MSA_ERR_UNSUPPORTED;
   int rc = ensure_device();
@@ -805,7 +829,7 @@ int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_pla
   P->d.m = P->d.n = P->d.a_off = P->d.b_off = nullptr;
   P->d.single = desc->single ? 1 : 0;
   int kalg, tp;
-  if ((rc = choose_algorithm(desc, kalg, tp)) != MSA_OK) return rc;
+  if ((rc = choose_algorithm(desc, wide32, kalg, tp)) != MSA_OK) return rc;
   P->tp = tp;
   if (desc->single && desc->n_pairs != 1) return MSA_ERR_ARG;
   // (alg, cells, tracking) combinations no kernel computes: every family takes a subset of the stripe kernel's
@@ -814,14 +838,15 @@ int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_pla
   if (desc->alg == MSA_NW_BANDED && desc->cells == MSA_CELLS_DIR) return MSA_ERR_UNSUPPORTED;
   P->main.kp = base_kparams(desc, kalg);
   P->nc = nc_of(kalg);
-  if (kalg == MSA_ALG_NWA && P->main.kp.h < 0) return MSA_ERR_UNSUPPORTED;
+  if (nwg(kalg) && P->main.kp.h < 0) return MSA_ERR_UNSUPPORTED;
   // the substitution scores of the banded recurrence: MSA_NW_SCORED's table, or its match / mismatch; 1 / 0 for
   // MSA_NW_BANDED and MSA_NW_ALIGN, whatever their description says; MSA_NW_FIT scores as MSA_NW_SCORED does
   const bool scored = desc->alg == MSA_NW_SCORED || desc->alg == MSA_NW_FIT;
   int smax = 0;
   if (scored && !sub && (desc->match < -128 || desc->match > 127 || desc->mismatch < -128 || desc->mismatch > 127))
     return MSA_ERR_UNSUPPORTED;
-  for (int k = 0; k < 64; ++k) {
+  if (wide32) std::memcpy(P->sub, sub, sizeof(P->sub));
+  for (int k = 0; k < 64 && !wide32; ++k) {
     const bool diag = k / 8 == k % 8;
     P->sub[k] = sub ? sub[k] : (int8_t)(scored ? (diag ? desc->match : desc->mismatch) : (diag ? 1 : 0));
     smax = k ? std::max(smax, (int)P->sub[k]) : (int)P->sub[k];

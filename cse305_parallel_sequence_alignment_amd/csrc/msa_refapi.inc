@@ -152,9 +152,10 @@ class DeviceCall {
     return MSA_OK;
   }
   // a plan of this call's own (sub: msa_plan_create_scored's table, or nullptr), destroyed with the call
-  int create_plan(const msa_plan_desc& d, const int8_t* sub, msa_plan** out) {
+  // wide32: sub is a 32 x 32 table (msa_plan_create_scored32)
+  int create_plan(const msa_plan_desc& d, const int8_t* sub, msa_plan** out, bool wide32 = false) {
     if (plans_.n == kMaxPlans) return MSA_ERR_NOMEM;
-    const int rc = msa_plan_create_scored(&d, sub, out);
+    const int rc = wide32 ? msa_plan_create_scored32(&d, sub, out) : msa_plan_create_scored(&d, sub, out);
     if (rc == MSA_OK) plans_.v[plans_.n++] = *out;
     return rc;
   }
@@ -1154,7 +1155,7 @@ struct AlignSpec {
   int alg_walk, alg_score;  // the plan with direction bytes, and the value plan of the same recurrence without
   int match, mismatch, start_type, track_end;  // the plan description's
   bool scored;              // tab is msa_plan_create_scored's 8 x 8 table (else match / mismatch score)
-  int8_t tab[64];
+  int8_t tab[1024];         // (wide: msa_plan_create_scored32's 32 x 32 table)
   SymbolMap symbols;        // first-seen with the kind's code limit, or the caller's alphabet as a fixed map
   GapRule gaps;
   bool banded;              // a band is accepted
@@ -1163,6 +1164,7 @@ struct AlignSpec {
   int (*walk)(msa_plan*, int64_t, const uint8_t*, uint8_t*, int64_t, int64_t*, void*);
   Border border;            // how the walk's ops become the whole alignment
   bool walk_for_beg;        // the walk is wanted for the start cell too, not only for a CIGAR
+  bool wide = false;        // more than 8 symbols: 5-bit codes, tab is 32 x 32
 };
 
 // Smith-Waterman: code 7 is the kernels' out-of-matrix sentinel, so 7 codes
@@ -1176,22 +1178,26 @@ AlignSpec spec_nw(const char* preset) {
                    GAPS_GLOBAL, true, FOOT_BAND, msa_plan_traceback_nw, BORDER_GLOBAL, false};
 }
 // global under the caller's alphabet -- a symbol's code is its index -- and its n_sym x n_sym matrix;
-// status MSA_ERR_ARG for a NULL alphabet or matrix, n_sym outside 1..8 or a duplicate symbol
-AlignSpec spec_scored(const char* alphabet, size_t n_sym, const int8_t* sub) {
+// status MSA_ERR_ARG for a NULL alphabet or matrix, n_sym outside 1..max_sym or a duplicate symbol.  max_sym: 8, or 32
+// (the *32 entries); up to 8 symbols make the same spec under either, 9..32 a wide one
+AlignSpec spec_scored(const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym = 8) {
   AlignSpec s = spec_nw("");
   s.alg_walk = s.alg_score = MSA_NW_SCORED;
   s.scored = true;
-  if (!alphabet || !sub || n_sym < 1 || n_sym > 8) s.status = MSA_ERR_ARG;
+  if (!alphabet || !sub || n_sym < 1 || n_sym > max_sym) s.status = MSA_ERR_ARG;
+  s.wide = s.status == MSA_OK && n_sym > 8;
+  if (s.wide) s.symbols = SymbolMap(32);
+  const size_t stride = s.wide ? 32 : 8;
   for (size_t a = 0; s.status == MSA_OK && a < n_sym; ++a) {
     if (!s.symbols.add(alphabet[a])) s.status = MSA_ERR_ARG;
-    for (size_t b = 0; b < n_sym; ++b) s.tab[8 * a + b] = sub[n_sym * a + b];
+    for (size_t b = 0; b < n_sym; ++b) s.tab[stride * a + b] = sub[n_sym * a + b];
   }
   s.symbols.fix();
   return s;
 }
 // ... and with free ends on B: all of A in a substring of B
-AlignSpec spec_fit(const char* alphabet, size_t n_sym, const int8_t* sub) {
-  AlignSpec s = spec_scored(alphabet, n_sym, sub);
+AlignSpec spec_fit(const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym = 8) {
+  AlignSpec s = spec_scored(alphabet, n_sym, sub, max_sym);
   s.alg_walk = s.alg_score = MSA_NW_FIT;
   s.banded = false;
   s.border = BORDER_FIT;
@@ -1286,7 +1292,7 @@ int align_range(const AlignSpec& spec, int single, const GapBand& gb, bool want_
   d.a_off = ao.data();
   d.b_off = bo.data();
   msa_plan* P = nullptr;
-  if ((rc = dc.create_plan(d, spec.scored ? spec.tab : nullptr, &P)) != MSA_OK) return rc;
+  if ((rc = dc.create_plan(d, spec.scored ? spec.tab : nullptr, &P, spec.wide)) != MSA_OK) return rc;
   void *dDir = nullptr, *dOps = nullptr, *dOff = nullptr, *dInfo = nullptr;
   const hipStream_t st = dc.stream();
   if (want_tb) {
@@ -1448,6 +1454,29 @@ int msa_fit_align(const char* A0, size_t m, const char* B0, size_t n, const char
   return rc;
 }
 
+int msa_nw_align_scored32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                          const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band, int32_t* score,
+                          char* cigar, size_t cigar_cap) {
+  const OnePairIn one(A0, m, B0, n);
+  int64_t coff[2];
+  const AlignOut out{score, PairOut(), PairOut(), PairOut(), cigar, cigar_cap, coff};
+  return align_pairs(spec_scored(alphabet, n_sym, sub, 32), 1, one.in, kPairLimit, gap_open, gap_extend, band, out);
+}
+
+int msa_fit_align32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                    const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_j,
+                    int64_t* end_j, char* cigar, size_t cigar_cap) {
+  const OnePairIn one(A0, m, B0, n);
+  int64_t coff[2], be[2] = {-1, -1};
+  const AlignOut out{score, PairOut(), PairOut(), PairOut(be), cigar, cigar_cap, coff};
+  const int rc = align_pairs(spec_fit(alphabet, n_sym, sub, 32), 1, one.in, kPairLimit, gap_open, gap_extend, -1, out);
+  if (rc == MSA_OK || rc == MSA_ERR_CAPACITY) {
+    if (beg_j) *beg_j = be[0];
+    if (end_j) *end_j = be[1];
+  }
+  return rc;
+}
+
 int msa_sw_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
                        const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n, int32_t match,
                        int32_t mismatch, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_ij,
@@ -1485,6 +1514,27 @@ int msa_fit_align_batch(const char* A, size_t a_len, const char* B, size_t b_len
   const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
   const AlignOut out{score, PairOut(), PairOut(), PairOut(beg_end), cigars, cigar_cap, cigar_off};
   return align_pairs(spec_fit(alphabet, n_sym, sub), 0, in, kPairLimit, gap_open, gap_extend, -1, out);
+}
+
+int msa_nw_align_batch_scored32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                                const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                                const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                                int32_t gap_extend, int64_t band, int32_t* score, char* cigars, size_t cigar_cap,
+                                int64_t* cigar_off) {
+  const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  const AlignOut out{score, PairOut(), PairOut(), PairOut(), cigars, cigar_cap, cigar_off};
+  return align_pairs(spec_scored(alphabet, n_sym, sub, 32), 0, in, kPairLimit, gap_open, gap_extend, band, out);
+}
+
+int msa_fit_align_batch32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                          const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                          const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                          int32_t gap_extend, int32_t* score, int64_t* beg_end, char* cigars, size_t cigar_cap,
+                          int64_t* cigar_off) {
+  if (!beg_end) return MSA_ERR_ARG;
+  const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  const AlignOut out{score, PairOut(), PairOut(), PairOut(beg_end), cigars, cigar_cap, cigar_off};
+  return align_pairs(spec_fit(alphabet, n_sym, sub, 32), 0, in, kPairLimit, gap_open, gap_extend, -1, out);
 }
 
 }  // extern "C"

@@ -25,6 +25,9 @@ enum msa_alg {
   MSA_ALG_FIT = 8,   // MSA_ALG_NWA's cell (no band) under a zero top border, H(0, j) = 0: all of A against a
                      // substring of B (MSA_NW_FIT plans).  The lane of row m keeps the first maximum of
                      // H(m, 1..n): the stripe meta's best / best_i = m / best_j
+  MSA_ALG_NWA32 = 9,   // MSA_ALG_NWA over 5-bit codes: scores from the plan's 32 x 32 table (KArgs::sub, raw int8 S),
+                       // the lane's 32-byte row of it in eight registers (msa_plan_create_scored32, stripe_kernel only)
+  MSA_ALG_FIT32 = 10,  // MSA_ALG_FIT over 5-bit codes, likewise
 };
 
 // Per-cell outputs.
@@ -35,7 +38,7 @@ enum msa_out {
   MSA_OUT_TAB = 3,   // three int32 planes T1,T2,T3 per cell (skewed stripe layout)
 };
 
-// One pair of sequences inside a launch.  Codes are uint8 in [0,8).
+// One pair of sequences inside a launch.  Codes are uint8 in [0,8) ([0,32): MSA_ALG_NWA32, MSA_ALG_FIT32).
 typedef struct msa_pair_desc {
   int64_t a_off;       // offset of row codes (A[0] = row 1) in the A code array
   int64_t b_off;       // offset of column codes (B[0] = column 1) in the B code array

@@ -53,6 +53,8 @@ class Plan:
                  gap_extend=1, start_type=-1, band=-1, track_end=False, single=None, sub=None):
         """``sub`` (NW_SCORED and NW_FIT only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code a against
         column code b (msa_plan_create_scored); None scores ``match`` on the diagonal and ``mismatch`` elsewhere.
+        A 32 x 32 ``sub`` makes a plan over 5-bit codes (msa_plan_create_scored32: inputs in [0, 32), always the
+        stripe kernel); any other shape is a ValueError.
         An NW_FIT plan (all of A against a substring of B: ``band`` -1, CELLS_DIR or CELLS_NONE) reports in
         ``results()`` the score and ``end = (m, end_j)``, the first column of row m's maximum; ``traceback_nw`` and
         ``traceback_batch`` walk from there."""
@@ -74,11 +76,13 @@ class Plan:
             LB.check(L.msa_plan_create(C.byref(d), C.byref(self._h)), "msa_plan_create")
         else:
             tab = np.asarray(sub)
-            if tab.shape != (8, 8) or (tab != tab.astype(np.int8)).any():
-                raise ValueError("sub must be 8 x 8 scores in [-128, 127]")
+            if tab.shape not in ((8, 8), (32, 32)) or (tab != tab.astype(np.int8)).any():
+                raise ValueError("sub must be 8 x 8 or 32 x 32 scores in [-128, 127]")
+            wide = tab.shape == (32, 32)
             tab = np.ascontiguousarray(tab, dtype=np.int8)
-            LB.check(L.msa_plan_create_scored(C.byref(d), tab.ctypes.data_as(C.c_void_p), C.byref(self._h)),
-                     "msa_plan_create_scored")
+            create, what = (L.msa_plan_create_scored32, "msa_plan_create_scored32") if wide else \
+                (L.msa_plan_create_scored, "msa_plan_create_scored")
+            LB.check(create(C.byref(d), tab.ctypes.data_as(C.c_void_p), C.byref(self._h)), what)
         self.band = band
         self.single = bool(single)
         e = C.c_int64()
@@ -163,12 +167,13 @@ class Plan:
 
     def format_info(self) -> dict:
         """The number formats the plan chose (msa_plan_format_info): values ("int32", "packed16" couples or
-        "tagged4" Gotoh), end-cell tracking ("none", "select" or the packed "key"), and whether the chunks of a
-        chunked banded plan write int16 cells."""
+        "tagged4" Gotoh), end-cell tracking ("none", "select" or the packed "key"), whether the chunks of a
+        chunked banded plan write int16 cells, and the symbol codes the plan takes (8, or 32 for a 32 x 32 table)."""
         v = (C.c_int32 * 4)()
         LB.check(LB.lib().msa_plan_format_info(self._h, v), "msa_plan_format_info")
         return dict(values={0: "int32", 1: "packed16", 2: "tagged4"}[v[0]],
-                    tracking={0: "none", 1: "select", 2: "key"}[v[1]], int16_cells=int(v[2]))
+                    tracking={0: "none", 1: "select", 2: "key"}[v[1]], int16_cells=int(v[2]),
+                    codes=32 if v[3] else 8)
 
     def clear_error(self, stream=None) -> None:
         LB.check(LB.lib().msa_plan_clear_error(self._h, _stream_ptr(stream)), "msa_plan_clear_error")

@@ -46,6 +46,12 @@
  *                        best, with the reference span and the CIGAR (build extension: MSA_NW_FIT plans --
  *                        a zero top border, the first maximum of row m found inside the fill kernel, and
  *                        the two global walks started at that cell)
+ *   msa_plan_create_scored32, msa_nw_align_scored32, msa_nw_align_batch_scored32, msa_fit_align32,
+ *   msa_fit_align_batch32
+ *                        MSA_NW_SCORED and MSA_NW_FIT over alphabets of up to 32 symbols (proteins, IUPAC DNA):
+ *                        5-bit codes under a 32 x 32 int8 substitution table (build extension: stripe kernel
+ *                        instantiations of their own, whose lanes hold a 32-byte row of the table and look four
+ *                        scores up with seven v_perm_b32)
  */
 #ifndef MSA_H
 #define MSA_H
@@ -61,7 +67,7 @@ extern "C" {
 typedef enum msa_status {
   MSA_OK = 0,
   MSA_ERR_ARG = -1,          /* bad argument (size 0 where the path needs >0, NULL, ...) */
-  MSA_ERR_ALPHABET = -2,     /* more than 8 distinct symbols in a pair */
+  MSA_ERR_ALPHABET = -2,     /* more than 8 distinct symbols in a pair, or a symbol outside the caller's alphabet */
   MSA_ERR_HIP = -3,          /* a HIP runtime call failed */
   MSA_ERR_NODEV = -4,        /* no gfx950 device visible */
   MSA_ERR_UNSUPPORTED = -5,  /* e.g. non-integral g/h (the GPU path is exact int32) */
@@ -219,7 +225,7 @@ int msa_partition_tables(const int32_t* T1, const int32_t* T2, const int32_t* T3
  * in chunks with the exact launch as fallback).  Running the plan stages the
  * column codes, launches that family and a tiny per-pair reduction on
  * `stream` (no allocation, no host sync inside msa_plan_run).  Inputs are
- * uint8 codes in [0,8) already in device memory (see msa_encode_pair for the
+ * uint8 codes in [0,8) ([0,32) for msa_plan_create_scored32's plans) already in device memory (see msa_encode_pair for the
  * host-side code map); the
  * Smith-Waterman algorithms reserve code 7 (out-of-matrix sentinel), so their
  * inputs use codes 0..6. */
@@ -283,6 +289,14 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** plan);
  * same way and under the same inequality (its zero top border is within the bound); it is MSA_ERR_UNSUPPORTED
  * with any band but -1 and with cells other than MSA_CELLS_DIR / MSA_CELLS_NONE. */
 int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_plan** plan);
+/* MSA_NW_SCORED and MSA_NW_FIT over 5-bit codes: sub32 = 1,024 scores, row-major sub32[32*a + b] = the score of A's
+ * code a against B's code b.  The inputs of msa_plan_run are codes in [0, 32).  desc->alg must be MSA_NW_SCORED or
+ * MSA_NW_FIT (anything else: MSA_ERR_UNSUPPORTED); sub32 == NULL is MSA_ERR_ARG.  Cells, band and gap rules, the
+ * value-range inequality (s = the largest |score| of the 1,024) and their errors are msa_plan_create_scored's.
+ * Such a plan always launches the stripe kernel (msa_plan_launch_info mode 0): one pair, a batch, any band (a banded
+ * single pair runs the exact masked stripe launch).  msa_plan_format_info reports it in its fourth word;
+ * msa_plan_traceback_nw and msa_plan_traceback_batch walk its direction bytes as they walk an 8-code plan's. */
+int msa_plan_create_scored32(const msa_plan_desc* desc, const int8_t* sub32, msa_plan** plan);
 void msa_plan_destroy(msa_plan* plan);
 /* Elements (int32 for H/TAB planes, bytes for DIR) the per-cell output needs. */
 int msa_plan_cells_size(const msa_plan* plan, int64_t* elems);
@@ -314,7 +328,7 @@ int msa_plan_launch_info(const msa_plan* plan, int32_t* out8);
  * int16 couples (two score-only SW-linear pairs per lane), 2 the x4 tagged values of the reference's Gotoh
  * (start type -1); end-cell tracking: 0 none, 1 compare-select on (value, position), 2 the first maximum's
  * step packed with the value into one int; 1 if the chunks of a chunked banded plan write int16 cells;
- * 0 (reserved)}. */
+ * 1 for a plan over 5-bit codes (msa_plan_create_scored32), 0 for every other plan}. */
 int msa_plan_format_info(const msa_plan* plan, int32_t* out4);
 /* The sticky error word (0 = no error; else the kernel site code), synchronizes. */
 int msa_plan_error(msa_plan* plan, int* code, void* stream);
@@ -525,6 +539,31 @@ int msa_fit_align_batch(const char* A, size_t a_len, const char* B, size_t b_len
                         const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
                         int32_t gap_extend, int32_t* score, int64_t* beg_end /* 2 n_pairs: {beg_j, end_j} */,
                         char* cigars, size_t cigar_cap, int64_t* cigar_off);
+
+/* The four matrix-scored entries above for alphabets of up to 32 symbols (proteins with B Z X *, IUPAC DNA): the
+ * signatures of their 8-symbol twins, 1 <= n_sym <= 32, sub = n_sym x n_sym.  With n_sym <= 8 a call builds exactly
+ * the plans its twin builds: the same kernels, the same results.  With 9..32 symbols the codes are 5 bits wide and
+ * the plans are msa_plan_create_scored32's (always the stripe kernel; a banded single pair runs its exact masked
+ * launch).  n_sym 0 or 33, a duplicate symbol, or a NULL alphabet or sub: MSA_ERR_ARG.  Then, in this order: the other
+ * argument errors, the gap rule (MSA_ERR_UNSUPPORTED), the band rule (MSA_ERR_ARG), a symbol of A or B outside the
+ * alphabet (MSA_ERR_ALPHABET), and only then the device.  Admission, chunks of pairs, the border gap, the CIGAR
+ * format and MSA_ERR_CAPACITY are the twins'.  The 8-symbol entries keep their contract (n_sym == 9: MSA_ERR_ARG). */
+int msa_nw_align_scored32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                          const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band, int32_t* score,
+                          char* cigar, size_t cigar_cap);
+int msa_nw_align_batch_scored32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                                const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                                const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                                int32_t gap_extend, int64_t band, int32_t* score, char* cigars, size_t cigar_cap,
+                                int64_t* cigar_off);
+int msa_fit_align32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                    const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_j,
+                    int64_t* end_j, char* cigar, size_t cigar_cap);
+int msa_fit_align_batch32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                          const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                          const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                          int32_t gap_extend, int32_t* score, int64_t* beg_end /* 2 n_pairs: {beg_j, end_j} */,
+                          char* cigars, size_t cigar_cap, int64_t* cigar_off);
 
 #ifdef __cplusplus
 }
