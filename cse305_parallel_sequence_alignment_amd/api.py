@@ -264,17 +264,49 @@ def partial_tables(A, B, m, n, g, h, start_type, end_type):
     return T, R
 
 
-def sw_align(A, B, match=1, mismatch=0, gap_open=1, gap_extend=1, traceback=True):
-    """Smith-Waterman local alignment (build extension) -> dict(score, end, beg, cigar)."""
+def _sw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols):
+    """The scoring of sw_align / sw_align_batch: None for today's match / mismatch call (``max_symbols`` 8 and neither
+    ``alphabet`` nor ``matrix``), else _nw_scoring's (alphabet bytes, int8 matrix) under its rules and ValueErrors.
+    The local kernels keep their highest code as the out-of-matrix sentinel, so ``max_symbols=32`` with ``match`` /
+    ``mismatch`` takes at most 31 distinct symbols in ``seqs`` (more: MsaError with the ALPHABET status)."""
+    if max_symbols not in (8, 32):
+        raise ValueError("max_symbols must be 8 or 32")
+    if alphabet is None and matrix is None:
+        if max_symbols == 8:
+            return None
+        if len(set(b"".join(seqs))) > 31:
+            raise LB.MsaError(-2, "sw_align")
+        match = 1 if match is None else match
+    return _nw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols)
+
+
+def sw_align(A, B, match=None, mismatch=None, gap_open=1, gap_extend=1, traceback=True, alphabet=None, matrix=None,
+             max_symbols=8):
+    """Smith-Waterman local alignment (build extension) -> dict(score, end, beg, cigar).
+
+    ``match`` / ``mismatch`` (None: 1 / 0) over the symbols of A and B, at most 7 (msa_sw_align).  Or ``alphabet``
+    (up to 7 distinct bytes) with ``matrix``, len(alphabet) x len(alphabet) scores in [-128, 127], ``matrix[a][b]`` =
+    alphabet[a] in A against alphabet[b] in B (msa_sw_align_scored); giving ``match`` or ``mismatch`` with it is a
+    ValueError, as for nw_align.  ``max_symbols=32`` (msa_sw_align_scored32; any value but 8 or 32 is a ValueError):
+    ``alphabet`` may hold up to 31 bytes -- proteins, IUPAC DNA --, and ``match`` / ``mismatch`` score the symbols of
+    A and B themselves, at most 31.  The matrix-scored calls run the stripe kernel whatever the pair's size."""
     A, B = _buf(A), _buf(B)
+    scoring = _sw_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
     sc = C.c_int32()
     ei, ej, bi, bj = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
     cap = 4 * (len(A) + len(B)) + 16
     cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(LB.lib().msa_sw_align(A, len(A), B, len(B), match, mismatch, gap_open, gap_extend, C.byref(sc),
-                                   C.byref(ei), C.byref(ej), C.byref(bi) if traceback else None,
-                                   C.byref(bj) if traceback else None, cig, cap if traceback else 0),
-             "msa_sw_align")
+    outs = (C.byref(sc), C.byref(ei), C.byref(ej), C.byref(bi) if traceback else None,
+            C.byref(bj) if traceback else None, cig, cap if traceback else 0)
+    if scoring is None:
+        LB.check(LB.lib().msa_sw_align(A, len(A), B, len(B), 1 if match is None else match,
+                                       0 if mismatch is None else mismatch, gap_open, gap_extend, *outs),
+                 "msa_sw_align")
+    else:
+        alpha, S = scoring
+        name = "msa_sw_align_scored" if max_symbols == 8 else "msa_sw_align_scored32"
+        LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p),
+                                         gap_open, gap_extend, *outs), name)
     r = dict(score=sc.value, end=(ei.value, ej.value))
     if traceback:
         r["beg"] = (bi.value, bj.value)
@@ -392,15 +424,21 @@ def _i64p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def sw_align_batch(As, Bs, match=1, mismatch=0, gap_open=1, gap_extend=1, traceback=True):
+def sw_align_batch(As, Bs, match=None, mismatch=None, gap_open=1, gap_extend=1, traceback=True, alphabet=None,
+                   matrix=None, max_symbols=8):
     """A batch of Smith-Waterman local alignments (msa_sw_align_batch) -> a list of sw_align()'s dicts.
 
     ``Bs``: a list as long as ``As``, or one bytes object every A is aligned against (uploaded once).  One symbol
     map serves the whole call: at most 7 distinct symbols in all of As and Bs together.  The pairs run as batch
-    plans (one fill and one walk launch per chunk of pairs that fits a quarter of the device budget)."""
+    plans (one fill and one walk launch per chunk of pairs that fits a quarter of the device budget).
+    ``match`` / ``mismatch`` / ``alphabet`` / ``matrix`` / ``max_symbols`` as for sw_align (msa_sw_align_batch_scored,
+    msa_sw_align_batch_scored32), over one alphabet for the whole call: up to 7 symbols, or 31."""
+    if max_symbols not in (8, 32):
+        raise ValueError("max_symbols must be 8 or 32")
     if len(As) == 0:
         return []
     A, B, a_off, m, b_off, n = _batch_in(As, Bs)
+    scoring = _sw_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
     k = len(m)
     sc = np.zeros(k, dtype=np.int32)
     end = np.zeros((k, 2), dtype=np.int64)
@@ -408,10 +446,18 @@ def sw_align_batch(As, Bs, match=1, mismatch=0, gap_open=1, gap_extend=1, traceb
     coff = np.zeros(k + 1, dtype=np.int64)
     cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
     cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(LB.lib().msa_sw_align_batch(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
-                                         match, mismatch, gap_open, gap_extend, sc.ctypes.data_as(C.c_void_p),
-                                         _i64p(end), _i64p(beg) if traceback else None, cig, cap,
-                                         _i64p(coff) if traceback else None), "msa_sw_align_batch")
+    outs = (sc.ctypes.data_as(C.c_void_p), _i64p(end), _i64p(beg) if traceback else None, cig, cap,
+            _i64p(coff) if traceback else None)
+    if scoring is None:
+        LB.check(LB.lib().msa_sw_align_batch(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
+                                             1 if match is None else match, 0 if mismatch is None else mismatch,
+                                             gap_open, gap_extend, *outs), "msa_sw_align_batch")
+    else:
+        alpha, S = scoring
+        name = "msa_sw_align_batch_scored" if max_symbols == 8 else "msa_sw_align_batch_scored32"
+        LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
+                                         alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend, *outs),
+                 name)
     out = []
     for p in range(k):
         r = dict(score=int(sc[p]), end=(int(end[p, 0]), int(end[p, 1])))

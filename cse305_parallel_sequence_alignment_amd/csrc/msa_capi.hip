@@ -352,6 +352,7 @@ int nc_of(int alg) {
   switch (alg) {
     case MSA_ALG_SWL: case MSA_ALG_SWL0: case MSA_ALG_SWLP: return 1;
     case MSA_ALG_SWA: case MSA_ALG_NWA: case MSA_ALG_REF1: case MSA_ALG_FIT: case MSA_ALG_NWA32: case MSA_ALG_FIT32:
+    case MSA_ALG_SWS: case MSA_ALG_SWS32:
       return 2;
     default: return 3;
   }
@@ -478,6 +479,18 @@ kfn_t pick_kernel(int alg, int out, int tp, bool sgl) {
     case MSA_ALG_FIT32:
       if (out == MSA_OUT_NONE) return kf<MSA_ALG_FIT32, MSA_OUT_NONE, 0>(sgl);
       if (out == MSA_OUT_DIR) return kf<MSA_ALG_FIT32, MSA_OUT_DIR, 0>(sgl);
+      break;
+    // MSA_SW_SCORED: the SW-affine cell under the plan's table.  Such a plan always tracks its end cell, so
+    // compare-select (1) or the packed key (2) only; the MSA_ALG_SWA kernels' code is unchanged
+    case MSA_ALG_SWS:
+      if (tp != 1 && tp != 2) break;
+      if (out == MSA_OUT_NONE) return tp == 2 ? kf<MSA_ALG_SWS, MSA_OUT_NONE, 2>(sgl) : kf<MSA_ALG_SWS, MSA_OUT_NONE, 1>(sgl);
+      if (out == MSA_OUT_DIR) return tp == 2 ? kf<MSA_ALG_SWS, MSA_OUT_DIR, 2>(sgl) : kf<MSA_ALG_SWS, MSA_OUT_DIR, 1>(sgl);
+      break;
+    case MSA_ALG_SWS32:
+      if (tp != 1 && tp != 2) break;
+      if (out == MSA_OUT_NONE) return tp == 2 ? kf<MSA_ALG_SWS32, MSA_OUT_NONE, 2>(sgl) : kf<MSA_ALG_SWS32, MSA_OUT_NONE, 1>(sgl);
+      if (out == MSA_OUT_DIR) return tp == 2 ? kf<MSA_ALG_SWS32, MSA_OUT_DIR, 2>(sgl) : kf<MSA_ALG_SWS32, MSA_OUT_DIR, 1>(sgl);
       break;
   }
 #undef K3
@@ -650,7 +663,9 @@ int msa_plan_run(msa_plan* P, const uint8_t* dA, const uint8_t* dB, void* c0, vo
   a.ps_shift = __builtin_ctz((unsigned)P->ps);
   a.nblk = P->nblk;
   {
-    const unsigned virt = (is_linear(P->main.kp.alg) || P->main.kp.alg == MSA_ALG_SWA) ? MSA_VIRT_CODE : 0u;
+    // (the SW kernels' virtual code: 7, or 31 over 5-bit codes)
+    const unsigned virt = (is_linear(P->main.kp.alg) || swaf(P->main.kp.alg))
+                              ? (wide(P->main.kp.alg) ? MSA_VIRT_CODE32 : MSA_VIRT_CODE) : 0u;
     // about two output words per thread for one long pair (64 x 256 threads took 22 us for
     // C3's 97k columns, 24 dependent rounds each), at least 64 workgroups per segment
     const int64_t words = MSA_NCOPY * (P->cod_copy / 4) / std::max<int64_t>(1, (int64_t)P->segs.size());
@@ -703,7 +718,7 @@ int msa_plan_run(msa_plan* P, const uint8_t* dA, const uint8_t* dB, void* c0, vo
     return MSA_OK;
   }
   // (2: a fit plan's pair result is the first maximum of row m, from the meta of the stripe that holds it)
-  const int sw = (is_linear(P->main.kp.alg) || P->main.kp.alg == MSA_ALG_SWA) ? 1 : (fitk(P->main.kp.alg) ? 2 : 0);
+  const int sw = (is_linear(P->main.kp.alg) || swaf(P->main.kp.alg)) ? 1 : (fitk(P->main.kp.alg) ? 2 : 0);
   const int np = (int)P->d.n_pairs;
   hipLaunchKernelGGL(reduce_pairs_kernel, dim3(np), dim3(64), 0, st, P->d_pairs, P->d_meta, np, sw,
                      P->d_res);
@@ -829,7 +844,8 @@ int msa_plan_traceback(msa_plan* P, int64_t pair, const uint8_t* dDir, uint8_t* 
                        int64_t* d_info, void* stream) {
   if (!P || !dDir || !d_ops || !d_info || ops_cap < 0 || pair < 0 || pair >= P->d.n_pairs) return MSA_ERR_ARG;
   // the walk starts at the fill's end cell: plans without track_end have none
-  if (P->main.kp.alg != MSA_ALG_SWA || P->d.cells != MSA_CELLS_DIR || !P->d.track_end) return MSA_ERR_UNSUPPORTED;
+  // (an MSA_SW_SCORED plan always has one: plan_create sets its track_end)
+  if (!swaf(P->main.kp.alg) || P->d.cells != MSA_CELLS_DIR || !P->d.track_end) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   P->note_stream(st);
   hipLaunchKernelGGL((P->R == 2 ? traceback_kernel<TB_SW, 2> : traceback_kernel<TB_SW>), dim3(1), dim3(384), 0, st, dDir, P->d_pairs, P->d_meta,
@@ -882,8 +898,8 @@ int msa_plan_traceback_batch(msa_plan* P, const uint8_t* dDir, uint8_t* d_ops, c
   if (P->mode == PM_FLOW || P->R == 2 || P->fused_reduce) return MSA_ERR_UNSUPPORTED;
   const bool nw = nw_bytes(P);
   // (the SW walk starts at the fill's end cell: plans without track_end have none)
-  const bool sw = P->d.alg == MSA_SW_AFFINE && P->main.kp.alg == MSA_ALG_SWA && P->d.cells == MSA_CELLS_DIR &&
-                  P->d.track_end;
+  const bool sw = ((P->d.alg == MSA_SW_AFFINE && P->main.kp.alg == MSA_ALG_SWA) || P->d.alg == MSA_SW_SCORED) &&
+                  P->d.cells == MSA_CELLS_DIR && P->d.track_end;
   const bool fit = fit_bytes(P);  // (the global walk from each pair's end cell (m, end_j))
   if (!nw && !sw && !fit) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;

@@ -70,6 +70,7 @@
 #define MSA_GOFF 128
 #define MSA_NEG (-(1 << 30))
 #define MSA_VIRT_CODE 7u     // SW: column code outside [1, n] (real symbols use codes 0..6)
+#define MSA_VIRT_CODE32 31u  // ... over 5-bit codes (MSA_ALG_SWS32: real symbols use codes 0..30)
 #define MSA_NTICKET 128      // run tickets (ints): [0] stripe_kernel, [4..11] flow item chunks,
 #define MSA_TK_ARRIVE 32     // flow kernel: arrival order (pass-1 / pass-2 role), own 128-B line
 #define MSA_TK_BLOCK 64      // flow kernel: pass-2 blocks, own 128-B line
@@ -95,8 +96,14 @@ template <> struct Tr<MSA_ALG_NWA> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_FIT> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_NWA32> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_FIT32> { static constexpr int NC = 2; };
+template <> struct Tr<MSA_ALG_SWS> { static constexpr int NC = 2; };
+template <> struct Tr<MSA_ALG_SWS32> { static constexpr int NC = 2; };
 // 5-bit codes: the lane's profile is a 32-byte row of the plan's 32 x 32 table (score4_wide)
-constexpr bool wide(int alg) { return alg == MSA_ALG_NWA32 || alg == MSA_ALG_FIT32; }
+constexpr bool wide(int alg) { return alg == MSA_ALG_NWA32 || alg == MSA_ALG_FIT32 || alg == MSA_ALG_SWS32; }
+// the SW-affine cell with scores from the plan's table (swsc), with those or match / mismatch (swaf): the zero floor,
+// zero borders, best tracking and the virtual columns are the same
+constexpr bool swsc(int alg) { return alg == MSA_ALG_SWS || alg == MSA_ALG_SWS32; }
+constexpr bool swaf(int alg) { return alg == MSA_ALG_SWA || swsc(alg); }
 // the banded Gotoh cell under the global borders (nwg), the same cell under the fit alignment's zero top border
 // (fitk), either (nwa) -- over 3-bit or 5-bit codes
 constexpr bool nwg(int alg) { return alg == MSA_ALG_NWA || alg == MSA_ALG_NWA32; }
@@ -202,7 +209,8 @@ struct KArgs {
   unsigned long long* best_key;
   // MSA_ALG_NWA, MSA_ALG_FIT: the plan's substitution table, one 8-byte profile per row code (byte b of entry a = the
   // score of row code a against column code b, in the launch's own space: msa_plan.inc, sub_table).
-  // MSA_ALG_NWA32, MSA_ALG_FIT32: 1,024 raw scores, byte 32 a + b
+  // MSA_ALG_NWA32, MSA_ALG_FIT32: 1,024 raw scores, byte 32 a + b.
+  // MSA_ALG_SWS / MSA_ALG_SWS32: the same two layouts, the virtual code's column (7 / 31) holding MSA_VIRT_SCORE
   const uint2* sub;
 };
 #ifndef MSA_H16_PAIRED
@@ -220,7 +228,7 @@ __device__ __forceinline__ void border_top(const msa_kparams& kp, int c, int (&v
     if constexpr (pk16(ALG)) v[0] = pk2(v[0]);
     v[1] = MSA_NEG;
     v[2] = MSA_NEG;
-  } else if constexpr (ALG == MSA_ALG_SWA) {
+  } else if constexpr (swaf(ALG)) {
     v[0] = c >= 0 ? 0 : MSA_NEG;  // H
     v[1] = MSA_NEG;               // F
     v[2] = MSA_NEG;
@@ -284,7 +292,7 @@ __device__ __forceinline__ void border_left(const msa_kparams& kp, int i, int (&
     v[0] = pk16(ALG) ? pk2(kp.gap_open * i) : kp.gap_open * i;  // G(i,0) = H(i,0) + g*i
     v[1] = MSA_NEG;
     v[2] = MSA_NEG;
-  } else if constexpr (ALG == MSA_ALG_SWA) {
+  } else if constexpr (swaf(ALG)) {
     v[0] = 0;        // H
     v[1] = MSA_NEG;  // E
     v[2] = MSA_NEG;  // F
@@ -372,7 +380,7 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
     nS[0] = imax3(L.U[0] + s, up, L.S[0]);
     asm("" : "+v"(nS[0]));
     L.U[0] = up;
-  } else if constexpr (ALG == MSA_ALG_SWA) {
+  } else if constexpr (swaf(ALG)) {
     const int upH = dpp_shr1(in[0], L.S[0]);
     const int upF = dpp_shr1(in[1], L.S[2]);
     const int f = imax(upF - kp.gap_ext, upH - kp.gap_open);
@@ -475,7 +483,7 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
     const bool after = t > L.tmax;
 #pragma unroll
     for (int v = 0; v < NS; ++v) nS[v] = before ? L.LB[v] : (after ? MSA_NEG : nS[v]);
-    if constexpr (swlin(ALG) || ALG == MSA_ALG_SWA) {
+    if constexpr (swlin(ALG) || swaf(ALG)) {
       const int hv = swlin(ALG) ? nS[0] - ct : nS[0];
       hout = hv;
       if constexpr (TRACKPOS == 2) {
@@ -503,7 +511,7 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
       // values, and these updates are dead code there)
       L.pb = pk_max(L.pb, pk_add(nS[0], ct));
       hout = 0;
-    } else if constexpr (swlin(ALG) || ALG == MSA_ALG_SWA) {
+    } else if constexpr (swlin(ALG) || swaf(ALG)) {
       const int hv = swlin(ALG) ? nS[0] - ct : nS[0];
       hout = hv;
       if constexpr (TRACKPOS == 2) {
@@ -520,7 +528,7 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
   // carried values (what the lane below / next stripe needs)
   if constexpr (swlin(ALG)) {
     carry[0] = nS[0];
-  } else if constexpr (ALG == MSA_ALG_SWA || nwa(ALG) || ALG == MSA_ALG_REF1) {
+  } else if constexpr (swaf(ALG) || nwa(ALG) || ALG == MSA_ALG_REF1) {
     carry[0] = nS[0];
     carry[1] = nS[2];
   } else {
@@ -673,7 +681,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
   // Smith-Waterman kernels never mask: columns outside [1, n] carry the
   // virtual code whose score (MSA_VIRT_SCORE) keeps every out-of-matrix cell
   // strictly below a real cell, so the plain recurrence runs over them.
-  constexpr bool SWK = (swlin(ALG) || ALG == MSA_ALG_SWA);
+  constexpr bool SWK = (swlin(ALG) || swaf(ALG));
   extern __shared__ __attribute__((aligned(16))) int smem[];
   const msa_kparams& kp = a.kp;
   const int lane = threadIdx.x & 63;
@@ -1017,7 +1025,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
       // row is taken by selects at the stripe's start (a load at a.sub[ac] would wait for ac here, in front of the
       // workgroup's barriers)
       uint2 tab[8] = {};
-      if constexpr (nwa(ALG) && !wide(ALG)) {
+      if constexpr ((nwa(ALG) || swsc(ALG)) && !wide(ALG)) {
 #pragma unroll
         for (int c = 0; c < 8; ++c) tab[c] = a.sub[c];
       }
@@ -1064,7 +1072,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         L.pw[0] = p0.x; L.pw[1] = p0.y; L.pw[2] = p0.z; L.pw[3] = p0.w;
         L.pw[4] = p1.x; L.pw[5] = p1.y; L.pw[6] = p1.z; L.pw[7] = p1.w;
         L.plo = L.phi = L.plo2 = L.phi2 = 0;
-      } else if constexpr (nwa(ALG)) {
+      } else if constexpr (nwa(ALG) || swsc(ALG)) {  // (MSA_ALG_SWS: byte 7 of every row is MSA_VIRT_SCORE already)
         L.plo = tab[0].x;
         L.phi = tab[0].y;
 #pragma unroll
@@ -1368,7 +1376,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
                              imax3(hist[0][4 * u + 1], hist[1][4 * u + 1], hist[2][4 * u + 1]),
                              imax3(hist[0][4 * u + 2], hist[1][4 * u + 2], hist[2][4 * u + 2]),
                              imax3(hist[0][4 * u + 3], hist[1][4 * u + 3], hist[2][4 * u + 3]));
-            } else if constexpr (swlin(ALG) || ALG == MSA_ALG_SWA) {
+            } else if constexpr (swlin(ALG) || swaf(ALG)) {
               h4 = make_int4(hv[4 * u], hv[4 * u + 1], hv[4 * u + 2], hv[4 * u + 3]);
             } else {
               h4 = make_int4(hist[0][4 * u], hist[0][4 * u + 1], hist[0][4 * u + 2], hist[0][4 * u + 3]);
@@ -1523,7 +1531,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
             mh->phases = sg.P * CPP;
           }
         }
-      } else if constexpr (swlin(ALG) || ALG == MSA_ALG_SWA) {
+      } else if constexpr (swlin(ALG) || swaf(ALG)) {
         // first max in row-major order: max best, then min row
         const int bv = (TRACKPOS == 2) ? (L.best >> 15) : L.best;
         const int bt = (TRACKPOS == 2) ? 32767 - (L.best & 32767) : L.bt;

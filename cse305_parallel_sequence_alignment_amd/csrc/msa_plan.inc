@@ -123,6 +123,7 @@ struct msa_plan {
   // MSA_ALG_NWA: the substitution scores S[8 a + b] (row code a, column code b; 1 / 0 unless MSA_NW_SCORED) and
   // their device table, one 8-byte profile per row code in the launch's space (alloc_buffers)
   // MSA_ALG_NWA32, MSA_ALG_FIT32 (msa_plan_create_scored32): S[32 a + b], uploaded as it is (1,024 bytes)
+  // MSA_ALG_SWS, MSA_ALG_SWS32 (MSA_SW_SCORED): either layout, MSA_VIRT_SCORE in the virtual code's row and column
   int8_t sub[1024] = {};
   uint2* d_sub = nullptr;
 
@@ -159,7 +160,8 @@ bool fit_bytes(const msa_plan* P) { return P->d.alg == MSA_NW_FIT && P->d.cells 
 
 // ---- step 1: kernel algorithm and end-cell tracking mode --------------------------------------------
 // wide32: a 32 x 32 table over 5-bit codes (msa_plan_create_scored32: MSA_NW_SCORED and MSA_NW_FIT only)
-int choose_algorithm(const msa_plan_desc* desc, bool wide32, int& kalg, int& tp) {
+// sw_smax: max(0, the largest table entry over real codes) of an MSA_SW_SCORED plan (unused by every other plan)
+int choose_algorithm(const msa_plan_desc* desc, bool wide32, int sw_smax, int& kalg, int& tp) {
   const int out_mode = desc->cells;
   switch (desc->alg) {
     case MSA_SW_LINEAR:
@@ -181,6 +183,13 @@ int choose_algorithm(const msa_plan_desc* desc, bool wide32, int& kalg, int& tp)
       }
       break;
     case MSA_SW_AFFINE: kalg = MSA_ALG_SWA; break;
+    case MSA_SW_SCORED:
+      // MSA_SW_AFFINE with f = S[row code][column code] (the plan's table: plan_create): a kernel algorithm of its
+      // own (new stripe_kernel instantiations).  Direction bytes or the score alone, no band; the gap costs' and the
+      // table's sizes are check_ranges'
+      kalg = wide32 ? MSA_ALG_SWS32 : MSA_ALG_SWS;
+      if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->band != -1) return MSA_ERR_UNSUPPORTED;
+      break;
     case MSA_NW_BANDED: kalg = MSA_ALG_NWA; break;
     case MSA_NW_ALIGN:
       // MSA_NW_BANDED's recurrence with one direction byte per cell, walked by msa_plan_traceback_nw: direction
@@ -222,11 +231,13 @@ int choose_algorithm(const msa_plan_desc* desc, bool wide32, int& kalg, int& tp)
     default: return MSA_ERR_ARG;
   }
   tp = (kalg == MSA_ALG_SWL || kalg == MSA_ALG_SWL0 || kalg == MSA_ALG_SWA) ? (desc->track_end ? 1 : 0) : 0;
+  if (swsc(kalg)) tp = 1;  // (an MSA_SW_SCORED plan always tracks its end cell)
   if (tp) {
     // the first-maximum position packs with the value into one int (TRACKPOS 2) when every local score is below 2^16
     // and a stripe has < 2^15 steps.  A local score gains at most max(0, match, mismatch) per diagonal step (gaps
-    // only subtract), and a path has at most min(m, n) diagonal steps.
-    const int64_t smax = std::max({0, desc->match, desc->mismatch});
+    // only subtract), and a path has at most min(m, n) diagonal steps.  (MSA_SW_SCORED: the table's largest entry
+    // over real codes in their place.)
+    const int64_t smax = swsc(kalg) ? sw_smax : std::max({0, desc->match, desc->mismatch});
     bool pack = true;
     for (int64_t p = 0; p < desc->n_pairs && pack; ++p)
       pack = smax * std::min(desc->m[p], desc->n[p]) < 65536 && desc->n[p] + 512 < 32768;
@@ -262,7 +273,8 @@ int sub_abs_max(const int8_t* sub, int count) {
 }
 // `scored`: the table of an MSA_NW_SCORED or MSA_NW_FIT plan (nullptr for every other plan), 64 scores or, for the
 // 32-code kernels, 1,024
-int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t* scored) {
+// sw_smax: as for choose_algorithm
+int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t* scored, int sw_smax) {
   for (int64_t p = 0; p < desc->n_pairs; ++p) {
     const int64_t m = desc->m[p], n = desc->n[p];
     if (m <= 0 || n <= 0 || m > (1 << 26) || n > (1 << 26)) return MSA_ERR_ARG;
@@ -313,6 +325,19 @@ int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t*
           kp.gap_ext < 0 || top >= (int64_t(1) << 29))
         return MSA_ERR_UNSUPPORTED;
     }
+    if (swsc(kp.alg)) {
+      // MSA_SW_SCORED: MSA_ALG_SWA's bound with smax = max(0, the largest S over real codes) for max(0, match,
+      // mismatch).  One inequality on the top suffices, unlike the global plans' two-sided K above, because the zero
+      // floor stops every drift downwards: H >= 0 in every cell, virtual ones included, and E (F) is a max that
+      // contains the left (upper) cell's H - gap_open, so E, F >= -gap_open however long the row or column: no value
+      // drifts with m + n, and no negative S, real (>= -128) or virtual (MSA_VIRT_SCORE), outlives its own cell --
+      // d = H_diag + S enters a max with 0.  Upwards, an H is a sum of at most min(m, n) diagonal scores <= smax less
+      // gap costs >= 0 (a virtual cell adds none), so H <= smax min(m, n) < 2^29 and H + S stays inside int32.  A -inf
+      // (MSA_NEG: E, F and the diagonal at a stripe's start, the masked inputs) meets one subtraction of a gap cost or
+      // one addition of an S before a max with a finite value, exactly as in MSA_ALG_SWA.
+      if (kp.gap_open < 0 || kp.gap_ext < 0 || (int64_t)sw_smax * std::min(m, n) >= (int64_t(1) << 29))
+        return MSA_ERR_UNSUPPORTED;
+    }
     if (kp.band >= 0 && std::llabs(m - n) > kp.band) return MSA_ERR_ARG;
   }
   return MSA_OK;
@@ -354,6 +379,9 @@ PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp, int smax) {
   const int out_mode = desc->cells;
   // 5-bit codes: stripe_kernel alone has the 32-code lookup -- a single pair (any band: the exact masked launch), a batch
   if (wide(kalg)) return PM_STRIPE;
+  // MSA_SW_SCORED: stripe_kernel alone scores the SW-affine cell from a table (the flow kernels build their profile
+  // from match / mismatch, and the split launch is not instantiated for it) -- one pair or a batch
+  if (swsc(kalg)) return PM_STRIPE;
   const int band = (kalg == MSA_ALG_NWA) ? desc->band : -1;
   if (desc->single) {
     // flow kernels: one SW-linear pair (8 byte-shifted LDS code rings), or one SW-affine / reference-Gotoh (start
@@ -738,7 +766,8 @@ int alloc_buffers(msa_plan& P) {
     // the 32 x 32 table as it is: stripe_kernel's bytes are the raw S (each workgroup copies it to LDS)
     if (!P.alloc(&P.d_sub, sizeof(P.sub))) return MSA_ERR_HIP;
     HIPCHK(hipMemcpy(P.d_sub, P.sub, sizeof(P.sub), hipMemcpyHostToDevice));
-  } else if (P.main.kp.alg == MSA_ALG_NWA || P.main.kp.alg == MSA_ALG_FIT) {
+  } else if (P.main.kp.alg == MSA_ALG_NWA || P.main.kp.alg == MSA_ALG_FIT || P.main.kp.alg == MSA_ALG_SWS) {
+    // (MSA_ALG_SWS: stripe_kernel, so the raw S -- with plan_create's MSA_VIRT_SCORE in column 7)
     // the substitution table, one 8-byte profile per row code: band_kernel's bytes are S + 2g + h (its values are
     // shifted by g (i + j); wrapped to a byte as the kernel's own arithmetic did for the 1 / 0 plans), stripe_kernel's S
     const bool bandk = P.mode == PM_BAND || P.mode == PM_BAND_CHUNKED;
@@ -819,7 +848,8 @@ int msa_plan_create_scored32(const msa_plan_desc* desc, const int8_t* sub32, msa
 // sub: 64 scores S[8 a + b] or nullptr, or with wide32 1,024 scores S[32 a + b]
 static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32, msa_plan** out) {
   if (!desc || !out || desc->n_pairs <= 0 || !desc->m || !desc->n || !desc->a_off || !desc->b_off) return MSA_ERR_ARG;
-  if (sub && desc->alg != MSA_NW_SCORED && desc->alg != MSA_NW_FIT) return MSA_ERR_UNSUPPORTED;
+  const bool sw_scored = desc->alg == MSA_SW_SCORED;
+  if (sub && desc->alg != MSA_NW_SCORED && desc->alg != MSA_NW_FIT && !sw_scored) return MSA_ERR_UNSUPPORTED;
   int rc = ensure_device();
   if (rc != MSA_OK) return rc;
   // (a plan without device buffers yet destroys cleanly: no streams, no blocks, null events)
@@ -828,8 +858,25 @@ static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32
   P->d = *desc;
   P->d.m = P->d.n = P->d.a_off = P->d.b_off = nullptr;
   P->d.single = desc->single ? 1 : 0;
+  // MSA_SW_SCORED: the launch's own table.  The highest code (7, or 31 over 5-bit codes) is the virtual column's, so
+  // the caller's entries with either index equal to it are ignored: that column carries MSA_VIRT_SCORE in every row
+  // (and so does its row, which no input selects); smax is taken over the real codes alone
+  int sw_smax = 0;
+  if (sw_scored) {
+    if (!sub && (desc->match < -128 || desc->match > 127 || desc->mismatch < -128 || desc->mismatch > 127))
+      return MSA_ERR_UNSUPPORTED;
+    const int nc = wide32 ? 32 : 8;
+    for (int a = 0; a < nc; ++a)
+      for (int b = 0; b < nc; ++b) {
+        const bool virt = a == nc - 1 || b == nc - 1;
+        const int v = virt ? MSA_VIRT_SCORE : (sub ? (int)sub[nc * a + b] : (a == b ? desc->match : desc->mismatch));
+        P->sub[nc * a + b] = (int8_t)v;
+        if (!virt) sw_smax = std::max(sw_smax, v);
+      }
+    P->d.track_end = 1;  // (always tracked: the walkers' check)
+  }
   int kalg, tp;
-  if ((rc = choose_algorithm(desc, wide32, kalg, tp)) != MSA_OK) return rc;
+  if ((rc = choose_algorithm(desc, wide32, sw_smax, kalg, tp)) != MSA_OK) return rc;
   P->tp = tp;
   if (desc->single && desc->n_pairs != 1) return MSA_ERR_ARG;
   // (alg, cells, tracking) combinations no kernel computes: every family takes a subset of the stripe kernel's
@@ -845,13 +892,13 @@ static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32
   int smax = 0;
   if (scored && !sub && (desc->match < -128 || desc->match > 127 || desc->mismatch < -128 || desc->mismatch > 127))
     return MSA_ERR_UNSUPPORTED;
-  if (wide32) std::memcpy(P->sub, sub, sizeof(P->sub));
-  for (int k = 0; k < 64 && !wide32; ++k) {
+  if (wide32 && !sw_scored) std::memcpy(P->sub, sub, sizeof(P->sub));
+  for (int k = 0; k < 64 && !wide32 && !sw_scored; ++k) {
     const bool diag = k / 8 == k % 8;
     P->sub[k] = sub ? sub[k] : (int8_t)(scored ? (diag ? desc->match : desc->mismatch) : (diag ? 1 : 0));
     smax = k ? std::max(smax, (int)P->sub[k]) : (int)P->sub[k];
   }
-  if ((rc = check_ranges(desc, P->main.kp, scored ? P->sub : nullptr)) != MSA_OK) return rc;
+  if ((rc = check_ranges(desc, P->main.kp, scored ? P->sub : nullptr, sw_smax)) != MSA_OK) return rc;
   P->mode = choose_mode(desc, kalg, tp, smax);
   set_layout_mode(*P, desc);
   const Extents ex = lay_out_pairs(*P, desc);

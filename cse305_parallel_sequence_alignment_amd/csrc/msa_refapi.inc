@@ -1172,6 +1172,24 @@ AlignSpec spec_sw(int match, int mismatch, const char* preset) {
   return AlignSpec{MSA_OK, MSA_SW_AFFINE, MSA_SW_AFFINE, match, mismatch, 0, 1, false, {}, SymbolMap(7, preset),
                    GAPS_LOCAL, false, FOOT_MATRIX, msa_plan_traceback, BORDER_NONE, true};
 }
+// Smith-Waterman under the caller's alphabet -- a symbol's code is its index -- and its n_sym x n_sym matrix
+// (MSA_SW_SCORED).  The highest code is the sentinel's, so max_sym is 7, or 31 (the *32 entries); up to 7 symbols make
+// the same spec under either, 8..31 a wide one.  status MSA_ERR_ARG as for spec_scored
+AlignSpec spec_sw_scored(const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym) {
+  AlignSpec s = spec_sw(0, 0, "");
+  s.alg_walk = s.alg_score = MSA_SW_SCORED;
+  s.scored = true;
+  if (!alphabet || !sub || n_sym < 1 || n_sym > max_sym) s.status = MSA_ERR_ARG;
+  s.wide = s.status == MSA_OK && n_sym > 7;
+  if (s.wide) s.symbols = SymbolMap(31);
+  const size_t stride = s.wide ? 32 : 8;
+  for (size_t a = 0; s.status == MSA_OK && a < n_sym; ++a) {
+    if (!s.symbols.add(alphabet[a])) s.status = MSA_ERR_ARG;
+    for (size_t b = 0; b < n_sym; ++b) s.tab[stride * a + b] = sub[n_sym * a + b];
+  }
+  s.symbols.fix();
+  return s;
+}
 // global, +1 / 0 over the call's own symbols
 AlignSpec spec_nw(const char* preset) {
   return AlignSpec{MSA_OK, MSA_NW_ALIGN, MSA_NW_BANDED, 1, 0, -1, 0, false, {}, SymbolMap(8, preset),
@@ -1535,6 +1553,60 @@ int msa_fit_align_batch32(const char* A, size_t a_len, const char* B, size_t b_l
   const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
   const AlignOut out{score, PairOut(), PairOut(), PairOut(beg_end), cigars, cigar_cap, cigar_off};
   return align_pairs(spec_fit(alphabet, n_sym, sub, 32), 0, in, kPairLimit, gap_open, gap_extend, -1, out);
+}
+
+// ---- local alignment under a substitution matrix (MSA_SW_SCORED): msa_sw_align / msa_sw_align_batch with the
+// caller's alphabet and matrix in place of match / mismatch; 7 symbols, or 31 for the *32 entries
+static int sw_align_scored(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                           const int8_t* sub, size_t max_sym, int32_t gap_open, int32_t gap_extend, int32_t* score,
+                           int64_t* end_i, int64_t* end_j, int64_t* beg_i, int64_t* beg_j, char* cigar,
+                           size_t cigar_cap) {
+  const OnePairIn one(A0, m, B0, n);
+  int64_t coff[2];
+  const AlignOut out{score, PairOut(end_i, end_j), PairOut(beg_i, beg_j), PairOut(), cigar, cigar_cap, coff};
+  return align_pairs(spec_sw_scored(alphabet, n_sym, sub, max_sym), 1, one.in, INT64_MAX, gap_open, gap_extend, -1,
+                     out);
+}
+static int sw_align_batch_scored(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                                 const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                                 const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym,
+                                 int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_ij,
+                                 int64_t* beg_ij, char* cigars, size_t cigar_cap, int64_t* cigar_off) {
+  const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  const AlignOut out{score, PairOut(end_ij), PairOut(beg_ij), PairOut(), cigars, cigar_cap, cigar_off};
+  return align_pairs(spec_sw_scored(alphabet, n_sym, sub, max_sym), 0, in, kPairLimit, gap_open, gap_extend, -1, out);
+}
+
+int msa_sw_align_scored(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                        const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_i,
+                        int64_t* end_j, int64_t* beg_i, int64_t* beg_j, char* cigar, size_t cigar_cap) {
+  return sw_align_scored(A0, m, B0, n, alphabet, n_sym, sub, 7, gap_open, gap_extend, score, end_i, end_j, beg_i,
+                         beg_j, cigar, cigar_cap);
+}
+
+int msa_sw_align_scored32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                          const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_i,
+                          int64_t* end_j, int64_t* beg_i, int64_t* beg_j, char* cigar, size_t cigar_cap) {
+  return sw_align_scored(A0, m, B0, n, alphabet, n_sym, sub, 31, gap_open, gap_extend, score, end_i, end_j, beg_i,
+                         beg_j, cigar, cigar_cap);
+}
+
+int msa_sw_align_batch_scored(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                              const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                              const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                              int32_t gap_extend, int32_t* score, int64_t* end_ij, int64_t* beg_ij, char* cigars,
+                              size_t cigar_cap, int64_t* cigar_off) {
+  return sw_align_batch_scored(A, a_len, B, b_len, n_pairs, a_off, m, b_off, n, alphabet, n_sym, sub, 7, gap_open,
+                               gap_extend, score, end_ij, beg_ij, cigars, cigar_cap, cigar_off);
+}
+
+int msa_sw_align_batch_scored32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                                const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                                const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                                int32_t gap_extend, int32_t* score, int64_t* end_ij, int64_t* beg_ij, char* cigars,
+                                size_t cigar_cap, int64_t* cigar_off) {
+  return sw_align_batch_scored(A, a_len, B, b_len, n_pairs, a_off, m, b_off, n, alphabet, n_sym, sub, 31, gap_open,
+                               gap_extend, score, end_ij, beg_ij, cigars, cigar_cap, cigar_off);
 }
 
 }  // extern "C"

@@ -28,6 +28,10 @@ enum msa_alg {
   MSA_ALG_NWA32 = 9,   // MSA_ALG_NWA over 5-bit codes: scores from the plan's 32 x 32 table (KArgs::sub, raw int8 S),
                        // the lane's 32-byte row of it in eight registers (msa_plan_create_scored32, stripe_kernel only)
   MSA_ALG_FIT32 = 10,  // MSA_ALG_FIT over 5-bit codes, likewise
+  MSA_ALG_SWS = 11,    // MSA_ALG_SWA's cell, borders, best tracking and virtual columns with substitution scores from
+                       // the plan's 8 x 8 table (MSA_SW_SCORED plans, stripe_kernel only): real codes 0..6, column 7
+                       // of every row = MSA_VIRT_SCORE (the host-side table builder fills it in)
+  MSA_ALG_SWS32 = 12,  // MSA_ALG_SWS over 5-bit codes under the 32 x 32 table: real codes 0..30, the virtual code 31
 };
 
 // Per-cell outputs.
@@ -38,7 +42,8 @@ enum msa_out {
   MSA_OUT_TAB = 3,   // three int32 planes T1,T2,T3 per cell (skewed stripe layout)
 };
 
-// One pair of sequences inside a launch.  Codes are uint8 in [0,8) ([0,32): MSA_ALG_NWA32, MSA_ALG_FIT32).
+// One pair of sequences inside a launch.  Codes are uint8 in [0,8) ([0,32): MSA_ALG_NWA32, MSA_ALG_FIT32,
+// MSA_ALG_SWS32).
 typedef struct msa_pair_desc {
   int64_t a_off;       // offset of row codes (A[0] = row 1) in the A code array
   int64_t b_off;       // offset of column codes (B[0] = column 1) in the B code array

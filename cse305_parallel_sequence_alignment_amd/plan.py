@@ -51,13 +51,17 @@ class Plan:
 
     def __init__(self, alg: int, cells: int, ms, ns, a_offs, b_offs, match=1, mismatch=0, gap_open=1,
                  gap_extend=1, start_type=-1, band=-1, track_end=False, single=None, sub=None):
-        """``sub`` (NW_SCORED and NW_FIT only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code a against
-        column code b (msa_plan_create_scored); None scores ``match`` on the diagonal and ``mismatch`` elsewhere.
-        A 32 x 32 ``sub`` makes a plan over 5-bit codes (msa_plan_create_scored32: inputs in [0, 32), always the
+        """``sub`` (NW_SCORED, NW_FIT and SW_SCORED only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code
+        a against column code b (msa_plan_create_scored); None scores ``match`` on the diagonal and ``mismatch``
+        elsewhere.  A 32 x 32 ``sub`` makes a plan over 5-bit codes (msa_plan_create_scored32: inputs in [0, 32), always the
         stripe kernel); any other shape is a ValueError.
         An NW_FIT plan (all of A against a substring of B: ``band`` -1, CELLS_DIR or CELLS_NONE) reports in
         ``results()`` the score and ``end = (m, end_j)``, the first column of row m's maximum; ``traceback_nw`` and
-        ``traceback_batch`` walk from there."""
+        ``traceback_batch`` walk from there.
+        An SW_SCORED plan (SW_AFFINE's recurrence under the table: ``band`` -1, CELLS_DIR or CELLS_NONE) keeps the
+        highest code, 7 or 31, as the kernels' out-of-matrix sentinel: inputs are codes 0..6 / 0..30 and ``sub``'s last
+        row and column are ignored.  It always tracks its end cell and runs the stripe kernel; ``traceback``,
+        ``traceback_batch`` and ``deskew_dir`` serve it as they serve an SW_AFFINE plan."""
         L = LB.lib()
         self.alg, self.cells = alg, cells
         self.ms = [int(x) for x in ms]

@@ -52,6 +52,11 @@
  *                        5-bit codes under a 32 x 32 int8 substitution table (build extension: stripe kernel
  *                        instantiations of their own, whose lanes hold a 32-byte row of the table and look four
  *                        scores up with seven v_perm_b32)
+ *   msa_sw_align_scored, msa_sw_align_batch_scored, msa_sw_align_scored32, msa_sw_align_batch_scored32
+ *                        local (Smith-Waterman) alignment under an int8 substitution matrix over up to 7 symbols,
+ *                        or 31 over 5-bit codes (build extension: MSA_SW_SCORED plans -- the stripe kernel's
+ *                        SW-affine cell with its score from the plan's table, the highest code kept as the
+ *                        out-of-matrix sentinel; msa_plan_traceback and msa_plan_traceback_batch walk them)
  */
 #ifndef MSA_H
 #define MSA_H
@@ -228,7 +233,7 @@ int msa_partition_tables(const int32_t* T1, const int32_t* T2, const int32_t* T3
  * uint8 codes in [0,8) ([0,32) for msa_plan_create_scored32's plans) already in device memory (see msa_encode_pair for the
  * host-side code map); the
  * Smith-Waterman algorithms reserve code 7 (out-of-matrix sentinel), so their
- * inputs use codes 0..6. */
+ * inputs use codes 0..6 (MSA_SW_SCORED over 5-bit codes: code 31, inputs 0..30). */
 typedef enum msa_alg_e {
   MSA_SW_LINEAR = 0,  /* Smith-Waterman, linear gap (gap_open == gap_extend used) */
   MSA_SW_AFFINE = 1,  /* Smith-Waterman, affine gap */
@@ -241,9 +246,15 @@ typedef enum msa_alg_e {
                          f(i,j) = S[code of A_i][code of B_j]: S from match / mismatch, or an 8 x 8 table
                          (msa_plan_create_scored); MSA_CELLS_DIR (walked by msa_plan_traceback_nw /
                          msa_plan_traceback_batch) or MSA_CELLS_NONE (the score only) */
-  MSA_NW_FIT = 7      /* fit ("glocal", "semi-global", "infix") alignment: all of A against a substring of B that
+  MSA_NW_FIT = 7,     /* fit ("glocal", "semi-global", "infix") alignment: all of A against a substring of B that
                          the alignment chooses, MSA_NW_SCORED's cells under a zero top border; the contract is
                          at msa_fit_align below.  band = -1, MSA_CELLS_DIR or MSA_CELLS_NONE */
+  MSA_SW_SCORED = 8   /* MSA_SW_AFFINE's recurrence with f(i,j) = S[code of A_i][code of B_j]: the same zero floor,
+                         borders, direction byte (h == 0 -> 0, then diagonal, E, F; bits 2 / 3 "open wins a tie"), end
+                         cell (first maximum, row-major) and walk.  S from match / mismatch, or a table
+                         (msa_plan_create_scored: 8 x 8, inputs are codes 0..6; msa_plan_create_scored32: 32 x 32,
+                         codes 0..30 -- the highest code is the out-of-matrix sentinel's).  The contract is at
+                         msa_plan_create_scored below */
 } msa_alg_e;
 
 typedef enum msa_out_e { MSA_CELLS_NONE = 0, MSA_CELLS_H = 1, MSA_CELLS_DIR = 2, MSA_CELLS_TAB = 3 } msa_out_e;
@@ -287,7 +298,20 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** plan);
  * for every pair (the derivation is at check_ranges, msa_plan.inc); anything else is MSA_ERR_UNSUPPORTED.  The
  * band rule and its MSA_ERR_ARG are MSA_NW_ALIGN's.  MSA_NW_FIT takes a table (or NULL: match / mismatch) in the
  * same way and under the same inequality (its zero top border is within the bound); it is MSA_ERR_UNSUPPORTED
- * with any band but -1 and with cells other than MSA_CELLS_DIR / MSA_CELLS_NONE. */
+ * with any band but -1 and with cells other than MSA_CELLS_DIR / MSA_CELLS_NONE.
+ * MSA_SW_SCORED takes a table too (NULL: desc->match on the diagonal, desc->mismatch elsewhere, in [-128, 127]; the
+ * results are then an MSA_SW_AFFINE plan's).  The kernels keep their out-of-matrix sentinel: code 7 is the virtual
+ * column's, the inputs are codes 0..6 -- 7 symbols --, table entries with either index 7 are ignored, and the launch's
+ * own copy carries the sentinel score in that column of every row.  Cells MSA_CELLS_DIR or MSA_CELLS_NONE, band -1,
+ * gap_open >= 0, gap_extend >= 0 (MSA_SW_AFFINE's rule) and, with smax = max(0, the largest entry over codes 0..6),
+ *     smax min(m, n) < 2^29
+ * for every pair; anything else is MSA_ERR_UNSUPPORTED.  The plan always tracks its end cell (desc->track_end is
+ * ignored): packed with the value when smax min(m, n) < 65536 and n + 512 < 32768 for every pair, else by
+ * compare-select (msa_plan_format_info).  Every MSA_SW_SCORED plan launches the stripe kernel (msa_plan_launch_info
+ * mode 0), one pair or a batch: no flow, cflow or split launch.  msa_plan_traceback (one pair) and
+ * msa_plan_traceback_batch (no walk for a score <= 0) walk its direction bytes under their unchanged contracts;
+ * msa_plan_traceback_nw and msa_plan_traceback_gotoh reject it with MSA_ERR_UNSUPPORTED.  A non-NULL sub with
+ * MSA_SW_AFFINE stays MSA_ERR_UNSUPPORTED, and MSA_SW_AFFINE plans choose their kernels as before. */
 int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_plan** plan);
 /* MSA_NW_SCORED and MSA_NW_FIT over 5-bit codes: sub32 = 1,024 scores, row-major sub32[32*a + b] = the score of A's
  * code a against B's code b.  The inputs of msa_plan_run are codes in [0, 32).  desc->alg must be MSA_NW_SCORED or
@@ -295,7 +319,10 @@ int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_pla
  * value-range inequality (s = the largest |score| of the 1,024) and their errors are msa_plan_create_scored's.
  * Such a plan always launches the stripe kernel (msa_plan_launch_info mode 0): one pair, a batch, any band (a banded
  * single pair runs the exact masked stripe launch).  msa_plan_format_info reports it in its fourth word;
- * msa_plan_traceback_nw and msa_plan_traceback_batch walk its direction bytes as they walk an 8-code plan's. */
+ * msa_plan_traceback_nw and msa_plan_traceback_batch walk its direction bytes as they walk an 8-code plan's.
+ * MSA_SW_SCORED is accepted too, under msa_plan_create_scored's rules for it with 31 in place of 7: code 31 is the
+ * virtual column's, the inputs are codes 0..30 -- 31 symbols --, entries with either index 31 are ignored, smax is
+ * taken over codes 0..30; msa_plan_traceback and msa_plan_traceback_batch walk it. */
 int msa_plan_create_scored32(const msa_plan_desc* desc, const int8_t* sub32, msa_plan** plan);
 void msa_plan_destroy(msa_plan* plan);
 /* Elements (int32 for H/TAB planes, bytes for DIR) the per-cell output needs. */
@@ -351,7 +378,7 @@ int64_t msa_plan_stripes(const msa_plan* plan);
  * for two-pass single-pair SW-linear H plans. */
 int msa_plan_pair_layout(const msa_plan* plan, int64_t pair, int64_t* out4);
 /* Smith-Waterman traceback ON THE DEVICE (msa_traceback.hip), for an
- * MSA_SW_AFFINE plan with MSA_CELLS_DIR after msa_plan_run on the same stream:
+ * MSA_SW_AFFINE (with track_end) or MSA_SW_SCORED plan with MSA_CELLS_DIR after msa_plan_run on the same stream:
  * one workgroup (a walker wave, four stripe-group loader waves, an op decoder
  * wave) walks pair `pair`'s direction bytes dDir from the end cell the run
  * found (first maximum, row-major) and writes the ops end -> start into d_ops
@@ -405,7 +432,7 @@ int msa_plan_traceback_nw(msa_plan* plan, int64_t pair, const uint8_t* dDir, uin
 /* Every pair's traceback ON THE DEVICE in ONE launch (msa_tbatch.hip), after msa_plan_run on the same
  * stream: one wave per pair, four walks per workgroup, each wave staging its own stripe groups and writing
  * its own ops (the single walkers above spend a six-wave workgroup on one long walk and take a launch
- * per pair).  Plans: MSA_SW_AFFINE with MSA_CELLS_DIR and track_end (msa_plan_traceback's walk, from each
+ * per pair).  Plans: MSA_SW_AFFINE with MSA_CELLS_DIR and track_end, or MSA_SW_SCORED with MSA_CELLS_DIR (msa_plan_traceback's walk, from each
  * pair's end cell; no walk for a score <= 0) or MSA_NW_ALIGN / MSA_NW_SCORED (msa_plan_traceback_nw's walk, from (m, n) to
  * the matrix border; the caller appends the border gap; MSA_NW_FIT: that walk from each pair's (m, end_j)), laid
  * out one row per lane with the stripe starts
@@ -564,6 +591,35 @@ int msa_fit_align_batch32(const char* A, size_t a_len, const char* B, size_t b_l
                           const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
                           int32_t gap_extend, int32_t* score, int64_t* beg_end /* 2 n_pairs: {beg_j, end_j} */,
                           char* cigars, size_t cigar_cap, int64_t* cigar_off);
+
+/* msa_sw_align and msa_sw_align_batch under a substitution matrix (build extension: MSA_SW_SCORED plans): their
+ * signatures with `alphabet, n_sym, sub` in place of `match, mismatch`.  alphabet: n_sym distinct bytes, a symbol's
+ * code is its index; sub: n_sym x n_sym scores in int8, row-major, the row is A's symbol (it need not be symmetric).
+ * The kernels' highest code is their out-of-matrix sentinel, so 1 <= n_sym <= 7 for the plain entries and <= 31 for
+ * the *32 entries; up to 7 symbols build exactly the plain entry's plans under either, 8..31 build plans over 5-bit
+ * codes (msa_plan_create_scored32).  Every such plan runs the stripe kernel, a single long pair included.
+ * n_sym outside that range, a duplicate symbol, or a NULL alphabet or sub: MSA_ERR_ARG.  Then, in this order: the
+ * other argument errors, the gap rule (gap_open, gap_extend >= 0, else MSA_ERR_UNSUPPORTED), a symbol of A or B
+ * outside the alphabet (MSA_ERR_ALPHABET), and only then the device.  The score, the end cell (first maximum,
+ * row-major), the start cell and the CIGAR, score-only calls (cigar and beg NULL), MSA_ERR_CAPACITY (batches: with
+ * the needed size in cigar_off[n_pairs]), chunks of pairs, a shared reference and admission against the device
+ * budget are msa_sw_align's and msa_sw_align_batch's. */
+int msa_sw_align_scored(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                        const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_i,
+                        int64_t* end_j, int64_t* beg_i, int64_t* beg_j, char* cigar, size_t cigar_cap);
+int msa_sw_align_batch_scored(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                              const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                              const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                              int32_t gap_extend, int32_t* score, int64_t* end_ij, int64_t* beg_ij, char* cigars,
+                              size_t cigar_cap, int64_t* cigar_off);
+int msa_sw_align_scored32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                          const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_i,
+                          int64_t* end_j, int64_t* beg_i, int64_t* beg_j, char* cigar, size_t cigar_cap);
+int msa_sw_align_batch_scored32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                                const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                                const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                                int32_t gap_extend, int32_t* score, int64_t* end_ij, int64_t* beg_ij, char* cigars,
+                                size_t cigar_cap, int64_t* cigar_off);
 
 #ifdef __cplusplus
 }
