@@ -25,6 +25,7 @@
 
 #include "../../include/msa.h"
 #include "msa_hostutil.h"
+#include "msa_refwalk.h"
 #include "msa_kernels.hip"
 #include "msa_flow.hip"
 #include "msa_cflow.hip"
@@ -75,7 +76,7 @@ int current_device() {
   return dev;
 }
 
-// Frees pooled blocks held by idle cached plans (msa_refapi.inc) when the device runs out.
+// Frees pooled blocks held by idle cached plans (msa_devcall.inc) when the device runs out.
 void (*g_pool_reclaim)() = nullptr;
 
 // Device memory pool.  The reference's harness calls main_alignment_function
@@ -199,7 +200,7 @@ DevPool& dev_pool() {
 // runs alone (it waits until nothing else is admitted).  Budget: MSA_DEVICE_BUDGET_MB, else 90% of
 // the device's memory; msa_set_device_budget overrides it at run time.
 // Memory the library holds on a device outside the admitted calls: idle cached plans of the reference
-// walk and free blocks of the device pool (msa_refapi.inc).  An admission that would put admitted +
+// walk and free blocks of the device pool (msa_devcall.inc).  An admission that would put admitted +
 // idle bytes over the budget first releases the idle ones, so cached memory never pushes admitted calls
 // into the allocator's out-of-memory path.
 size_t idle_device_bytes(int dev);
@@ -926,5 +927,8 @@ int msa_plan_checksum(msa_plan* P, const int32_t* dH, int64_t pair, uint64_t* di
 }
 
 }  // extern "C"
+// the host-pointer entries: the device-call scaffold, then the reference's API and the alignment entries over it
+#include "msa_devcall.inc"
 #include "msa_refapi.inc"
 #include "msa_rowapi.inc"
+#include "msa_alignapi.inc"

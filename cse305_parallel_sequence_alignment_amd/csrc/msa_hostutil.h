@@ -1,6 +1,7 @@
-// msa_hostutil.h -- the pure host-side steps of the host-pointer entries (msa_capi.hip, msa_refapi.inc): symbol
-// codes, CIGAR strings, the border gap, plan descriptions.  Standard C++ only -- no HIP -- so that
-// tests/cpp/hostutil_driver.cpp runs every one of them on the CPU under sanitizers.
+// msa_hostutil.h -- the pure host-side steps of the host-pointer entries (msa_capi.hip, msa_refapi.inc,
+// msa_alignapi.inc): symbol codes, CIGAR strings, the border gap, plan descriptions.  Standard C++ only -- no HIP --
+// so that tests/cpp/hostutil_driver.cpp runs every one of them on the CPU under sanitizers.  (msa_refwalk.h: the
+// reference API's own rules, in the same way.)
 #pragma once
 
 #include <algorithm>

@@ -1,7 +1,7 @@
 // msa_rowapi.inc -- C-ABI over rowsweep_kernel (msa_rowsweep.hip): the
 // reference's double-precision tables for any g, h, and its per-row / per-range
 // steps for the source-compatible `class Subproblem` (subproblem_alignment.h).
-// Included by msa_capi.hip after msa_refapi.inc (uses DeviceCall; neither entry reserves a footprint).
+// Included by msa_capi.hip after msa_devcall.inc (uses DeviceCall; neither entry reserves a footprint).
 
 extern "C" {
 

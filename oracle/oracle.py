@@ -110,12 +110,20 @@ def subproblem_tables(A: bytes, B: bytes, start_type=-1, g=1.0, h=2.0, idA=0, id
     return T[0], T[1], T[2], bool(inv.value)
 
 
-def subproblem_align(A: bytes, B: bytes, start_type=-1, end_type=-1, g=1.0, h=2.0, idA=0, idB=0, m=None, n=None):
-    """Tables + find_alignment. Returns dict(nodes=[(i,j,t)...], end=(i,j,t), invert, T1,T2,T3)."""
-    T1, T2, T3, inv = subproblem_tables(A, B, start_type, g, h, idA, idB, m, n)
+def subproblem_align(A: bytes, B: bytes, start_type=-1, end_type=-1, g=1.0, h=2.0, idA=0, idB=0, m=None, n=None,
+                     tables=None):
+    """Tables + find_alignment. Returns dict(nodes=[(i,j,t)...], end=(i,j,t), invert, T1,T2,T3).
+
+    tables: walk these three (m'+1, n'+1) double tables (after the ctor swap) instead of the oracle's own."""
     a, b = _bytes1(A), _bytes1(B)
     m = len(A) - idA if m is None else m
     n = len(B) - idB if n is None else n
+    if tables is None:
+        T1, T2, T3, inv = subproblem_tables(A, B, start_type, g, h, idA, idB, m, n)
+    else:
+        T1, T2, T3 = (np.ascontiguousarray(t, dtype=np.float64) for t in tables)
+        inv = m > n
+        assert T1.shape == T2.shape == T3.shape == (min(m, n) + 1, max(m, n) + 1)
     if inv:
         a, b, m, n, idA, idB = b, a, n, m, idB, idA
     cap = m + n + 2

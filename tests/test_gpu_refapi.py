@@ -95,6 +95,46 @@ def test_one_row_subproblem(oracle, dev, m, n, st, en):
     assert sp.alignment_end.as_tuple() == o["end"]
 
 
+def _subproblem_tables_and_path(A, B, m, n, idA, idB, st, en, g, h):
+    """msa_subproblem asked for T1, T2, T3 and the path in ONE call: the path then comes from the host walk over the
+    int32 tables, not from the device walk.  Returns (tables (3, m'+1, n'+1), nodes, end node, invert)."""
+    import ctypes as C
+
+    from cse305_parallel_sequence_alignment_amd import _lib as LB
+
+    mm, nn = min(m, n), max(m, n)
+    T = np.empty((3, mm + 1, nn + 1), dtype=np.int32)
+    cap = m + n + 2
+    nd, cnt, endn, inv = (LB.Node * cap)(), C.c_size_t(), LB.Node(), C.c_int()
+    LB.check(LB.lib().msa_subproblem(b"\0" + A, b"\0" + B, m, n, idA, idB, st, en, g, h,
+                                     *[T[v].ctypes.data_as(C.c_void_p) for v in range(3)], nd, cap, C.byref(cnt),
+                                     C.byref(endn), C.byref(inv)), "msa_subproblem")
+    return T, [(nd[k].i, nd[k].j, nd[k].t) for k in range(cnt.value)], (endn.i, endn.j, endn.t), bool(inv.value)
+
+
+def test_subproblem_tables_and_path_in_one_call(oracle, dev, dataset):
+    """Tables and node outputs of msa_subproblem together (find_alignment over the de-skewed int32 tables on the
+    host): the five largest reference-produced fixtures -- 127 x 129 and 200 x 130 cross the 64-row stripe boundary
+    -- and a 70 x 90 window of the dataset at (idA, idB) = (2, 1) against the oracle."""
+    paths = {(len(c["A"]), len(c["B"])): c for c in json.loads((GOLDEN / "subproblem_paths.json").read_text())}
+    tabs = np.load(GOLDEN / "subproblem_tables.npz")
+    for shape in ((64, 64), (60, 64), (64, 37), (127, 129), (200, 130)):
+        c = paths[shape]
+        A, B = c["A"].encode(), c["B"].encode()
+        T, nodes, end, inv = _subproblem_tables_and_path(A, B, len(A), len(B), 0, 0, c["start"], c["end"], c["g"],
+                                                         c["h"])
+        assert np.array_equal(T, tabs[c["key"] + "_T"]), c["key"]
+        assert nodes == [tuple(x) for x in c["nodes"]] and end == tuple(c["end_node"]) and inv == c["invert"], c["key"]
+    _, seqs = dataset
+    A, B = seqs[4][:80], seqs[9][:100]
+    o = oracle.subproblem_align(A, B, -1, -2, 1.0, 2.0, idA=2, idB=1, m=70, n=90)
+    T, nodes, end, inv = _subproblem_tables_and_path(A, B, 70, 90, 2, 1, -1, -2, 1.0, 2.0)
+    for x, y in zip(T, (o["T1"], o["T2"], o["T3"])):
+        assert np.array_equal(_as_f64(x), y)
+    assert nodes == o["nodes"] and end == o["end"] and inv == o["invert"]
+    assert any(x[2] == 1 and y[2] == 1 for x, y in zip(nodes, nodes[1:]))  # a T1 -> T1 step: Q2 with idA != idB
+
+
 def test_concurrent_main_alignment(oracle, dev, dataset):
     """Reentrancy: 8 host threads call msa_main_alignment at once (pooled streams and device
     blocks); every call's text is byte-exact."""

@@ -254,6 +254,149 @@ def test_cpp_host_helpers_under_sanitizers():
     assert (r.returncode, r.stdout, r.stderr) == (0, "OK\n", "")
 
 
+MSA_NEG = -(1 << 30)  # -inf of the library's int32 tables (the fixtures and the C-ABI use INT32_MIN)
+NOMATCH = -9
+
+
+def _refwalk(lines):
+    """tests/cpp/refwalk_driver on one command per line: its answers, one per command, and no sanitizer report."""
+    import subprocess
+
+    r = subprocess.run([str(_cpp_driver("refwalk_driver"))], input="".join(lines), capture_output=True, text=True,
+                       timeout=120)
+    assert (r.returncode, r.stderr) == (0, ""), (r.stdout[-500:], r.stderr[-2000:])
+    out = r.stdout.split("END_CASE\n")
+    assert out[-1] == "" and len(out) == len(lines) + 1, r.stdout[-500:]
+    return out[:-1]
+
+
+def _walk_line(kind, T, A, B, idA, idB, end, g, h):
+    """find_alignment over tables T (3, m+1, n+1; -inf as INT32_MIN or -inf) of the window (idA, idB) of A x B, the
+    strings as the Subproblem holds them after its swap: kind "i" as int32 with MSA_NEG, "d" as double."""
+    T = np.asarray(T)
+    m, n = T.shape[1] - 1, T.shape[2] - 1
+    if T.dtype != np.float64:
+        T = np.where(T == np.iinfo(np.int32).min, -np.inf, T.astype(np.float64))
+    if kind == "i":
+        cells = " ".join(str(MSA_NEG if x == -np.inf else int(x)) for x in T.ravel())
+    else:
+        cells = " ".join(float(x).hex() for x in T.ravel())
+    return f"walk {kind} {m} {n} {idA} {idB} {end} {g!r} {h!r} {A} {B} {cells}\n"
+
+
+def _walk_result(block):
+    ln = block.splitlines()
+    if ln[0] != "RC 0":
+        return ln[0], None, None
+    k = int(ln[2].split()[1])
+    assert ln[2].startswith("NODES ") and len(ln) == 3 + k, block[:200]
+    return ln[0], tuple(int(x) for x in ln[1].split()[1:]), [tuple(int(x) for x in r.split()) for r in ln[3:]]
+
+
+def test_reference_walk_rules_under_sanitizers(oracle):
+    """csrc/msa_refwalk.h -- the one host find_alignment (end node, table walk, nodes from ops with quirks Q1 / Q2),
+    solve_order, stitch, the alignment text, partition_from_keys, the borders -- through tests/cpp/refwalk_driver, a
+    stand-alone program built with -fsanitize=address,undefined.  No expected value comes from the code under
+    test: the reference-produced fixtures, the oracle's C restatement, and values written out by hand."""
+    import json
+
+    from conftest import GOLDEN
+
+    lines, checks = ["selftest\n"], [lambda b: b == "SELFTEST OK\n"]
+
+    def walk_case(T, A, B, idA, idB, end, g, h, nodes, end_node, what):
+        def check(b, nodes=nodes, end_node=end_node):
+            rc, e, got = _walk_result(b)
+            return rc == "RC 0" and e == tuple(end_node) and got == [tuple(x) for x in nodes]
+        for kind in ("i", "d") if float(g).is_integer() and float(h).is_integer() and g >= 0 and g + h >= 0 else ("d",):
+            lines.append(_walk_line(kind, T, A, B, idA, idB, end, g, h))
+            checks.append(check)
+            what_of.append((what, kind))
+
+    what_of = [("selftest", "")]
+    # the 41 reference-produced Subproblem paths over their reference-produced tables, as int32 and as double
+    paths = json.loads((GOLDEN / "subproblem_paths.json").read_text())
+    tabs = np.load(GOLDEN / "subproblem_tables.npz")
+    assert len(paths) == 41
+    for c in paths:
+        A, B = (c["B"], c["A"]) if c["invert"] else (c["A"], c["B"])
+        walk_case(tabs[c["key"] + "_T"], A, B, 0, 0, c["end"], c["g"], c["h"], c["nodes"], c["end_node"], c["key"])
+    assert len(lines) == 1 + 2 * 41
+    # non-integral and negative g, h, all 30 cases: the oracle's walk (the C restatement test_oracle_golden.py ties
+    # to the reference) over the reference's own compute_tables() cells, and over the oracle's own tables (the direct
+    # recurrence: other low bits).  Where rounding leaves a cell without a predecessor the reference never returns
+    # and the oracle says so: MSA_ERR_NOMATCH then, in 21 of the 30 over the reference's cells, 12 over the oracle's.
+    f64 = json.loads((GOLDEN / "f64_cases.json").read_text())
+    ftabs = np.load(GOLDEN / "f64_tables.npz")
+    walked = {"ref": 0, "own": 0}
+    for c in f64:
+        A, B = (c["B"], c["A"]) if c["invert"] else (c["A"], c["B"])
+        args = (c["A"].encode(), c["B"].encode(), c["start"], c["end"], c["g"], c["h"])
+        own = oracle.subproblem_tables(*args[:3], *args[4:])
+        assert own[3] == c["invert"]
+        for src, T in (("ref", ftabs[c["key"] + "_C"]), ("own", own[:3])):
+            try:
+                o = oracle.subproblem_align(*args, tables=T)
+                want = ("RC 0", o["end"], o["nodes"])
+                walked[src] += 1
+            except RuntimeError:
+                want = (f"RC {NOMATCH}", None, None)
+            lines.append(_walk_line("d", np.stack(T), A, B, 0, 0, c["end"], c["g"], c["h"]))
+            checks.append(lambda b, want=want: _walk_result(b) == want)
+            what_of.append((c["key"], src))
+    assert len(f64) == 30 and walked == {"ref": 9, "own": 18}
+    # windows with idA != idB, both nonzero: Q2 (a T1 -> T1 step offsets j by idA) shows
+    A, B = b"TTACGTACGTACGTAAGGCATG", b"GACGTACGTACGTTACGTTGCA"
+    q2 = 0
+    for (idA, idB, m, n, st, en) in ((2, 1, 9, 12, -1, -1), (5, 11, 10, 6, -2, 1), (3, 4, 7, 7, 1, -3),
+                                     (1, 6, 12, 13, -3, 2)):
+        o = oracle.subproblem_align(A, B, st, en, 1.0, 2.0, idA=idA, idB=idB, m=m, n=n)
+        a, b, ia, ib = (B, A, idB, idA) if o["invert"] else (A, B, idA, idB)
+        nd = o["nodes"]
+        q2 += sum(1 for x, y in zip(nd, nd[1:]) if x[2] == 1 and y[2] == 1)
+        walk_case(np.stack([o["T1"], o["T2"], o["T3"]]), a.decode(), b.decode(), ia, ib, en, 1.0, 2.0, nd, o["end"],
+                  (idA, idB, m, n))
+    assert q2 >= 3
+    # nodes_from_ops: one walk by hand (window (2, 1) of 3 x 4: T1 -> T1 puts j at 3 + idA, the last step's node is
+    # dropped), then ops that are no walk: none, a first op that is not the end node's table, an unknown byte, ops
+    # past row 0, ops that stop short of the border
+    for ops, want in (("MMDM", "RC 0\nNODES 4\n3 2 1\n0 3 2\n4 5 1\n5 5 1\n"), ("-", None), ("DMMM", None),
+                      ("MXM", None), ("MMMM", None), ("MM", None), ("MMD", None)):
+        lines.append(f"ops 3 4 2 1 5 5 1 {ops}\n")
+        checks.append(lambda b, want=want: b == (want or f"RC {NOMATCH}\n"))
+        what_of.append(("ops", ops))
+    # solve_order: written out in the driver's selftest for num = 1..8; its length is the fixtures' n_solved
+    opt = json.loads((GOLDEN / "optimal.json").read_text())
+    for num in range(1, 9):
+        for fix, key in ((0, "ref"), (1, "fix_all")):
+            solved = {c[key]["n_solved"] for c in opt if len(c["bp"]) - 1 == num}
+            assert len(solved) <= 1
+            lines.append(f"order {num} {fix}\n")
+            checks.append(lambda b, solved=solved: b.startswith("ORDER ") and solved <= {len(b.split()) - 1})
+            what_of.append(("order", (num, fix)))
+    # the alignment text of two partitions whose reference and fix_all outputs differ, from their stitched paths
+    differ = [c for c in opt if c["ref"]["text"] != c["fix_all"]["text"]]
+    for c in (differ[0], differ[-1]):
+        for key in ("ref", "fix_all"):
+            p = c[key]["path"]
+            lines.append(f"text {c[key]['n_solved']} {len(c['A'])} {len(c['B'])} {c['A']} {c['B']} {len(p)} " +
+                         " ".join(f"{i} {j} {t}" for i, j, t in p) + "\n")
+            checks.append(lambda b, want=c[key]["text"]: b == want)
+            what_of.append(("text", key))
+    # partition_from_keys: std::sort's order of tied points past 16 elements.  p > m, n: every band is empty, every
+    # winner the reference's {0, 0, 0} (key 0), and they tie with (0, 0, -1)
+    c = next(c for c in json.loads((GOLDEN / "partial_ties.json").read_text()) if c["differs_from_stable"])
+    m, n, p = len(c["A"]), len(c["B"]), c["p"]
+    assert p > max(m, n) and p + 1 > 16
+    assert sorted(map(tuple, c["partition"])) == sorted([(0, 0, -1), (m, n, 1)] + [(0, 0, 0)] * (p - 1))
+    lines.append(f"part {m} {n} {p} " + " ".join(["0"] * (2 * (p + 1))) + "\n")
+    checks.append(lambda b, c=c: b == f"NODES {p + 1}\n" + "".join(f"{i} {j} {t}\n" for i, j, t in c["partition"]))
+    what_of.append(("part", p))
+
+    for what, block, ok in zip(what_of, _refwalk(lines), checks):
+        assert ok(block), (what, block[:400])
+
+
 def _similarity_reference_loop(s1: bytes, s2: bytes, T: int) -> float:
     """pull_data.cpp:97-125 transcribed as loops (chunking, remainder on chunk T-1, / max length)."""
     L = min(len(s1), len(s2))
