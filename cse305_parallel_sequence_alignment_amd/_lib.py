@@ -26,6 +26,7 @@ STATUS = {
 # msa_alg_e / msa_out_e
 SW_LINEAR, SW_AFFINE, NW_BANDED, REF_GOTOH, PARTIAL, NW_ALIGN, NW_SCORED, NW_FIT = 0, 1, 2, 3, 4, 5, 6, 7
 SW_SCORED = 8
+NW_OVERLAP = 9
 CELLS_NONE, CELLS_H, CELLS_DIR, CELLS_TAB = 0, 1, 2, 3
 
 
@@ -137,6 +138,12 @@ def lib() -> C.CDLL:
     L.msa_nw_align_batch_scored32.argtypes = L.msa_nw_align_batch_scored.argtypes
     L.msa_fit_align32.argtypes = L.msa_fit_align.argtypes
     L.msa_fit_align_batch32.argtypes = L.msa_fit_align_batch.argtypes
+    # overlap alignment: fit's arguments, with {a_beg, b_beg} and {a_end, b_end} for beg_j and end_j (the batch: two
+    # arrays of 2 n_pairs for fit's one)
+    L.msa_overlap_align.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, C.POINTER(i32), P, P, P, sz]
+    L.msa_overlap_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, P, P, P, P, sz, P]
+    L.msa_overlap_align32.argtypes = L.msa_overlap_align.argtypes
+    L.msa_overlap_align_batch32.argtypes = L.msa_overlap_align_batch.argtypes
     # local alignment under a matrix: msa_sw_align's / msa_sw_align_batch's, (alphabet, n_sym, sub) for (match, mismatch)
     L.msa_sw_align_scored.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64),
                                       C.POINTER(i64), C.POINTER(i64), P, sz]
@@ -174,4 +181,5 @@ EXPORTED = [
     "msa_plan_create_scored32", "msa_nw_align_scored32", "msa_nw_align_batch_scored32",
     "msa_fit_align32", "msa_fit_align_batch32",
     "msa_sw_align_scored", "msa_sw_align_batch_scored", "msa_sw_align_scored32", "msa_sw_align_batch_scored32",
+    "msa_overlap_align", "msa_overlap_align_batch", "msa_overlap_align32", "msa_overlap_align_batch32",
 ]

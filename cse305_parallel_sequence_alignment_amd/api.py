@@ -321,7 +321,8 @@ def _entry(name: str, max_symbols: int) -> str:
     if max_symbols == 8:
         return name
     return {"msa_nw_align_scored": "msa_nw_align_scored32", "msa_nw_align_batch_scored": "msa_nw_align_batch_scored32",
-            "msa_fit_align": "msa_fit_align32", "msa_fit_align_batch": "msa_fit_align_batch32"}[name]
+            "msa_fit_align": "msa_fit_align32", "msa_fit_align_batch": "msa_fit_align_batch32",
+            "msa_overlap_align": "msa_overlap_align32", "msa_overlap_align_batch": "msa_overlap_align_batch32"}[name]
 
 
 def _nw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols=8):
@@ -571,3 +572,64 @@ def fit_align_batch(queries, refs, gap_open=3, gap_extend=1, traceback=True, mat
             r["cigar"] = cig.raw[coff[p]:coff[p + 1] - 1].decode()
         out.append(r)
     return out
+
+
+def _overlap_dict(score, beg, end, traceback, cigar):
+    r = dict(score=int(score), a_beg=int(beg[0]) if traceback else None, a_end=int(end[0]),
+             b_beg=int(beg[1]) if traceback else None, b_end=int(end[1]))
+    if traceback:
+        r["cigar"] = cigar
+    return r
+
+
+def overlap_align(A, B, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
+                  matrix=None, max_symbols=8):
+    """Overlap ("dovetail", "ends-free") alignment (build extension, msa_overlap_align): the best alignment of a
+    suffix of one sequence with a prefix of the other, or of one sequence inside the other -> dict(score, a_beg,
+    a_end, b_beg, b_end[, cigar]): ``A[a_beg:a_end]`` against ``B[b_beg:b_end]``.
+
+    All four ends are free: ``a_beg == 0 or b_beg == 0``, and ``a_end == len(A) or b_end == len(B)``.  A gap of L
+    costs (gap_open - gap_extend) + gap_extend * L.  Of equally good end cells one on A's last symbol wins (the
+    leftmost there), then the topmost on B's last symbol.  No positive score: the empty overlap, score 0,
+    ``a_beg == a_end == len(A)``, ``b_beg == b_end == 0`` and an empty CIGAR.  The CIGAR (start -> end, I consumes A,
+    D consumes B) consumes exactly ``a_end - a_beg`` and ``b_end - b_beg``.  ``traceback=False`` gives the score and
+    the two ends only (``a_beg`` and ``b_beg`` are None).  Scoring and ``max_symbols`` as for fit_align."""
+    A, B = _buf(A), _buf(B)
+    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
+    name = _entry("msa_overlap_align", max_symbols)
+    sc = C.c_int32()
+    beg, end = np.zeros(2, dtype=np.int64), np.zeros(2, dtype=np.int64)
+    cap = 4 * (len(A) + len(B)) + 16
+    cig = C.create_string_buffer(cap) if traceback else None
+    LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open,
+                                     gap_extend, C.byref(sc), _i64p(beg), _i64p(end), cig,
+                                     cap if traceback else 0), name)
+    return _overlap_dict(sc.value, beg, end, traceback, cig.value.decode() if traceback else None)
+
+
+def overlap_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
+                        matrix=None, max_symbols=8):
+    """A batch of overlap alignments (msa_overlap_align_batch) -> a list of overlap_align()'s dicts.
+
+    ``Bs``: a list as long as ``As``, or one bytes object every A is aligned against (uploaded once), exactly like
+    nw_align_batch's; scoring as for overlap_align, over one alphabet for the whole call (``match`` / ``mismatch``:
+    the distinct symbols of all As, then all Bs, in first-seen order).  ``max_symbols=32``
+    (msa_overlap_align_batch32): up to 32 symbols in the whole call."""
+    name = _entry("msa_overlap_align_batch", max_symbols)
+    if len(As) == 0:
+        return []
+    A, B, a_off, m, b_off, n = _batch_in(As, Bs)
+    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
+    k = len(m)
+    sc = np.zeros(k, dtype=np.int32)
+    beg = np.zeros((k, 2), dtype=np.int64)
+    end = np.zeros((k, 2), dtype=np.int64)
+    coff = np.zeros(k + 1, dtype=np.int64)
+    cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
+    cig = C.create_string_buffer(cap) if traceback else None
+    LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
+                                     alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend,
+                                     sc.ctypes.data_as(C.c_void_p), _i64p(beg), _i64p(end), cig, cap,
+                                     _i64p(coff) if traceback else None), name)
+    return [_overlap_dict(sc[p], beg[p], end[p], traceback,
+                          cig.raw[coff[p]:coff[p + 1] - 1].decode() if traceback else None) for p in range(k)]

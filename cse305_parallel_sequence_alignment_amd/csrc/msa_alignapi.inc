@@ -5,6 +5,7 @@
 //     msa_nw_align, msa_nw_align_batch                  banded global alignment, +1 / 0
 //     msa_nw_align_scored, ..._batch_scored, *32        ... under match / mismatch scores or a matrix, 8 or 32 symbols
 //     msa_fit_align, msa_fit_align_batch, *32           all of A in a substring of B
+//     msa_overlap_align, msa_overlap_align_batch, *32   a suffix of one sequence against a prefix of the other
 // The host encodes the inputs, runs plans (the flow / band kernels behind msa_plan_run) and the device walks
 // (traceback_kernel, msa_plan_traceback_batch), and turns a walk's O(m + n) ops into a CIGAR.
 namespace {
@@ -50,6 +51,8 @@ struct AlignSpec {
   Border border;            // how the walk's ops become the whole alignment
   bool walk_for_beg;        // the walk is wanted for the start cell too, not only for a CIGAR
   bool wide = false;        // more than 8 symbols: 5-bit codes, tab is 32 x 32
+  bool stop_is_beg = false; // the walk's stop cell (i, j) is the alignment's 0-based start, reported through
+                            // AlignOut::beg where a walk ran (-1, -1 where none did); never a reason to walk
 };
 
 // Smith-Waterman: code 7 is the kernels' out-of-matrix sentinel, so 7 codes
@@ -106,6 +109,15 @@ AlignSpec spec_fit(const char* alphabet, size_t n_sym, const int8_t* sub, size_t
   s.border = BORDER_FIT;
   return s;
 }
+// ... and on A too: a suffix of one sequence against a prefix of the other, or one inside the other.  The walk's ops are
+// the whole alignment (both prefixes are free: nothing is appended) and its stop cell is where the alignment begins
+AlignSpec spec_overlap(const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym = 8) {
+  AlignSpec s = spec_fit(alphabet, n_sym, sub, max_sym);
+  s.alg_walk = s.alg_score = MSA_NW_OVERLAP;
+  s.border = BORDER_NONE;
+  s.stop_is_beg = true;
+  return s;
+}
 
 // The pairs of a call: pair p is A[a_off[p] .. + m[p]) against B[b_off[p] .. + n[p]).
 struct AlignIn {
@@ -136,7 +148,7 @@ struct PairOut {
 };
 struct AlignOut {
   int32_t* score;
-  PairOut end, beg;  // local: the end cell, the start cell
+  PairOut end, beg;  // local: the end cell, the start cell; overlap: {a_end, b_end}, {a_beg, b_beg}
   PairOut span;      // fit: {beg_j, end_j}, beg_j = -1 without a walk
   char* cigars;      // the CIGARs back to back, each with its NUL; cigar_off[np + 1]
   size_t cigar_cap;
@@ -222,6 +234,7 @@ int align_range(const AlignSpec& spec, int single, const GapBand& gb, bool want_
     if (out.score) out.score[p0 + k] = res[(size_t)k].score;
     out.end.put(p0 + k, res[(size_t)k].end_i, res[(size_t)k].end_j);
     out.span.put(p0 + k, -1, res[(size_t)k].end_j);
+    if (spec.stop_is_beg) out.beg.put(p0 + k, -1, -1);
   }
   if (!want_tb) return MSA_OK;
   std::vector<int64_t> info(8 * (size_t)K);
@@ -243,6 +256,7 @@ int align_range(const AlignSpec& spec, int single, const GapBand& gb, bool want_
     const int64_t beg_j = complete_border(o, inf[1] - 1, inf[2] - 1, spec.border);
     if (spec.border == BORDER_FIT) out.span.put(p0 + k, beg_j, res[(size_t)k].end_j);
     if (spec.walk_for_beg) out.beg.put(p0 + k, inf[1], inf[2]);
+    if (spec.stop_is_beg) out.beg.put(p0 + k, inf[1] - 1, inf[2] - 1);
     if (out.cigars) {
       out.cigar_off[p0 + k] = (int64_t)all.size();
       all += cigar_of(o.data(), o.size());
@@ -438,6 +452,59 @@ int msa_fit_align_batch32(const char* A, size_t a_len, const char* B, size_t b_l
   const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
   const AlignOut out{score, PairOut(), PairOut(), PairOut(beg_end), cigars, cigar_cap, cigar_off};
   return align_pairs(spec_fit(alphabet, n_sym, sub, 32), 0, in, kPairLimit, gap_open, gap_extend, -1, out);
+}
+
+// ---- overlap alignment (MSA_NW_OVERLAP): the fit entries with both of A's ends free as well; 8 symbols, or 32 for
+// the *32 entries
+static int overlap_align(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                         const int8_t* sub, size_t max_sym, int32_t gap_open, int32_t gap_extend, int32_t* score,
+                         int64_t* beg_ij, int64_t* end_ij, char* cigar, size_t cigar_cap) {
+  const OnePairIn one(A0, m, B0, n);
+  int64_t coff[2];
+  const AlignOut out{score, PairOut(end_ij), PairOut(beg_ij), PairOut(), cigar, cigar_cap, coff};
+  return align_pairs(spec_overlap(alphabet, n_sym, sub, max_sym), 1, one.in, kPairLimit, gap_open, gap_extend, -1, out);
+}
+static int overlap_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                               const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                               const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym,
+                               int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_ij,
+                               int64_t* end_ij, char* cigars, size_t cigar_cap, int64_t* cigar_off) {
+  if (!beg_ij || !end_ij) return MSA_ERR_ARG;
+  const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  const AlignOut out{score, PairOut(end_ij), PairOut(beg_ij), PairOut(), cigars, cigar_cap, cigar_off};
+  return align_pairs(spec_overlap(alphabet, n_sym, sub, max_sym), 0, in, kPairLimit, gap_open, gap_extend, -1, out);
+}
+
+int msa_overlap_align(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                      const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_ij,
+                      int64_t* end_ij, char* cigar, size_t cigar_cap) {
+  return overlap_align(A0, m, B0, n, alphabet, n_sym, sub, 8, gap_open, gap_extend, score, beg_ij, end_ij, cigar,
+                       cigar_cap);
+}
+
+int msa_overlap_align32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                        const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_ij,
+                        int64_t* end_ij, char* cigar, size_t cigar_cap) {
+  return overlap_align(A0, m, B0, n, alphabet, n_sym, sub, 32, gap_open, gap_extend, score, beg_ij, end_ij, cigar,
+                       cigar_cap);
+}
+
+int msa_overlap_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                            const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                            const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                            int32_t gap_extend, int32_t* score, int64_t* beg_ij, int64_t* end_ij, char* cigars,
+                            size_t cigar_cap, int64_t* cigar_off) {
+  return overlap_align_batch(A, a_len, B, b_len, n_pairs, a_off, m, b_off, n, alphabet, n_sym, sub, 8, gap_open,
+                             gap_extend, score, beg_ij, end_ij, cigars, cigar_cap, cigar_off);
+}
+
+int msa_overlap_align_batch32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                              const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                              const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                              int32_t gap_extend, int32_t* score, int64_t* beg_ij, int64_t* end_ij, char* cigars,
+                              size_t cigar_cap, int64_t* cigar_off) {
+  return overlap_align_batch(A, a_len, B, b_len, n_pairs, a_off, m, b_off, n, alphabet, n_sym, sub, 32, gap_open,
+                             gap_extend, score, beg_ij, end_ij, cigars, cigar_cap, cigar_off);
 }
 
 // ---- local alignment under a substitution matrix (MSA_SW_SCORED): msa_sw_align / msa_sw_align_batch with the

@@ -353,7 +353,7 @@ int nc_of(int alg) {
   switch (alg) {
     case MSA_ALG_SWL: case MSA_ALG_SWL0: case MSA_ALG_SWLP: return 1;
     case MSA_ALG_SWA: case MSA_ALG_NWA: case MSA_ALG_REF1: case MSA_ALG_FIT: case MSA_ALG_NWA32: case MSA_ALG_FIT32:
-    case MSA_ALG_SWS: case MSA_ALG_SWS32:
+    case MSA_ALG_SWS: case MSA_ALG_SWS32: case MSA_ALG_OVL: case MSA_ALG_OVL32:
       return 2;
     default: return 3;
   }
@@ -480,6 +480,16 @@ kfn_t pick_kernel(int alg, int out, int tp, bool sgl) {
     case MSA_ALG_FIT32:
       if (out == MSA_OUT_NONE) return kf<MSA_ALG_FIT32, MSA_OUT_NONE, 0>(sgl);
       if (out == MSA_OUT_DIR) return kf<MSA_ALG_FIT32, MSA_OUT_DIR, 0>(sgl);
+      break;
+    // MSA_NW_OVERLAP: the fit kernels' cell and row search under zero borders on both sides, with the last
+    // column's search in every stripe; instantiations of their own, the MSA_ALG_FIT kernels' code is unchanged
+    case MSA_ALG_OVL:
+      if (out == MSA_OUT_NONE) return kf<MSA_ALG_OVL, MSA_OUT_NONE, 0>(sgl);
+      if (out == MSA_OUT_DIR) return kf<MSA_ALG_OVL, MSA_OUT_DIR, 0>(sgl);
+      break;
+    case MSA_ALG_OVL32:
+      if (out == MSA_OUT_NONE) return kf<MSA_ALG_OVL32, MSA_OUT_NONE, 0>(sgl);
+      if (out == MSA_OUT_DIR) return kf<MSA_ALG_OVL32, MSA_OUT_DIR, 0>(sgl);
       break;
     // MSA_SW_SCORED: the SW-affine cell under the plan's table.  Such a plan always tracks its end cell, so
     // compare-select (1) or the packed key (2) only; the MSA_ALG_SWA kernels' code is unchanged
@@ -718,8 +728,10 @@ int msa_plan_run(msa_plan* P, const uint8_t* dA, const uint8_t* dB, void* c0, vo
     }
     return MSA_OK;
   }
-  // (2: a fit plan's pair result is the first maximum of row m, from the meta of the stripe that holds it)
-  const int sw = (is_linear(P->main.kp.alg) || swaf(P->main.kp.alg)) ? 1 : (fitk(P->main.kp.alg) ? 2 : 0);
+  // (2: a fit plan's pair result is the first maximum of row m, from the meta of the stripe that holds it; 3: an
+  // overlap plan's, that maximum against the last column's, from every stripe's meta)
+  const int sw = (is_linear(P->main.kp.alg) || swaf(P->main.kp.alg)) ? 1
+                 : ovlk(P->main.kp.alg) ? 3 : (fitk(P->main.kp.alg) ? 2 : 0);
   const int np = (int)P->d.n_pairs;
   hipLaunchKernelGGL(reduce_pairs_kernel, dim3(np), dim3(64), 0, st, P->d_pairs, P->d_meta, np, sw,
                      P->d_res);
@@ -878,12 +890,13 @@ int msa_plan_traceback_gotoh(msa_plan* P, int64_t pair, int end_type, const uint
 int msa_plan_traceback_nw(msa_plan* P, int64_t pair, const uint8_t* dDir, uint8_t* d_ops, int64_t ops_cap,
                           int64_t* d_info, void* stream) {
   if (!P || !dDir || !d_ops || !d_info || ops_cap < 0 || pair < 0 || pair >= P->d.n_pairs) return MSA_ERR_ARG;
-  const bool fit = fit_bytes(P);
+  const bool fit = fit_bytes(P) || overlap_bytes(P);
   if (!nw_bytes(P) && !fit) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   P->note_stream(st);
   // stripe starts from the stripe meta (band geometry); the walk needs no end type and no PairResult (a fit plan's
-  // walk, TB_FIT: the same walk from the run's end cell (m, end_j) in its PairResult)
+  // walk, TB_FIT: the same walk from the run's end cell (m, end_j) in its PairResult; an overlap plan's end cell
+  // may lie on the last column instead, (end_i, n), or be the empty overlap's (m, 0), which ends the walk at once)
   hipLaunchKernelGGL((fit ? traceback_kernel<TB_FIT> : traceback_kernel<TB_NW>), dim3(1), dim3(384), 0, st, dDir, P->d_pairs, P->d_meta,
                      (const PairResult*)P->d_res, (int)pair, 0, 0, d_ops, (long long)ops_cap, (long long*)d_info, 0,
                      (const unsigned long long*)nullptr);
@@ -901,7 +914,9 @@ int msa_plan_traceback_batch(msa_plan* P, const uint8_t* dDir, uint8_t* d_ops, c
   // (the SW walk starts at the fill's end cell: plans without track_end have none)
   const bool sw = ((P->d.alg == MSA_SW_AFFINE && P->main.kp.alg == MSA_ALG_SWA) || P->d.alg == MSA_SW_SCORED) &&
                   P->d.cells == MSA_CELLS_DIR && P->d.track_end;
-  const bool fit = fit_bytes(P);  // (the global walk from each pair's end cell (m, end_j))
+  // (the global walk from each pair's end cell: fit (m, end_j); overlap (end_i, end_j), one of them on the last row
+  // or column -- or (m, 0), the empty overlap, whose walk the kernel's own `j > 0` ends before its first step)
+  const bool fit = fit_bytes(P) || overlap_bytes(P);
   if (!nw && !sw && !fit) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   P->note_stream(st);

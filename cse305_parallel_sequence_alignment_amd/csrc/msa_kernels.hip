@@ -98,16 +98,22 @@ template <> struct Tr<MSA_ALG_NWA32> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_FIT32> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_SWS> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_SWS32> { static constexpr int NC = 2; };
+template <> struct Tr<MSA_ALG_OVL> { static constexpr int NC = 2; };
+template <> struct Tr<MSA_ALG_OVL32> { static constexpr int NC = 2; };
 // 5-bit codes: the lane's profile is a 32-byte row of the plan's 32 x 32 table (score4_wide)
-constexpr bool wide(int alg) { return alg == MSA_ALG_NWA32 || alg == MSA_ALG_FIT32 || alg == MSA_ALG_SWS32; }
+constexpr bool wide(int alg) {
+  return alg == MSA_ALG_NWA32 || alg == MSA_ALG_FIT32 || alg == MSA_ALG_SWS32 || alg == MSA_ALG_OVL32;
+}
 // the SW-affine cell with scores from the plan's table (swsc), with those or match / mismatch (swaf): the zero floor,
 // zero borders, best tracking and the virtual columns are the same
 constexpr bool swsc(int alg) { return alg == MSA_ALG_SWS || alg == MSA_ALG_SWS32; }
 constexpr bool swaf(int alg) { return alg == MSA_ALG_SWA || swsc(alg); }
 // the banded Gotoh cell under the global borders (nwg), the same cell under the fit alignment's zero top border
-// (fitk), either (nwa) -- over 3-bit or 5-bit codes
+// (fitk), either (nwa) -- over 3-bit or 5-bit codes.  The overlap kernels (ovlk) are fit kernels -- the zero top border
+// and the row-m maximum are theirs unchanged -- with a zero left border and the last column's maximum besides
 constexpr bool nwg(int alg) { return alg == MSA_ALG_NWA || alg == MSA_ALG_NWA32; }
-constexpr bool fitk(int alg) { return alg == MSA_ALG_FIT || alg == MSA_ALG_FIT32; }
+constexpr bool ovlk(int alg) { return alg == MSA_ALG_OVL || alg == MSA_ALG_OVL32; }
+constexpr bool fitk(int alg) { return alg == MSA_ALG_FIT || alg == MSA_ALG_FIT32 || ovlk(alg); }
 constexpr bool nwa(int alg) { return nwg(alg) || fitk(alg); }
 template <> struct Tr<MSA_ALG_REF> { static constexpr int NC = 3; };
 template <> struct Tr<MSA_ALG_REF1> { static constexpr int NC = 2; };
@@ -292,7 +298,8 @@ __device__ __forceinline__ void border_left(const msa_kparams& kp, int i, int (&
     v[0] = pk16(ALG) ? pk2(kp.gap_open * i) : kp.gap_open * i;  // G(i,0) = H(i,0) + g*i
     v[1] = MSA_NEG;
     v[2] = MSA_NEG;
-  } else if constexpr (swaf(ALG)) {
+  } else if constexpr (swaf(ALG) || ovlk(ALG)) {
+    // (overlap: A's symbols before the aligned suffix are free, as the fit top border's are on B)
     v[0] = 0;        // H
     v[1] = MSA_NEG;  // E
     v[2] = MSA_NEG;  // F
@@ -554,17 +561,21 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
 // final cell at t == tmax.  Cost: 2 compares + 5 selects per step, against ~13 for
 // the range masks -- and for a band the masked head phases are the chain's
 // critical path (stripe k+1 starts ~9 phases into stripe k).
-// (MSA_ALG_FIT, no band: the same two edges are column 0 and column n + 1)
-template <bool FIN, int ALG>
+// (MSA_ALG_FIT, MSA_ALG_OVL, no band: the same two edges are column 0 and column n + 1.  LB is whatever border_left
+// gave the row -- the overlap kernels' zero column enters here and nowhere else -- and the right edge does not depend on
+// the border.)
+// FIN: 0 no capture; 1 the row's state at its last column (t == tmax) into L.fin; 2 its H alone (the overlap kernels'
+// last-column candidate in the stripes that do not hold row m).
+template <int FIN, int ALG>
 __device__ __forceinline__ void band_fix(LaneState<ALG>& L, int t, int (&carry)[3]) {
   static_assert(nwa(ALG), "the Gotoh cell's state order");
   const bool fl = (t == L.tmin - 1);
 #pragma unroll
   for (int v = 0; v < 3; ++v) L.S[v] = fl ? L.LB[v] : L.S[v];
-  if constexpr (FIN) {
+  if constexpr (FIN != 0) {
     const bool e = (t == L.tmax);
 #pragma unroll
-    for (int v = 0; v < 3; ++v) L.fin[v] = e ? L.S[v] : L.fin[v];
+    for (int v = 0; v < (FIN == 1 ? 3 : 1); ++v) L.fin[v] = e ? L.S[v] : L.fin[v];
   }
   const bool fr = (t == L.tmax + 1);
   L.S[0] = fr ? MSA_NEG : L.S[0];
@@ -1218,7 +1229,10 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         constexpr int MMODE = (int)decltype(MASKED_)::value;
         constexpr bool MASKED = MMODE != 0;
         constexpr bool INMASK = decltype(INMASK_)::value;  // input columns beyond the producer's last
-        constexpr bool FIN = decltype(FIN_)::value;        // capture the state at each row's last column
+        // 1 (true): capture the state at each row's last column (the stripe of row m); 2: the overlap kernels' other
+        // stripes, where a masked phase captures H at column n alone (band_fix) and nothing else of FIN applies
+        constexpr int FMODE = (int)decltype(FIN_)::value;
+        constexpr bool FIN = FMODE == 1;
         // ---- all LDS reads of the phase up front (one exposed latency per phase) ----
         int IN[NC][KS];
         {
@@ -1318,7 +1332,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
               }
             } else if constexpr (nwa(ALG) && MASKED) {
               d = step<ALG, OUT, false, TRACKPOS, false>(kp, L, inv, s, t, ct, cr, hv[k]);
-              band_fix<FIN>(L, t, cr);
+              band_fix<FMODE>(L, t, cr);
             } else {
               d = step<ALG, OUT, MASKED, TRACKPOS, FIN>(kp, L, inv, s, t, ct, cr, hv[k]);
             }
@@ -1457,6 +1471,14 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         if constexpr (fitk(ALG)) run_range(qa, qb, F_{}, F_{}, T_{});  // (row m's maximum: every phase)
         else run_range(qa, qb, F_{}, F_{}, F_{});
         run_range(qb, P, T_{}, T_{}, T_{});
+      } else if constexpr (ovlk(ALG)) {
+        // every stripe has column candidates: lane r's row reaches column n at t = tmax = n - cs + r.  mask_hi is
+        // lane 0's tmax less 1 and tmax grows with the lane, so no unmasked phase [qa, qb) holds any row's last
+        // step: the capture lives in the masked head (a short B ends there) and tail alone, and the body is fit's
+        using C_ = std::integral_constant<int, 2>;
+        run_range(0, qa, T_{}, T_{}, C_{});
+        run_range(qa, qb, F_{}, F_{}, F_{});
+        run_range(qb, P, T_{}, T_{}, C_{});
       } else {
         // banded Gotoh, a full stripe away from the matrix borders: lane r's first step is
         // A0 + 2r and its last C0 + 2r, so at a step of the right parity exactly one lane
@@ -1551,6 +1573,22 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
           md->best_j = TRACKPOS ? bj : -1;
         }
       } else {
+        if constexpr (ovlk(ALG)) {
+          // the stripe's last-column candidate: max over its rows i <= m of H(i, n) (L.fin[0], captured at t == tmax
+          // in a masked phase of every stripe), the smaller row on a tie.  Rows past m (the last stripe) never count
+          int b = (L.i <= m) ? L.fin[0] : INT32_MIN;
+          int bi = L.i;
+#pragma unroll
+          for (int off = 32; off >= 1; off >>= 1) {
+            const int ob = __shfl_xor(b, off);
+            const int oi = __shfl_xor(bi, off);
+            if (ob > b || (ob == b && oi < bi)) { b = ob; bi = oi; }
+          }
+          if (lane == 0) {
+            md->col_best = b;
+            md->col_i = bi;
+          }
+        }
         if (L.i == m) {
           if constexpr (fitk(ALG)) {
             md->best = L.best;
@@ -1785,7 +1823,8 @@ __global__ __launch_bounds__(256) void chunk_add_kernel(int32_t* H, const int16_
 
 __global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* pairs, const msa_stripe_meta* meta,
                                                          int n_pairs, int sw, PairResult* out) {
-  // sw: 1 Smith-Waterman (the best cell of any stripe), 0 global (the final state at (m, n)), 2 fit alignment
+  // sw: 1 Smith-Waterman (the best cell of any stripe), 0 global (the final state at (m, n)), 2 fit alignment,
+  // 3 overlap alignment (fit's row-m maximum against the best last-column candidate of any stripe)
   // one wave per pair: lanes stride over the pair's stripes (a serial loop of
   // dependent meta loads took ~27 us for a 157-stripe pair)
   const int p = blockIdx.x;
@@ -1822,11 +1861,37 @@ __global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* p
     r.end_i = pd.m;
     r.end_j = pd.n;
     r.status = md.has_fin ? 0 : -1;
-    if (sw == 2) {
+    if (sw == 2 || sw == 3) {
       // fit alignment: the first maximum of row m, found by the stripe of row m (fin stays (H, E, F) at (m, n),
       // which is not part of this algorithm's result)
       r.score = md.best;
       r.end_j = md.best_j;
+    }
+    if (sw == 3) {
+      // overlap alignment: the column candidates H(i, n), one per stripe (its maximum, its smallest row); lanes
+      // stride over the stripes -- rows increase with s, so a lane keeps its first maximum with a strict > -- and
+      // the smaller row wins a tie across lanes
+      int b = INT32_MIN, bi = 0;
+      for (int s = lane; s < S; s += 64) {
+        const msa_stripe_meta& mc = meta[pd.stripe0 + s];
+        if (mc.col_best > b) { b = mc.col_best; bi = mc.col_i; }
+      }
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        const int ob = __shfl_xor(b, off), oi = __shfl_xor(bi, off);
+        if (ob > b || (ob == b && oi < bi)) { b = ob; bi = oi; }
+      }
+      // the last row wins a tie with the last column; nothing positive: the empty overlap, score 0 at (m, 0)
+      if (b > r.score) {
+        r.score = b;
+        r.end_i = bi;
+        r.end_j = pd.n;
+      }
+      if (r.score <= 0) {
+        r.score = 0;
+        r.end_i = pd.m;
+        r.end_j = 0;
+      }
     }
   }
   if (lane == 0) out[p] = r;

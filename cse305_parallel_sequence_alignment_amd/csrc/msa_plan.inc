@@ -157,9 +157,13 @@ bool nw_bytes(const msa_plan* P) {
 }
 // ... the fit alignment's (the same bytes; the walks start at each pair's end cell (m, end_j))
 bool fit_bytes(const msa_plan* P) { return P->d.alg == MSA_NW_FIT && P->d.cells == MSA_CELLS_DIR; }
+// ... the overlap alignment's (the same bytes again; the walks start at each pair's end cell on the last row or column)
+bool overlap_bytes(const msa_plan* P) { return P->d.alg == MSA_NW_OVERLAP && P->d.cells == MSA_CELLS_DIR; }
+// the algorithms that score as MSA_NW_SCORED does (table or match / mismatch) under free ends, on the stripe kernel alone
+bool free_ends(int alg) { return alg == MSA_NW_FIT || alg == MSA_NW_OVERLAP; }
 
 // ---- step 1: kernel algorithm and end-cell tracking mode --------------------------------------------
-// wide32: a 32 x 32 table over 5-bit codes (msa_plan_create_scored32: MSA_NW_SCORED and MSA_NW_FIT only)
+// wide32: a 32 x 32 table over 5-bit codes (msa_plan_create_scored32: MSA_NW_SCORED, MSA_NW_FIT, MSA_NW_OVERLAP only)
 // sw_smax: max(0, the largest table entry over real codes) of an MSA_SW_SCORED plan (unused by every other plan)
 int choose_algorithm(const msa_plan_desc* desc, bool wide32, int sw_smax, int& kalg, int& tp) {
   const int out_mode = desc->cells;
@@ -212,6 +216,15 @@ int choose_algorithm(const msa_plan_desc* desc, bool wide32, int sw_smax, int& k
       // algorithm of its own (new stripe_kernel instantiations).  No band (|i - j| <= band means nothing when the
       // reference's ends are free), direction bytes or the score alone
       kalg = wide32 ? MSA_ALG_FIT32 : MSA_ALG_FIT;
+      if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->gap_extend < 0 ||
+          desc->gap_open < desc->gap_extend || desc->band != -1)
+        return MSA_ERR_UNSUPPORTED;
+      break;
+    case MSA_NW_OVERLAP:
+      // MSA_NW_FIT's cell and rules under zero borders on the top AND the left, with the better of row m's and
+      // column n's first maxima as the result: kernel algorithms of their own again.  No band, direction bytes or
+      // the score alone; which ends are free is not selectable
+      kalg = wide32 ? MSA_ALG_OVL32 : MSA_ALG_OVL;
       if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->gap_extend < 0 ||
           desc->gap_open < desc->gap_extend || desc->band != -1)
         return MSA_ERR_UNSUPPORTED;
@@ -304,6 +317,9 @@ int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t*
       // MSA_NW_FIT (MSA_ALG_FIT, stripe_kernel only, unshifted) adds one source, its top border H(0, j) = 0: within
       // the bound like the corner's 0.  Its paths, steps, left border and -inf are the unbanded MSA_ALG_NWA's, and
       // what it forms beside the cells is a copy of one of them (the row-m maximum): the same inequality holds.
+      // MSA_NW_OVERLAP (MSA_ALG_OVL) replaces the left border's -h - g i by one more zero source, H(i, 0) = 0 with
+      // E = F = -inf: inside the bound that the replaced border needed.  Paths, steps and -inf are unchanged, and the
+      // last-column maxima are copies of cells again: the same inequality holds.
       // The 32-code kernels (MSA_ALG_NWA32, MSA_ALG_FIT32: stripe_kernel, unshifted, raw S) differ in where a step's
       // S comes from, not in what a step is: the same inequality with s over the 1,024 scores.
       const int64_t s = sub_abs_max(scored, wide(kp.alg) ? 1024 : 64), g = kp.gap_ext, h = kp.h, G = kp.gap_open;
@@ -448,7 +464,7 @@ PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp, int smax) {
   for (int64_t p = 1; p < desc->n_pairs; ++p) eq_m = eq_m && desc->m[p] == desc->m[0];
   if (eq_m && batch_items(desc, kalg) < slots && stripes_of(desc->m[0]) >= 2 * MSA_WAVES_BATCH && band < 0 &&
       desc->alg != MSA_NW_ALIGN && desc->alg != MSA_NW_SCORED &&  // (a batch of global alignments with direction
-      desc->alg != MSA_NW_FIT)                                    // bytes, scored or fit: whole pairs per workgroup)
+      !free_ends(desc->alg))                             // bytes, scored, fit or overlap: whole pairs per workgroup)
     return PM_SPLIT;
   return PM_STRIPE;
 }
@@ -766,7 +782,8 @@ int alloc_buffers(msa_plan& P) {
     // the 32 x 32 table as it is: stripe_kernel's bytes are the raw S (each workgroup copies it to LDS)
     if (!P.alloc(&P.d_sub, sizeof(P.sub))) return MSA_ERR_HIP;
     HIPCHK(hipMemcpy(P.d_sub, P.sub, sizeof(P.sub), hipMemcpyHostToDevice));
-  } else if (P.main.kp.alg == MSA_ALG_NWA || P.main.kp.alg == MSA_ALG_FIT || P.main.kp.alg == MSA_ALG_SWS) {
+  } else if (P.main.kp.alg == MSA_ALG_NWA || P.main.kp.alg == MSA_ALG_FIT || P.main.kp.alg == MSA_ALG_OVL ||
+             P.main.kp.alg == MSA_ALG_SWS) {
     // (MSA_ALG_SWS: stripe_kernel, so the raw S -- with plan_create's MSA_VIRT_SCORE in column 7)
     // the substitution table, one 8-byte profile per row code: band_kernel's bytes are S + 2g + h (its values are
     // shifted by g (i + j); wrapped to a byte as the kernel's own arithmetic did for the 1 / 0 plans), stripe_kernel's S
@@ -849,7 +866,7 @@ int msa_plan_create_scored32(const msa_plan_desc* desc, const int8_t* sub32, msa
 static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32, msa_plan** out) {
   if (!desc || !out || desc->n_pairs <= 0 || !desc->m || !desc->n || !desc->a_off || !desc->b_off) return MSA_ERR_ARG;
   const bool sw_scored = desc->alg == MSA_SW_SCORED;
-  if (sub && desc->alg != MSA_NW_SCORED && desc->alg != MSA_NW_FIT && !sw_scored) return MSA_ERR_UNSUPPORTED;
+  if (sub && desc->alg != MSA_NW_SCORED && !free_ends(desc->alg) && !sw_scored) return MSA_ERR_UNSUPPORTED;
   int rc = ensure_device();
   if (rc != MSA_OK) return rc;
   // (a plan without device buffers yet destroys cleanly: no streams, no blocks, null events)
@@ -887,8 +904,9 @@ static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32
   P->nc = nc_of(kalg);
   if (nwg(kalg) && P->main.kp.h < 0) return MSA_ERR_UNSUPPORTED;
   // the substitution scores of the banded recurrence: MSA_NW_SCORED's table, or its match / mismatch; 1 / 0 for
-  // MSA_NW_BANDED and MSA_NW_ALIGN, whatever their description says; MSA_NW_FIT scores as MSA_NW_SCORED does
-  const bool scored = desc->alg == MSA_NW_SCORED || desc->alg == MSA_NW_FIT;
+  // MSA_NW_BANDED and MSA_NW_ALIGN, whatever their description says; MSA_NW_FIT and MSA_NW_OVERLAP score as
+  // MSA_NW_SCORED does
+  const bool scored = desc->alg == MSA_NW_SCORED || free_ends(desc->alg);
   int smax = 0;
   if (scored && !sub && (desc->match < -128 || desc->match > 127 || desc->mismatch < -128 || desc->mismatch > 127))
     return MSA_ERR_UNSUPPORTED;

@@ -91,7 +91,10 @@ __global__ __launch_bounds__(64 * TBB_WPB) void traceback_batch_kernel(
     const PairResult r0 = res[pair];
     i = (int)r0.end_i;
     j = (int)r0.end_j;
-    walk = KIND == TB_FIT || r0.score > 0;  // (a fit alignment exists whatever its score)
+    // (a fit alignment exists whatever its score.  An overlap plan's pairs walk as TB_FIT too: its empty overlap --
+    // score 0, the only score <= 0 it reports -- has the end cell (m, 0), so `j > 0` below ends that walk before its
+    // first step with n_ops 0; no score test is needed, and none is passed in)
+    walk = KIND == TB_FIT || r0.score > 0;
     // (an end cell outside the matrix: the plan has not run)
     if (r0.end_i < 0 || r0.end_i > pd.m || r0.end_j < 0 || r0.end_j > pd.n) {
       status = MSA_ERR_ARG;

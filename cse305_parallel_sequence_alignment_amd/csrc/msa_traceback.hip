@@ -134,7 +134,8 @@ __device__ __forceinline__ int ref_end_state(const int32_t (&fin)[3], int end_ty
 // Walk kinds: Smith-Waterman affine; the reference's Gotoh walk over table numbers (REF
 // fill) or over tags (REF1 fill, tag = 4 - table); the global walk over SW-affine bytes (MSA_NW_ALIGN).
 // TB_FIT (MSA_NW_FIT plans): TB_NW's walk -- words, state machine, stop rule -- started at the run's end cell
-// (m, end_j) from the pair's PairResult instead of (m, n).
+// (m, end_j) from the pair's PairResult instead of (m, n).  MSA_NW_OVERLAP plans walk as TB_FIT too: their end cell
+// is (m, end_j) or (end_i, n), or the empty overlap's (m, 0), where the walk loop's `j > 0` ends the walk at once.
 enum { TB_SW = 0, TB_REF = 1, TB_REF_TAG = 2, TB_NW = 3, TB_FIT = 4 };
 
 // The transition word of a cell (see the window comment in traceback_kernel): three 10-bit

@@ -32,6 +32,11 @@ enum msa_alg {
                        // the plan's 8 x 8 table (MSA_SW_SCORED plans, stripe_kernel only): real codes 0..6, column 7
                        // of every row = MSA_VIRT_SCORE (the host-side table builder fills it in)
   MSA_ALG_SWS32 = 12,  // MSA_ALG_SWS over 5-bit codes under the 32 x 32 table: real codes 0..30, the virtual code 31
+  MSA_ALG_OVL = 13,    // MSA_ALG_FIT's cell, zero top border and row-m maximum under a zero LEFT border too, H(i, 0) = 0
+                       // (MSA_NW_OVERLAP plans): a suffix of one sequence against a prefix of the other.  Every lane of
+                       // every stripe also keeps H of its row at column n; the stripe's maximum of them (the smaller
+                       // row on a tie) goes to the stripe meta's col_best / col_i
+  MSA_ALG_OVL32 = 14,  // MSA_ALG_OVL over 5-bit codes, as MSA_ALG_FIT32
 };
 
 // Per-cell outputs.
@@ -43,7 +48,7 @@ enum msa_out {
 };
 
 // One pair of sequences inside a launch.  Codes are uint8 in [0,8) ([0,32): MSA_ALG_NWA32, MSA_ALG_FIT32,
-// MSA_ALG_SWS32).
+// MSA_ALG_OVL32, MSA_ALG_SWS32).
 typedef struct msa_pair_desc {
   int64_t a_off;       // offset of row codes (A[0] = row 1) in the A code array
   int64_t b_off;       // offset of column codes (B[0] = column 1) in the B code array
@@ -58,12 +63,14 @@ typedef struct msa_pair_desc {
 typedef struct msa_stripe_meta {
   int32_t cs;          // column processed by lane 0 at step 0 (lane r: cs + t - r)
   int32_t phases;      // phases the stripe ran
-  int32_t best;        // SW: best H in the stripe (INT32_MIN if none); FIT, the stripe of row m: max H(m, 1..n)
-  int32_t best_i;      // SW: row of the best (first max, row-major); FIT: m
-  int32_t best_j;      // SW: column of the best; FIT: the smallest column attaining it
+  int32_t best;        // SW: best H in the stripe (INT32_MIN if none); FIT / OVL, the stripe of row m: max H(m, 1..n)
+  int32_t best_i;      // SW: row of the best (first max, row-major); FIT / OVL: m
+  int32_t best_j;      // SW: column of the best; FIT / OVL: the smallest column attaining it
   int32_t fin[3];      // global: state at (m, n) if this stripe holds row m (FIT too: not part of its result)
   int32_t has_fin;
-  int32_t pad[3];
+  int32_t col_best;    // OVL: max over the stripe's rows i <= m of H(i, n) (else unused, 0)
+  int32_t col_i;       // OVL: the smallest row attaining it
+  int32_t pad;
 } msa_stripe_meta;
 
 // Launch-wide scoring / geometry.

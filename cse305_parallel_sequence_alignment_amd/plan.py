@@ -51,13 +51,16 @@ class Plan:
 
     def __init__(self, alg: int, cells: int, ms, ns, a_offs, b_offs, match=1, mismatch=0, gap_open=1,
                  gap_extend=1, start_type=-1, band=-1, track_end=False, single=None, sub=None):
-        """``sub`` (NW_SCORED, NW_FIT and SW_SCORED only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code
+        """``sub`` (NW_SCORED, NW_FIT, NW_OVERLAP and SW_SCORED only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code
         a against column code b (msa_plan_create_scored); None scores ``match`` on the diagonal and ``mismatch``
         elsewhere.  A 32 x 32 ``sub`` makes a plan over 5-bit codes (msa_plan_create_scored32: inputs in [0, 32), always the
         stripe kernel); any other shape is a ValueError.
         An NW_FIT plan (all of A against a substring of B: ``band`` -1, CELLS_DIR or CELLS_NONE) reports in
         ``results()`` the score and ``end = (m, end_j)``, the first column of row m's maximum; ``traceback_nw`` and
         ``traceback_batch`` walk from there.
+        An NW_OVERLAP plan (a suffix of one sequence against a prefix of the other: NW_FIT's rules) reports the score
+        and its end cell ``end = (end_i, end_j)`` on the last row or column -- ``(m, 0)`` with score 0 for the empty
+        overlap --; the same two walks start there, append nothing, and their ``stop`` is where the alignment begins.
         An SW_SCORED plan (SW_AFFINE's recurrence under the table: ``band`` -1, CELLS_DIR or CELLS_NONE) keeps the
         highest code, 7 or 31, as the kernels' out-of-matrix sentinel: inputs are codes 0..6 / 0..30 and ``sub``'s last
         row and column are ignored.  It always tracks its end cell and runs the stripe kernel; ``traceback``,
@@ -302,7 +305,10 @@ class Plan:
     def _border_gap(self, i: int, j: int) -> bytes:
         """The ops a global walk that stopped on the matrix border at (i, j) still lacks: i x 'I' or j x 'D'.  An
         NW_FIT plan's alignment starts at reference column j for free: only the 'I' gap (the query overhangs the
-        reference's start) is appended, and ``stop[1]`` is where the aligned substring begins."""
+        reference's start) is appended, and ``stop[1]`` is where the aligned substring begins.  An NW_OVERLAP plan's
+        alignment starts at the stop cell itself: nothing is appended."""
+        if self.alg == LB.NW_OVERLAP:
+            return b""
         if i > 0:
             return b"I" * i
         return b"" if self.alg == LB.NW_FIT else b"D" * max(j, 0)
@@ -363,7 +369,7 @@ class Plan:
             LB.check(int(inf[k, 3]), "msa_plan_traceback_batch")
             o = oh[off[k]:off[k] + int(inf[k, 0])].tobytes()
             stats = dict(switches=int(inf[k, 4]), staged=int(inf[k, 5]), ticks=int(inf[k, 6]))
-            if self.alg in (LB.NW_ALIGN, LB.NW_SCORED, LB.NW_FIT):
+            if self.alg in (LB.NW_ALIGN, LB.NW_SCORED, LB.NW_FIT, LB.NW_OVERLAP):
                 i, j = int(inf[k, 1]) - 1, int(inf[k, 2]) - 1
                 o += self._border_gap(i, j)
                 out.append(dict(ops=o, stop=(i, j), cigar=cigar_of(o), stats=stats))

@@ -46,6 +46,9 @@
  *                        best, with the reference span and the CIGAR (build extension: MSA_NW_FIT plans --
  *                        a zero top border, the first maximum of row m found inside the fill kernel, and
  *                        the two global walks started at that cell)
+ *   msa_overlap_align, msa_overlap_align_batch, msa_overlap_align32, msa_overlap_align_batch32
+ *                        overlap ("dovetail", "ends-free") alignment: a suffix of one sequence against a prefix
+ *                        of the other, or one inside the other (build extension: MSA_NW_OVERLAP plans)
  *   msa_plan_create_scored32, msa_nw_align_scored32, msa_nw_align_batch_scored32, msa_fit_align32,
  *   msa_fit_align_batch32
  *                        MSA_NW_SCORED and MSA_NW_FIT over alphabets of up to 32 symbols (proteins, IUPAC DNA):
@@ -249,12 +252,15 @@ typedef enum msa_alg_e {
   MSA_NW_FIT = 7,     /* fit ("glocal", "semi-global", "infix") alignment: all of A against a substring of B that
                          the alignment chooses, MSA_NW_SCORED's cells under a zero top border; the contract is
                          at msa_fit_align below.  band = -1, MSA_CELLS_DIR or MSA_CELLS_NONE */
-  MSA_SW_SCORED = 8   /* MSA_SW_AFFINE's recurrence with f(i,j) = S[code of A_i][code of B_j]: the same zero floor,
+  MSA_SW_SCORED = 8,  /* MSA_SW_AFFINE's recurrence with f(i,j) = S[code of A_i][code of B_j]: the same zero floor,
                          borders, direction byte (h == 0 -> 0, then diagonal, E, F; bits 2 / 3 "open wins a tie"), end
                          cell (first maximum, row-major) and walk.  S from match / mismatch, or a table
                          (msa_plan_create_scored: 8 x 8, inputs are codes 0..6; msa_plan_create_scored32: 32 x 32,
                          codes 0..30 -- the highest code is the out-of-matrix sentinel's).  The contract is at
                          msa_plan_create_scored below */
+  MSA_NW_OVERLAP = 9  /* overlap ("dovetail", "ends-free") alignment: MSA_NW_FIT's cells under zero borders on the top
+                         AND the left, ending anywhere on the last row or the last column; the contract is at
+                         msa_overlap_align below.  band = -1, MSA_CELLS_DIR or MSA_CELLS_NONE */
 } msa_alg_e;
 
 typedef enum msa_out_e { MSA_CELLS_NONE = 0, MSA_CELLS_H = 1, MSA_CELLS_DIR = 2, MSA_CELLS_TAB = 3 } msa_out_e;
@@ -279,7 +285,8 @@ typedef struct msa_plan_desc {
 typedef struct msa_pair_result {
   int32_t score;
   int32_t status;
-  int64_t end_i, end_j;  /* SW: end cell; Gotoh: (m, n); MSA_NW_FIT: (m, first column of row m's maximum) */
+  int64_t end_i, end_j;  /* SW: end cell; Gotoh: (m, n); MSA_NW_FIT: (m, first column of row m's maximum);
+                            MSA_NW_OVERLAP: the end cell on row m or column n, or (m, 0) with score 0 */
   int32_t fin[3];        /* Gotoh: state at (m, n) (T1,T2,T3 / H,E,F); MSA_NW_FIT: the same cell's (H,E,F), which
                             is not part of that algorithm's result */
   int32_t pad;
@@ -298,7 +305,8 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** plan);
  * for every pair (the derivation is at check_ranges, msa_plan.inc); anything else is MSA_ERR_UNSUPPORTED.  The
  * band rule and its MSA_ERR_ARG are MSA_NW_ALIGN's.  MSA_NW_FIT takes a table (or NULL: match / mismatch) in the
  * same way and under the same inequality (its zero top border is within the bound); it is MSA_ERR_UNSUPPORTED
- * with any band but -1 and with cells other than MSA_CELLS_DIR / MSA_CELLS_NONE.
+ * with any band but -1 and with cells other than MSA_CELLS_DIR / MSA_CELLS_NONE.  MSA_NW_OVERLAP: exactly
+ * MSA_NW_FIT's rules and errors (its zero left border is within the bound too).
  * MSA_SW_SCORED takes a table too (NULL: desc->match on the diagonal, desc->mismatch elsewhere, in [-128, 127]; the
  * results are then an MSA_SW_AFFINE plan's).  The kernels keep their out-of-matrix sentinel: code 7 is the virtual
  * column's, the inputs are codes 0..6 -- 7 symbols --, table entries with either index 7 are ignored, and the launch's
@@ -313,9 +321,9 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** plan);
  * msa_plan_traceback_nw and msa_plan_traceback_gotoh reject it with MSA_ERR_UNSUPPORTED.  A non-NULL sub with
  * MSA_SW_AFFINE stays MSA_ERR_UNSUPPORTED, and MSA_SW_AFFINE plans choose their kernels as before. */
 int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_plan** plan);
-/* MSA_NW_SCORED and MSA_NW_FIT over 5-bit codes: sub32 = 1,024 scores, row-major sub32[32*a + b] = the score of A's
- * code a against B's code b.  The inputs of msa_plan_run are codes in [0, 32).  desc->alg must be MSA_NW_SCORED or
- * MSA_NW_FIT (anything else: MSA_ERR_UNSUPPORTED); sub32 == NULL is MSA_ERR_ARG.  Cells, band and gap rules, the
+/* MSA_NW_SCORED, MSA_NW_FIT and MSA_NW_OVERLAP over 5-bit codes: sub32 = 1,024 scores, row-major sub32[32*a + b] = the
+ * score of A's code a against B's code b.  The inputs of msa_plan_run are codes in [0, 32).  desc->alg must be one of
+ * those three (anything else but MSA_SW_SCORED, below: MSA_ERR_UNSUPPORTED); sub32 == NULL is MSA_ERR_ARG.  Cells, band and gap rules, the
  * value-range inequality (s = the largest |score| of the 1,024) and their errors are msa_plan_create_scored's.
  * Such a plan always launches the stripe kernel (msa_plan_launch_info mode 0): one pair, a batch, any band (a banded
  * single pair runs the exact masked stripe launch).  msa_plan_format_info reports it in its fourth word;
@@ -426,7 +434,10 @@ int msa_plan_traceback_gotoh(msa_plan* plan, int64_t pair, int end_type, const u
  * or MSA_NW_SCORED with direction bytes; msa_plan_traceback and msa_plan_traceback_gotoh reject both.
  * An MSA_NW_FIT plan with direction bytes is walked too: the same walk, started at the pair's end cell (m, end_j)
  * from the run's result (an end cell outside the matrix -- the plan has not run -- is status MSA_ERR_ARG); the
- * caller appends only the i x 'I' border gap, and the stop column j is where the aligned substring begins. */
+ * caller appends only the i x 'I' border gap, and the stop column j is where the aligned substring begins.
+ * An MSA_NW_OVERLAP plan with direction bytes likewise, from its end cell (end_i, end_j) on the last row or column;
+ * nothing is appended, and the stop cell (i, j) is where the alignment begins.  Its empty overlap -- end cell (m, 0)
+ * -- is no walk: n_ops 0, stop cell (m, 0), status 0.  msa_plan_traceback and msa_plan_traceback_gotoh reject it. */
 int msa_plan_traceback_nw(msa_plan* plan, int64_t pair, const uint8_t* dDir, uint8_t* d_ops, int64_t ops_cap,
                           int64_t* d_info, void* stream);
 /* Every pair's traceback ON THE DEVICE in ONE launch (msa_tbatch.hip), after msa_plan_run on the same
@@ -434,7 +445,8 @@ int msa_plan_traceback_nw(msa_plan* plan, int64_t pair, const uint8_t* dDir, uin
  * its own ops (the single walkers above spend a six-wave workgroup on one long walk and take a launch
  * per pair).  Plans: MSA_SW_AFFINE with MSA_CELLS_DIR and track_end, or MSA_SW_SCORED with MSA_CELLS_DIR (msa_plan_traceback's walk, from each
  * pair's end cell; no walk for a score <= 0) or MSA_NW_ALIGN / MSA_NW_SCORED (msa_plan_traceback_nw's walk, from (m, n) to
- * the matrix border; the caller appends the border gap; MSA_NW_FIT: that walk from each pair's (m, end_j)), laid
+ * the matrix border; the caller appends the border gap; MSA_NW_FIT: that walk from each pair's (m, end_j);
+ * MSA_NW_OVERLAP: from each pair's (end_i, end_j), n_ops 0 for an empty overlap), laid
  * out one row per lane with the stripe starts
  * in the stripe meta: the stripe kernel's batch, split-batch and single launches and the band kernel's.
  * MSA_ERR_UNSUPPORTED, before any launch, for the flow kernels' plans (msa_plan_launch_info mode 1: the
@@ -548,7 +560,8 @@ int msa_nw_align_batch_scored(const char* A, size_t a_len, const char* B, size_t
  *   A plan reports PairResult{score, status, end_i = m, end_j}; fin[] holds (H, E, F) at (m, n) as a global plan's
  *   does and is not part of this algorithm's result.
  *   Out of scope, each MSA_ERR_UNSUPPORTED at plan creation: any band other than -1 (|i - j| <= band means nothing
- *   here), cells other than MSA_CELLS_DIR / MSA_CELLS_NONE, free ends on A.  Such plans always run the stripe
+ *   here), cells other than MSA_CELLS_DIR / MSA_CELLS_NONE, free ends on A (those are MSA_NW_OVERLAP's, below, with
+ *   all four ends free at once).  Such plans always run the stripe
  *   kernel (msa_plan_launch_info mode 0), one pair or a batch.
  * msa_fit_align / msa_fit_align_batch behave as msa_nw_align_scored / msa_nw_align_batch_scored (alphabet, matrix
  * and range errors; admission against the device budget, here with the full m x n bytes; chunks of consecutive
@@ -566,6 +579,56 @@ int msa_fit_align_batch(const char* A, size_t a_len, const char* B, size_t b_len
                         const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
                         int32_t gap_extend, int32_t* score, int64_t* beg_end /* 2 n_pairs: {beg_j, end_j} */,
                         char* cigars, size_t cigar_cap, int64_t* cigar_off);
+
+/* Overlap alignment (build extension: MSA_NW_OVERLAP plans; other tools say "dovetail", "ends-free" or "semi-global
+ * with all four ends free"): the best alignment of a SUFFIX of one sequence with a PREFIX of the other, or of one
+ * sequence contained in the other.  The contract:
+ *   Inputs: A (m >= 1) and B (n >= 1); a score table S as for MSA_NW_SCORED (int8, 8 x 8 or 32 x 32, or match /
+ *   mismatch); g = gap_extend >= 0, h = gap_open - gap_extend >= 0, a gap of length L costs h + g L.
+ *     H(0, j) = 0  (0 <= j <= n)      H(i, 0) = 0  (1 <= i <= m)
+ *     E = F = -inf on both borders
+ *     E, F, H of interior cells, the direction byte and every tie rule: msa_plan_traceback_nw's text above
+ *     row candidates:    H(m, j), 1 <= j <= n;  best_r = their maximum, j_r the SMALLEST j attaining it
+ *     column candidates: H(i, n), 1 <= i <= m;  best_c = their maximum, i_c the SMALLEST i attaining it
+ *     best = max(best_r, best_c)
+ *     end cell = (m, j_r) if best_r >= best_c, else (i_c, n)      (the last row wins a tie)
+ *     if best <= 0: the empty overlap -- score 0, end cell (m, 0), no walk, empty CIGAR
+ *     else:         score = best
+ *   The walk is msa_plan_traceback_nw's, started at the end cell in state H; it stops as soon as i == 0 or j == 0,
+ *   at the stop cell (i, j).  NOTHING is appended: both prefixes are free.
+ *   The result is (score, a_beg = i, a_end = end_i, b_beg = j, b_end = end_j): A[a_beg, a_end) against
+ *   B[b_beg, b_end), 0-based and half open, with a_beg == 0 or b_beg == 0, and a_end == m or b_end == n; the CIGAR
+ *   (start -> end, run-length M/I/D, I consumes A) consumes exactly a_end - a_beg and b_end - b_beg.  The empty
+ *   overlap is (0, m, m, 0, 0).
+ *   A plan reports PairResult{score, status, end_i, end_j}; fin[] holds (H, E, F) at (m, n) as a fit plan's does
+ *   and is not part of this algorithm's result.
+ *   Out of scope, each MSA_ERR_UNSUPPORTED at plan creation: any band other than -1, cells other than
+ *   MSA_CELLS_DIR / MSA_CELLS_NONE; which ends are free is not selectable (MSA_NW_FIT frees B's alone).  Such plans
+ *   always run the stripe kernel (msa_plan_launch_info mode 0), one pair or a batch, never a split batch, and the
+ *   value-range inequality of msa_plan_create_scored holds unchanged (zero borders are inside its bound).
+ * The entries behave as msa_fit_align / msa_fit_align_batch and their *32 twins in everything else, in the order
+ * documented there: argument, alphabet and range errors decided on the host; admission with the full m x n bytes;
+ * chunks of consecutive pairs within a quarter of the budget; a B shared by every pair uploaded once;
+ * MSA_ERR_CAPACITY, the batch with the needed size in cigar_off[n_pairs].  *score, beg_ij[2] = {a_beg, b_beg},
+ * end_ij[2] = {a_end, b_end} (each may be NULL) / score (n_pairs), beg_ij and end_ij (2 n_pairs each, required).
+ * cigar(s) == NULL: scores and end cells from plans without direction bytes, beg_ij = {-1, -1}. */
+int msa_overlap_align(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                      const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_ij,
+                      int64_t* end_ij, char* cigar, size_t cigar_cap);
+int msa_overlap_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                            const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                            const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                            int32_t gap_extend, int32_t* score, int64_t* beg_ij, int64_t* end_ij, char* cigars,
+                            size_t cigar_cap, int64_t* cigar_off);
+/* ... for alphabets of up to 32 symbols, as msa_fit_align32 is to msa_fit_align (9..32 symbols: MSA_ALG_OVL32 plans) */
+int msa_overlap_align32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                        const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_ij,
+                        int64_t* end_ij, char* cigar, size_t cigar_cap);
+int msa_overlap_align_batch32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                              const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                              const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                              int32_t gap_extend, int32_t* score, int64_t* beg_ij, int64_t* end_ij, char* cigars,
+                              size_t cigar_cap, int64_t* cigar_off);
 
 /* The four matrix-scored entries above for alphabets of up to 32 symbols (proteins with B Z X *, IUPAC DNA): the
  * signatures of their 8-symbol twins, 1 <= n_sym <= 32, sub = n_sym x n_sym.  With n_sym <= 8 a call builds exactly
