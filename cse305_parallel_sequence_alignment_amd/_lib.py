@@ -27,6 +27,7 @@ STATUS = {
 SW_LINEAR, SW_AFFINE, NW_BANDED, REF_GOTOH, PARTIAL, NW_ALIGN, NW_SCORED, NW_FIT = 0, 1, 2, 3, 4, 5, 6, 7
 SW_SCORED = 8
 NW_OVERLAP = 9
+NW_EXTEND = 10
 CELLS_NONE, CELLS_H, CELLS_DIR, CELLS_TAB = 0, 1, 2, 3
 
 
@@ -144,6 +145,11 @@ def lib() -> C.CDLL:
     L.msa_overlap_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, P, P, P, P, sz, P]
     L.msa_overlap_align32.argtypes = L.msa_overlap_align.argtypes
     L.msa_overlap_align_batch32.argtypes = L.msa_overlap_align_batch.argtypes
+    # extension alignment: overlap's arguments with {a_end, b_end} and the global score H(m, n) for its two cells
+    L.msa_extend_align.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, C.POINTER(i32), P, C.POINTER(i32), P, sz]
+    L.msa_extend_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, P, P, P, P, sz, P]
+    L.msa_extend_align32.argtypes = L.msa_extend_align.argtypes
+    L.msa_extend_align_batch32.argtypes = L.msa_extend_align_batch.argtypes
     # local alignment under a matrix: msa_sw_align's / msa_sw_align_batch's, (alphabet, n_sym, sub) for (match, mismatch)
     L.msa_sw_align_scored.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64),
                                       C.POINTER(i64), C.POINTER(i64), P, sz]
@@ -182,4 +188,5 @@ EXPORTED = [
     "msa_fit_align32", "msa_fit_align_batch32",
     "msa_sw_align_scored", "msa_sw_align_batch_scored", "msa_sw_align_scored32", "msa_sw_align_batch_scored32",
     "msa_overlap_align", "msa_overlap_align_batch", "msa_overlap_align32", "msa_overlap_align_batch32",
+    "msa_extend_align", "msa_extend_align_batch", "msa_extend_align32", "msa_extend_align_batch32",
 ]

@@ -322,7 +322,8 @@ def _entry(name: str, max_symbols: int) -> str:
         return name
     return {"msa_nw_align_scored": "msa_nw_align_scored32", "msa_nw_align_batch_scored": "msa_nw_align_batch_scored32",
             "msa_fit_align": "msa_fit_align32", "msa_fit_align_batch": "msa_fit_align_batch32",
-            "msa_overlap_align": "msa_overlap_align32", "msa_overlap_align_batch": "msa_overlap_align_batch32"}[name]
+            "msa_overlap_align": "msa_overlap_align32", "msa_overlap_align_batch": "msa_overlap_align_batch32",
+            "msa_extend_align": "msa_extend_align32", "msa_extend_align_batch": "msa_extend_align_batch32"}[name]
 
 
 def _nw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols=8):
@@ -633,3 +634,64 @@ def overlap_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=
                                      _i64p(coff) if traceback else None), name)
     return [_overlap_dict(sc[p], beg[p], end[p], traceback,
                           cig.raw[coff[p]:coff[p + 1] - 1].decode() if traceback else None) for p in range(k)]
+
+
+def _extend_dict(score, end, gscore, traceback, cigar):
+    r = dict(score=int(score), a_end=int(end[0]), b_end=int(end[1]), global_score=int(gscore))
+    if traceback:
+        r["cigar"] = cigar
+    return r
+
+
+def extend_align(A, B, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
+                 matrix=None, max_symbols=8):
+    """Extension alignment (build extension, msa_extend_align): the alignment starts at the first symbols of both
+    sequences and may stop anywhere -> dict(score, a_end, b_end, global_score[, cigar]): the best-scoring pair of
+    prefixes, ``A[:a_end]`` against ``B[:b_end]``.
+
+    What a seed-and-extend pipeline runs on each flank of a seed (rightwards on the flanks, leftwards on the reversed
+    ones).  A gap of L costs (gap_open - gap_extend) + gap_extend * L.  Of equally good end cells the first in
+    row-major order wins (the smallest ``a_end``, then the smallest ``b_end``).  No positive score: the empty
+    extension, score 0, ``a_end == b_end == 0`` and an empty CIGAR.  The CIGAR (start -> end, I consumes A, D consumes
+    B) consumes exactly ``a_end`` and ``b_end``.  ``global_score`` is the end-to-end score of all of A against all of
+    B -- nw_align's -- from the same fill: compare it with ``score`` to choose between clipping and aligning to the
+    end.  ``traceback=False`` gives the scores and the end cell only.  Scoring and ``max_symbols`` as for fit_align."""
+    A, B = _buf(A), _buf(B)
+    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
+    name = _entry("msa_extend_align", max_symbols)
+    sc, gs = C.c_int32(), C.c_int32()
+    end = np.zeros(2, dtype=np.int64)
+    cap = 4 * (len(A) + len(B)) + 16
+    cig = C.create_string_buffer(cap) if traceback else None
+    LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open,
+                                     gap_extend, C.byref(sc), _i64p(end), C.byref(gs), cig,
+                                     cap if traceback else 0), name)
+    return _extend_dict(sc.value, end, gs.value, traceback, cig.value.decode() if traceback else None)
+
+
+def extend_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
+                       matrix=None, max_symbols=8):
+    """A batch of extension alignments (msa_extend_align_batch) -> a list of extend_align()'s dicts.
+
+    ``Bs``: a list as long as ``As``, or one bytes object every A is aligned against (uploaded once), exactly like
+    nw_align_batch's; scoring as for extend_align, over one alphabet for the whole call (``match`` / ``mismatch``:
+    the distinct symbols of all As, then all Bs, in first-seen order).  ``max_symbols=32``
+    (msa_extend_align_batch32): up to 32 symbols in the whole call."""
+    name = _entry("msa_extend_align_batch", max_symbols)
+    if len(As) == 0:
+        return []
+    A, B, a_off, m, b_off, n = _batch_in(As, Bs)
+    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
+    k = len(m)
+    sc = np.zeros(k, dtype=np.int32)
+    gs = np.zeros(k, dtype=np.int32)
+    end = np.zeros((k, 2), dtype=np.int64)
+    coff = np.zeros(k + 1, dtype=np.int64)
+    cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
+    cig = C.create_string_buffer(cap) if traceback else None
+    LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
+                                     alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend,
+                                     sc.ctypes.data_as(C.c_void_p), _i64p(end), gs.ctypes.data_as(C.c_void_p), cig, cap,
+                                     _i64p(coff) if traceback else None), name)
+    return [_extend_dict(sc[p], end[p], gs[p], traceback,
+                         cig.raw[coff[p]:coff[p + 1] - 1].decode() if traceback else None) for p in range(k)]

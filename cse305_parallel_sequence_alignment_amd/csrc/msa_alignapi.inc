@@ -6,6 +6,7 @@
 //     msa_nw_align_scored, ..._batch_scored, *32        ... under match / mismatch scores or a matrix, 8 or 32 symbols
 //     msa_fit_align, msa_fit_align_batch, *32           all of A in a substring of B
 //     msa_overlap_align, msa_overlap_align_batch, *32   a suffix of one sequence against a prefix of the other
+//     msa_extend_align, msa_extend_align_batch, *32     the best pair of prefixes (anchored start, free end)
 // The host encodes the inputs, runs plans (the flow / band kernels behind msa_plan_run) and the device walks
 // (traceback_kernel, msa_plan_traceback_batch), and turns a walk's O(m + n) ops into a CIGAR.
 namespace {
@@ -118,6 +119,14 @@ AlignSpec spec_overlap(const char* alphabet, size_t n_sym, const int8_t* sub, si
   s.stop_is_beg = true;
   return s;
 }
+// The global alignment's borders and walk with a free END instead: the best pair of prefixes.  The start is anchored
+// at (0, 0), so the walk's ops are completed along the border exactly as a global alignment's are
+AlignSpec spec_extend(const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym = 8) {
+  AlignSpec s = spec_fit(alphabet, n_sym, sub, max_sym);
+  s.alg_walk = s.alg_score = MSA_NW_EXTEND;
+  s.border = BORDER_GLOBAL;
+  return s;
+}
 
 // The pairs of a call: pair p is A[a_off[p] .. + m[p]) against B[b_off[p] .. + n[p]).
 struct AlignIn {
@@ -148,11 +157,13 @@ struct PairOut {
 };
 struct AlignOut {
   int32_t* score;
-  PairOut end, beg;  // local: the end cell, the start cell; overlap: {a_end, b_end}, {a_beg, b_beg}
+  PairOut end, beg;  // local: the end cell, the start cell; overlap: {a_end, b_end}, {a_beg, b_beg}; extension:
+                     // {a_end, b_end}, nothing
   PairOut span;      // fit: {beg_j, end_j}, beg_j = -1 without a walk
   char* cigars;      // the CIGARs back to back, each with its NUL; cigar_off[np + 1]
   size_t cigar_cap;
   int64_t* cigar_off;
+  int32_t* fin_h = nullptr;  // extension: H(m, n) of every pair, the global alignment's score (fin[0] of its result)
 };
 struct GapBand {
   int32_t gap_open, gap_extend;
@@ -232,6 +243,7 @@ int align_range(const AlignSpec& spec, int single, const GapBand& gb, bool want_
   // (the scores, end cells and span ends are the caller's whatever becomes of the walks)
   for (int64_t k = 0; k < K; ++k) {
     if (out.score) out.score[p0 + k] = res[(size_t)k].score;
+    if (out.fin_h) out.fin_h[p0 + k] = res[(size_t)k].fin[0];
     out.end.put(p0 + k, res[(size_t)k].end_i, res[(size_t)k].end_j);
     out.span.put(p0 + k, -1, res[(size_t)k].end_j);
     if (spec.stop_is_beg) out.beg.put(p0 + k, -1, -1);
@@ -505,6 +517,59 @@ int msa_overlap_align_batch32(const char* A, size_t a_len, const char* B, size_t
                               size_t cigar_cap, int64_t* cigar_off) {
   return overlap_align_batch(A, a_len, B, b_len, n_pairs, a_off, m, b_off, n, alphabet, n_sym, sub, 32, gap_open,
                              gap_extend, score, beg_ij, end_ij, cigars, cigar_cap, cigar_off);
+}
+
+// ---- extension alignment (MSA_NW_EXTEND): the overlap entries with {a_end, b_end} and H(m, n) for their two cells;
+// 8 symbols, or 32 for the *32 entries
+static int extend_align(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                        const int8_t* sub, size_t max_sym, int32_t gap_open, int32_t gap_extend, int32_t* score,
+                        int64_t* end_ij, int32_t* global_score, char* cigar, size_t cigar_cap) {
+  const OnePairIn one(A0, m, B0, n);
+  int64_t coff[2];
+  const AlignOut out{score, PairOut(end_ij), PairOut(), PairOut(), cigar, cigar_cap, coff, global_score};
+  return align_pairs(spec_extend(alphabet, n_sym, sub, max_sym), 1, one.in, kPairLimit, gap_open, gap_extend, -1, out);
+}
+static int extend_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                              const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                              const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym,
+                              int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_ij,
+                              int32_t* global_score, char* cigars, size_t cigar_cap, int64_t* cigar_off) {
+  if (!end_ij) return MSA_ERR_ARG;
+  const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
+  const AlignOut out{score, PairOut(end_ij), PairOut(), PairOut(), cigars, cigar_cap, cigar_off, global_score};
+  return align_pairs(spec_extend(alphabet, n_sym, sub, max_sym), 0, in, kPairLimit, gap_open, gap_extend, -1, out);
+}
+
+int msa_extend_align(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                     const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_ij,
+                     int32_t* global_score, char* cigar, size_t cigar_cap) {
+  return extend_align(A0, m, B0, n, alphabet, n_sym, sub, 8, gap_open, gap_extend, score, end_ij, global_score, cigar,
+                      cigar_cap);
+}
+
+int msa_extend_align32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                       const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_ij,
+                       int32_t* global_score, char* cigar, size_t cigar_cap) {
+  return extend_align(A0, m, B0, n, alphabet, n_sym, sub, 32, gap_open, gap_extend, score, end_ij, global_score, cigar,
+                      cigar_cap);
+}
+
+int msa_extend_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                           const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                           const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                           int32_t gap_extend, int32_t* score, int64_t* end_ij, int32_t* global_score, char* cigars,
+                           size_t cigar_cap, int64_t* cigar_off) {
+  return extend_align_batch(A, a_len, B, b_len, n_pairs, a_off, m, b_off, n, alphabet, n_sym, sub, 8, gap_open,
+                            gap_extend, score, end_ij, global_score, cigars, cigar_cap, cigar_off);
+}
+
+int msa_extend_align_batch32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                             const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                             const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                             int32_t gap_extend, int32_t* score, int64_t* end_ij, int32_t* global_score,
+                             char* cigars, size_t cigar_cap, int64_t* cigar_off) {
+  return extend_align_batch(A, a_len, B, b_len, n_pairs, a_off, m, b_off, n, alphabet, n_sym, sub, 32, gap_open,
+                            gap_extend, score, end_ij, global_score, cigars, cigar_cap, cigar_off);
 }
 
 // ---- local alignment under a substitution matrix (MSA_SW_SCORED): msa_sw_align / msa_sw_align_batch with the

@@ -353,7 +353,7 @@ int nc_of(int alg) {
   switch (alg) {
     case MSA_ALG_SWL: case MSA_ALG_SWL0: case MSA_ALG_SWLP: return 1;
     case MSA_ALG_SWA: case MSA_ALG_NWA: case MSA_ALG_REF1: case MSA_ALG_FIT: case MSA_ALG_NWA32: case MSA_ALG_FIT32:
-    case MSA_ALG_SWS: case MSA_ALG_SWS32: case MSA_ALG_OVL: case MSA_ALG_OVL32:
+    case MSA_ALG_SWS: case MSA_ALG_SWS32: case MSA_ALG_OVL: case MSA_ALG_OVL32: case MSA_ALG_EXT: case MSA_ALG_EXT32:
       return 2;
     default: return 3;
   }
@@ -490,6 +490,19 @@ kfn_t pick_kernel(int alg, int out, int tp, bool sgl) {
     case MSA_ALG_OVL32:
       if (out == MSA_OUT_NONE) return kf<MSA_ALG_OVL32, MSA_OUT_NONE, 0>(sgl);
       if (out == MSA_OUT_DIR) return kf<MSA_ALG_OVL32, MSA_OUT_DIR, 0>(sgl);
+      break;
+    // MSA_NW_EXTEND: the unbanded global kernels' cell, borders and bytes with the first maximum over all interior
+    // cells tracked by compare-select (1; never the packed key, whose values must be non-negative); instantiations
+    // of their own, the MSA_ALG_NWA kernels' code is unchanged
+    case MSA_ALG_EXT:
+      if (tp != 1) break;
+      if (out == MSA_OUT_NONE) return kf<MSA_ALG_EXT, MSA_OUT_NONE, 1>(sgl);
+      if (out == MSA_OUT_DIR) return kf<MSA_ALG_EXT, MSA_OUT_DIR, 1>(sgl);
+      break;
+    case MSA_ALG_EXT32:
+      if (tp != 1) break;
+      if (out == MSA_OUT_NONE) return kf<MSA_ALG_EXT32, MSA_OUT_NONE, 1>(sgl);
+      if (out == MSA_OUT_DIR) return kf<MSA_ALG_EXT32, MSA_OUT_DIR, 1>(sgl);
       break;
     // MSA_SW_SCORED: the SW-affine cell under the plan's table.  Such a plan always tracks its end cell, so
     // compare-select (1) or the packed key (2) only; the MSA_ALG_SWA kernels' code is unchanged
@@ -729,9 +742,10 @@ int msa_plan_run(msa_plan* P, const uint8_t* dA, const uint8_t* dB, void* c0, vo
     return MSA_OK;
   }
   // (2: a fit plan's pair result is the first maximum of row m, from the meta of the stripe that holds it; 3: an
-  // overlap plan's, that maximum against the last column's, from every stripe's meta)
+  // overlap plan's, that maximum against the last column's, from every stripe's meta; 4: an extension plan's, the
+  // first maximum of every stripe's best, or the empty extension, with the global final state kept in fin[])
   const int sw = (is_linear(P->main.kp.alg) || swaf(P->main.kp.alg)) ? 1
-                 : ovlk(P->main.kp.alg) ? 3 : (fitk(P->main.kp.alg) ? 2 : 0);
+                 : extk(P->main.kp.alg) ? 4 : ovlk(P->main.kp.alg) ? 3 : (fitk(P->main.kp.alg) ? 2 : 0);
   const int np = (int)P->d.n_pairs;
   hipLaunchKernelGGL(reduce_pairs_kernel, dim3(np), dim3(64), 0, st, P->d_pairs, P->d_meta, np, sw,
                      P->d_res);
@@ -890,13 +904,14 @@ int msa_plan_traceback_gotoh(msa_plan* P, int64_t pair, int end_type, const uint
 int msa_plan_traceback_nw(msa_plan* P, int64_t pair, const uint8_t* dDir, uint8_t* d_ops, int64_t ops_cap,
                           int64_t* d_info, void* stream) {
   if (!P || !dDir || !d_ops || !d_info || ops_cap < 0 || pair < 0 || pair >= P->d.n_pairs) return MSA_ERR_ARG;
-  const bool fit = fit_bytes(P) || overlap_bytes(P);
+  const bool fit = fit_bytes(P) || overlap_bytes(P) || extend_bytes(P);
   if (!nw_bytes(P) && !fit) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   P->note_stream(st);
   // stripe starts from the stripe meta (band geometry); the walk needs no end type and no PairResult (a fit plan's
   // walk, TB_FIT: the same walk from the run's end cell (m, end_j) in its PairResult; an overlap plan's end cell
-  // may lie on the last column instead, (end_i, n), or be the empty overlap's (m, 0), which ends the walk at once)
+  // may lie on the last column instead, (end_i, n), or be the empty overlap's (m, 0), which ends the walk at once;
+  // an extension plan's is any interior cell, or the empty extension's (0, 0), no walk either)
   hipLaunchKernelGGL((fit ? traceback_kernel<TB_FIT> : traceback_kernel<TB_NW>), dim3(1), dim3(384), 0, st, dDir, P->d_pairs, P->d_meta,
                      (const PairResult*)P->d_res, (int)pair, 0, 0, d_ops, (long long)ops_cap, (long long*)d_info, 0,
                      (const unsigned long long*)nullptr);
@@ -915,8 +930,9 @@ int msa_plan_traceback_batch(msa_plan* P, const uint8_t* dDir, uint8_t* d_ops, c
   const bool sw = ((P->d.alg == MSA_SW_AFFINE && P->main.kp.alg == MSA_ALG_SWA) || P->d.alg == MSA_SW_SCORED) &&
                   P->d.cells == MSA_CELLS_DIR && P->d.track_end;
   // (the global walk from each pair's end cell: fit (m, end_j); overlap (end_i, end_j), one of them on the last row
-  // or column -- or (m, 0), the empty overlap, whose walk the kernel's own `j > 0` ends before its first step)
-  const bool fit = fit_bytes(P) || overlap_bytes(P);
+  // or column -- or (m, 0), the empty overlap, whose walk the kernel's own `j > 0` ends before its first step;
+  // extension (end_i, end_j) anywhere inside -- or (0, 0), the empty extension, ended by `i > 0` likewise)
+  const bool fit = fit_bytes(P) || overlap_bytes(P) || extend_bytes(P);
   if (!nw && !sw && !fit) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   P->note_stream(st);

@@ -100,9 +100,12 @@ template <> struct Tr<MSA_ALG_SWS> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_SWS32> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_OVL> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_OVL32> { static constexpr int NC = 2; };
+template <> struct Tr<MSA_ALG_EXT> { static constexpr int NC = 2; };
+template <> struct Tr<MSA_ALG_EXT32> { static constexpr int NC = 2; };
 // 5-bit codes: the lane's profile is a 32-byte row of the plan's 32 x 32 table (score4_wide)
 constexpr bool wide(int alg) {
-  return alg == MSA_ALG_NWA32 || alg == MSA_ALG_FIT32 || alg == MSA_ALG_SWS32 || alg == MSA_ALG_OVL32;
+  return alg == MSA_ALG_NWA32 || alg == MSA_ALG_FIT32 || alg == MSA_ALG_SWS32 || alg == MSA_ALG_OVL32 ||
+         alg == MSA_ALG_EXT32;
 }
 // the SW-affine cell with scores from the plan's table (swsc), with those or match / mismatch (swaf): the zero floor,
 // zero borders, best tracking and the virtual columns are the same
@@ -114,7 +117,10 @@ constexpr bool swaf(int alg) { return alg == MSA_ALG_SWA || swsc(alg); }
 constexpr bool nwg(int alg) { return alg == MSA_ALG_NWA || alg == MSA_ALG_NWA32; }
 constexpr bool ovlk(int alg) { return alg == MSA_ALG_OVL || alg == MSA_ALG_OVL32; }
 constexpr bool fitk(int alg) { return alg == MSA_ALG_FIT || alg == MSA_ALG_FIT32 || ovlk(alg); }
-constexpr bool nwa(int alg) { return nwg(alg) || fitk(alg); }
+// The extension kernels (extk) are the unbanded global kernels -- cell, both borders, bytes -- and keep, beside them,
+// the first maximum of H over ALL interior cells (values may be negative: no zero floor, no packed key)
+constexpr bool extk(int alg) { return alg == MSA_ALG_EXT || alg == MSA_ALG_EXT32; }
+constexpr bool nwa(int alg) { return nwg(alg) || fitk(alg) || extk(alg); }
 template <> struct Tr<MSA_ALG_REF> { static constexpr int NC = 3; };
 template <> struct Tr<MSA_ALG_REF1> { static constexpr int NC = 2; };
 template <> struct Tr<MSA_ALG_PART> { static constexpr int NC = 3; };
@@ -215,7 +221,7 @@ struct KArgs {
   unsigned long long* best_key;
   // MSA_ALG_NWA, MSA_ALG_FIT: the plan's substitution table, one 8-byte profile per row code (byte b of entry a = the
   // score of row code a against column code b, in the launch's own space: msa_plan.inc, sub_table).
-  // MSA_ALG_NWA32, MSA_ALG_FIT32: 1,024 raw scores, byte 32 a + b.
+  // MSA_ALG_NWA32, MSA_ALG_FIT32, MSA_ALG_OVL32, MSA_ALG_EXT32: 1,024 raw scores, byte 32 a + b.
   // MSA_ALG_SWS / MSA_ALG_SWS32: the same two layouts, the virtual code's column (7 / 31) holding MSA_VIRT_SCORE
   const uint2* sub;
 };
@@ -244,7 +250,7 @@ __device__ __forceinline__ void border_top(const msa_kparams& kp, int c, int (&v
     v[0] = c >= 0 ? 0 : MSA_NEG;
     v[1] = MSA_NEG;
     v[2] = MSA_NEG;
-  } else if constexpr (nwg(ALG)) {
+  } else if constexpr (nwg(ALG) || extk(ALG)) {  // (extk: kp.band = -1, r0 = 0)
     if (r0 > 0) {
       const int d = c > r0 ? c - r0 : r0 - c;
       v[0] = (d <= kp.band) ? -kp.h - kp.gap_ext * d : MSA_NEG;
@@ -303,7 +309,7 @@ __device__ __forceinline__ void border_left(const msa_kparams& kp, int i, int (&
     v[0] = 0;        // H
     v[1] = MSA_NEG;  // E
     v[2] = MSA_NEG;  // F
-  } else if constexpr (nwa(ALG)) {  // (FIT: kp.band = -1)
+  } else if constexpr (nwa(ALG)) {  // (FIT, EXT: kp.band = -1)
     const bool inb = (kp.band < 0) || (i <= kp.band);
     v[0] = inb ? -kp.h - kp.gap_ext * i : MSA_NEG;  // H
     v[1] = MSA_NEG;                                 // T2 (E)
@@ -1054,7 +1060,8 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
 #pragma unroll
         for (int v = 0; v < 3; ++v) { L.LB[v] = lb[v]; L.S[v] = lb[v]; L.U[v] = MSA_NEG; L.fin[v] = 0; }
       }
-      L.best = fitk(ALG) ? INT32_MIN : 0;  // (FIT: every H(m, j) is finite, > MSA_NEG)
+      // (FIT: every H(m, j) is finite, > MSA_NEG; EXT: so is every interior H, and it may well be negative)
+      L.best = (fitk(ALG) || extk(ALG)) ? INT32_MIN : 0;
       L.bt = -1;
       L.pb = (int)0x80008000u;
       const int gdiag = kp.gap_open * (64 * ks + 1 + sg.cs);  // SWL: g*(i+j) at step 0, same for all lanes
@@ -1336,12 +1343,17 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
             } else {
               d = step<ALG, OUT, MASKED, TRACKPOS, FIN>(kp, L, inv, s, t, ct, cr, hv[k]);
             }
-            if constexpr (fitk(ALG) && FIN) {
+            if constexpr ((fitk(ALG) && FIN) || extk(ALG)) {
               // the stripe of row m (every phase of it, the unmasked body too: FIN): a lane keeps the first
               // maximum of its row's H over the row's own columns 1..n -- strict >, so the earliest step wins;
               // a step on column <= 0 or > n (t outside [tmin, tmax]) never counts, and in an unmasked phase
               // the lane of row m is inside its range by mask_lo / mask_hi.  One compare and two selects per
               // step, in this stripe alone; only the lane of row m is read (stripe finalize).
+              // (EXT: the same tracker in EVERY stripe and every phase, whatever FIN is, and every lane is read.  A
+              // masked "before" step holds the left border LB -- 0 when g = h = 0, a tie with the empty extension --
+              // and is outside [tmin, tmax] like a step past column n; mask_lo / mask_hi put every row <= m inside
+              // its range in an unmasked phase; a lane whose row is > m has tmax = -1 in the masked phases and
+              // counts what it likes in the unmasked ones: stripe finalize drops it.)
               const bool inr = !MASKED || (t >= L.tmin && t <= L.tmax);
               const bool better = inr && L.S[0] > L.best;
               L.best = better ? L.S[0] : L.best;
@@ -1573,6 +1585,26 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
           md->best_j = TRACKPOS ? bj : -1;
         }
       } else {
+        if constexpr (extk(ALG)) {
+          // the stripe's first maximum in row-major order, as the SW branch above finds it: max value, then min row
+          // (a lane's own bt is already its row's smallest column).  Rows past m (the last stripe) never count;
+          // lane 0's row always does, so b is a cell's H.  No test against 0 here: reduce_pairs_kernel's mode 4
+          int b = (L.i <= m) ? L.best : INT32_MIN;
+          int bi = L.i;
+          int bj = sg.cs + L.bt - lane;
+#pragma unroll
+          for (int off = 32; off >= 1; off >>= 1) {
+            const int ob = __shfl_xor(b, off);
+            const int oi = __shfl_xor(bi, off);
+            const int oj = __shfl_xor(bj, off);
+            if (ob > b || (ob == b && oi < bi)) { b = ob; bi = oi; bj = oj; }
+          }
+          if (lane == 0) {
+            md->best = b;
+            md->best_i = bi;
+            md->best_j = bj;
+          }
+        }
         if constexpr (ovlk(ALG)) {
           // the stripe's last-column candidate: max over its rows i <= m of H(i, n) (L.fin[0], captured at t == tmax
           // in a masked phase of every stripe), the smaller row on a tie.  Rows past m (the last stripe) never count
@@ -1824,7 +1856,8 @@ __global__ __launch_bounds__(256) void chunk_add_kernel(int32_t* H, const int16_
 __global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* pairs, const msa_stripe_meta* meta,
                                                          int n_pairs, int sw, PairResult* out) {
   // sw: 1 Smith-Waterman (the best cell of any stripe), 0 global (the final state at (m, n)), 2 fit alignment,
-  // 3 overlap alignment (fit's row-m maximum against the best last-column candidate of any stripe)
+  // 3 overlap alignment (fit's row-m maximum against the best last-column candidate of any stripe), 4 extension
+  // alignment (the best cell of any stripe over values that may be negative, with the global final state beside it)
   // one wave per pair: lanes stride over the pair's stripes (a serial loop of
   // dependent meta loads took ~27 us for a 157-stripe pair)
   const int p = blockIdx.x;
@@ -1892,6 +1925,27 @@ __global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* p
         r.end_i = pd.m;
         r.end_j = 0;
       }
+    }
+    if (sw == 4) {
+      // extension alignment: fin (H, E, F at (m, n), part of this result) stays as set above; the score and the end
+      // cell are the first maximum over every stripe's best.  Every stripe has one (row 64 s + 1 <= m, n >= 1) and
+      // it may be negative, so the search starts at INT32_MIN, not 0: lanes stride over the stripes -- rows increase
+      // with s: strict > keeps a lane's first --, the smaller row wins a tie across lanes (a stripe's best_j is its
+      // row's smallest column already).  Nothing positive: the empty extension, score 0 at (0, 0)
+      int b = INT32_MIN, bi = 0, bj = 0;
+      for (int s = lane; s < S; s += 64) {
+        const msa_stripe_meta& mc = meta[pd.stripe0 + s];
+        if (mc.best > b) { b = mc.best; bi = mc.best_i; bj = mc.best_j; }
+      }
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        const int ob = __shfl_xor(b, off), oi = __shfl_xor(bi, off), oj = __shfl_xor(bj, off);
+        if (ob > b || (ob == b && oi < bi)) { b = ob; bi = oi; bj = oj; }
+      }
+      const bool empty = b <= 0;
+      r.score = empty ? 0 : b;
+      r.end_i = empty ? 0 : bi;
+      r.end_j = empty ? 0 : bj;
     }
   }
   if (lane == 0) out[p] = r;

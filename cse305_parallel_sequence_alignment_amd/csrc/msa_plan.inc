@@ -159,11 +159,14 @@ bool nw_bytes(const msa_plan* P) {
 bool fit_bytes(const msa_plan* P) { return P->d.alg == MSA_NW_FIT && P->d.cells == MSA_CELLS_DIR; }
 // ... the overlap alignment's (the same bytes again; the walks start at each pair's end cell on the last row or column)
 bool overlap_bytes(const msa_plan* P) { return P->d.alg == MSA_NW_OVERLAP && P->d.cells == MSA_CELLS_DIR; }
+// ... the extension alignment's (the global plan's bytes; the walks start at each pair's end cell, any interior cell)
+bool extend_bytes(const msa_plan* P) { return P->d.alg == MSA_NW_EXTEND && P->d.cells == MSA_CELLS_DIR; }
 // the algorithms that score as MSA_NW_SCORED does (table or match / mismatch) under free ends, on the stripe kernel alone
-bool free_ends(int alg) { return alg == MSA_NW_FIT || alg == MSA_NW_OVERLAP; }
+bool free_ends(int alg) { return alg == MSA_NW_FIT || alg == MSA_NW_OVERLAP || alg == MSA_NW_EXTEND; }
 
 // ---- step 1: kernel algorithm and end-cell tracking mode --------------------------------------------
-// wide32: a 32 x 32 table over 5-bit codes (msa_plan_create_scored32: MSA_NW_SCORED, MSA_NW_FIT, MSA_NW_OVERLAP only)
+// wide32: a 32 x 32 table over 5-bit codes (msa_plan_create_scored32: MSA_NW_SCORED, MSA_NW_FIT, MSA_NW_OVERLAP,
+// MSA_NW_EXTEND only)
 // sw_smax: max(0, the largest table entry over real codes) of an MSA_SW_SCORED plan (unused by every other plan)
 int choose_algorithm(const msa_plan_desc* desc, bool wide32, int sw_smax, int& kalg, int& tp) {
   const int out_mode = desc->cells;
@@ -229,6 +232,15 @@ int choose_algorithm(const msa_plan_desc* desc, bool wide32, int sw_smax, int& k
           desc->gap_open < desc->gap_extend || desc->band != -1)
         return MSA_ERR_UNSUPPORTED;
       break;
+    case MSA_NW_EXTEND:
+      // an unbanded MSA_NW_SCORED plan's cell, borders and bytes with the first maximum over all interior cells as the
+      // result (the best pair of prefixes; nothing positive: the empty extension): kernel algorithms of their own.  No
+      // band (the global rule |m - n| <= band does not fit a free end), direction bytes or the score alone
+      kalg = wide32 ? MSA_ALG_EXT32 : MSA_ALG_EXT;
+      if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->gap_extend < 0 ||
+          desc->gap_open < desc->gap_extend || desc->band != -1)
+        return MSA_ERR_UNSUPPORTED;
+      break;
     case MSA_REF_GOTOH: {
       // start type -1 (main_alignment_function's single subproblem) with direction bytes or no
       // cells: the tagged-max form (every interior value is finite; values carried x4)
@@ -256,6 +268,9 @@ int choose_algorithm(const msa_plan_desc* desc, bool wide32, int sw_smax, int& k
       pack = smax * std::min(desc->m[p], desc->n[p]) < 65536 && desc->n[p] + 512 < 32768;
     if (pack) tp = 2;
   }
+  // (an MSA_NW_EXTEND plan always tracks its end cell, by compare-select: its values may be negative, which the
+  // packed key cannot hold)
+  if (extk(kalg)) tp = 1;
   return MSA_OK;
 }
 
@@ -320,7 +335,9 @@ int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t*
       // MSA_NW_OVERLAP (MSA_ALG_OVL) replaces the left border's -h - g i by one more zero source, H(i, 0) = 0 with
       // E = F = -inf: inside the bound that the replaced border needed.  Paths, steps and -inf are unchanged, and the
       // last-column maxima are copies of cells again: the same inequality holds.
-      // The 32-code kernels (MSA_ALG_NWA32, MSA_ALG_FIT32: stripe_kernel, unshifted, raw S) differ in where a step's
+      // MSA_NW_EXTEND (MSA_ALG_EXT) is the unbanded MSA_ALG_NWA itself in the stripe kernel, unshifted: same sources,
+      // steps and -inf, and the tracked maximum is a copy of a cell: the same inequality holds.
+      // The 32-code kernels (MSA_ALG_NWA32, MSA_ALG_FIT32, MSA_ALG_OVL32, MSA_ALG_EXT32: stripe_kernel, unshifted, raw S) differ in where a step's
       // S comes from, not in what a step is: the same inequality with s over the 1,024 scores.
       const int64_t s = sub_abs_max(scored, wide(kp.alg) ? 1024 : 64), g = kp.gap_ext, h = kp.h, G = kp.gap_open;
       if ((s + 2 * G + 2 * g) * (m + n + 256) + h >= (int64_t(1) << 28)) return MSA_ERR_UNSUPPORTED;
@@ -464,7 +481,7 @@ PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp, int smax) {
   for (int64_t p = 1; p < desc->n_pairs; ++p) eq_m = eq_m && desc->m[p] == desc->m[0];
   if (eq_m && batch_items(desc, kalg) < slots && stripes_of(desc->m[0]) >= 2 * MSA_WAVES_BATCH && band < 0 &&
       desc->alg != MSA_NW_ALIGN && desc->alg != MSA_NW_SCORED &&  // (a batch of global alignments with direction
-      !free_ends(desc->alg))                             // bytes, scored, fit or overlap: whole pairs per workgroup)
+      !free_ends(desc->alg))                  // bytes, scored, fit, overlap or extension: whole pairs per workgroup)
     return PM_SPLIT;
   return PM_STRIPE;
 }
@@ -778,12 +795,15 @@ int alloc_buffers(msa_plan& P) {
   if (!P.alloc(&P.d_segs, sizeof(msa_pair_desc) * P.segs.size())) return MSA_ERR_HIP;
   HIPCHK(hipMemcpy(P.d_segs, P.segs.data(), sizeof(msa_pair_desc) * P.segs.size(), hipMemcpyHostToDevice));
   if (!P.alloc(&P.d_res, sizeof(PairResult) * np) || !P.alloc(&P.d_sum, 64)) return MSA_ERR_HIP;
+  // (the walks of a fit, overlap or extension plan start at the run's end cell: until a run has written one it is
+  // (-1, -1), outside the matrix, which both walkers answer with MSA_ERR_ARG whatever the pooled block held before)
+  if (free_ends(P.d.alg)) HIPCHK(hipMemset(P.d_res, 0xff, sizeof(PairResult) * np));
   if (wide(P.main.kp.alg)) {
     // the 32 x 32 table as it is: stripe_kernel's bytes are the raw S (each workgroup copies it to LDS)
     if (!P.alloc(&P.d_sub, sizeof(P.sub))) return MSA_ERR_HIP;
     HIPCHK(hipMemcpy(P.d_sub, P.sub, sizeof(P.sub), hipMemcpyHostToDevice));
   } else if (P.main.kp.alg == MSA_ALG_NWA || P.main.kp.alg == MSA_ALG_FIT || P.main.kp.alg == MSA_ALG_OVL ||
-             P.main.kp.alg == MSA_ALG_SWS) {
+             P.main.kp.alg == MSA_ALG_EXT || P.main.kp.alg == MSA_ALG_SWS) {
     // (MSA_ALG_SWS: stripe_kernel, so the raw S -- with plan_create's MSA_VIRT_SCORE in column 7)
     // the substitution table, one 8-byte profile per row code: band_kernel's bytes are S + 2g + h (its values are
     // shifted by g (i + j); wrapped to a byte as the kernel's own arithmetic did for the 1 / 0 plans), stripe_kernel's S
@@ -904,8 +924,8 @@ static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32
   P->nc = nc_of(kalg);
   if (nwg(kalg) && P->main.kp.h < 0) return MSA_ERR_UNSUPPORTED;
   // the substitution scores of the banded recurrence: MSA_NW_SCORED's table, or its match / mismatch; 1 / 0 for
-  // MSA_NW_BANDED and MSA_NW_ALIGN, whatever their description says; MSA_NW_FIT and MSA_NW_OVERLAP score as
-  // MSA_NW_SCORED does
+  // MSA_NW_BANDED and MSA_NW_ALIGN, whatever their description says; MSA_NW_FIT, MSA_NW_OVERLAP and MSA_NW_EXTEND
+  // score as MSA_NW_SCORED does
   const bool scored = desc->alg == MSA_NW_SCORED || free_ends(desc->alg);
   int smax = 0;
   if (scored && !sub && (desc->match < -128 || desc->match > 127 || desc->mismatch < -128 || desc->mismatch > 127))

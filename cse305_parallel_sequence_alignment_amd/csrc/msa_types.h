@@ -37,6 +37,11 @@ enum msa_alg {
                        // every stripe also keeps H of its row at column n; the stripe's maximum of them (the smaller
                        // row on a tie) goes to the stripe meta's col_best / col_i
   MSA_ALG_OVL32 = 14,  // MSA_ALG_OVL over 5-bit codes, as MSA_ALG_FIT32
+  MSA_ALG_EXT = 15,    // the unbanded MSA_ALG_NWA's cell, borders and bytes (MSA_NW_EXTEND plans): the best pair of
+                       // prefixes.  Every lane of every stripe keeps the first maximum of its row's H over columns
+                       // 1..n (it may be negative); the stripe's first maximum in row-major order goes to the stripe
+                       // meta's best / best_i / best_j, and the stripe of row m still writes fin[] (H, E, F at (m, n))
+  MSA_ALG_EXT32 = 16,  // MSA_ALG_EXT over 5-bit codes, as MSA_ALG_NWA32
 };
 
 // Per-cell outputs.
@@ -48,7 +53,7 @@ enum msa_out {
 };
 
 // One pair of sequences inside a launch.  Codes are uint8 in [0,8) ([0,32): MSA_ALG_NWA32, MSA_ALG_FIT32,
-// MSA_ALG_OVL32, MSA_ALG_SWS32).
+// MSA_ALG_OVL32, MSA_ALG_EXT32, MSA_ALG_SWS32).
 typedef struct msa_pair_desc {
   int64_t a_off;       // offset of row codes (A[0] = row 1) in the A code array
   int64_t b_off;       // offset of column codes (B[0] = column 1) in the B code array
@@ -63,10 +68,11 @@ typedef struct msa_pair_desc {
 typedef struct msa_stripe_meta {
   int32_t cs;          // column processed by lane 0 at step 0 (lane r: cs + t - r)
   int32_t phases;      // phases the stripe ran
-  int32_t best;        // SW: best H in the stripe (INT32_MIN if none); FIT / OVL, the stripe of row m: max H(m, 1..n)
-  int32_t best_i;      // SW: row of the best (first max, row-major); FIT / OVL: m
-  int32_t best_j;      // SW: column of the best; FIT / OVL: the smallest column attaining it
-  int32_t fin[3];      // global: state at (m, n) if this stripe holds row m (FIT too: not part of its result)
+  int32_t best;        // SW: best H in the stripe (INT32_MIN if none); FIT / OVL, the stripe of row m: max H(m, 1..n);
+                       // EXT: max H over the stripe's rows i <= m and columns 1..n (any sign)
+  int32_t best_i;      // SW, EXT: row of the best (first max, row-major); FIT / OVL: m
+  int32_t best_j;      // SW, EXT: column of the best; FIT / OVL: the smallest column attaining it
+  int32_t fin[3];      // global, EXT: state at (m, n) if this stripe holds row m (FIT too: not part of its result)
   int32_t has_fin;
   int32_t col_best;    // OVL: max over the stripe's rows i <= m of H(i, n) (else unused, 0)
   int32_t col_i;       // OVL: the smallest row attaining it

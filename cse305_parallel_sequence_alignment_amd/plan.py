@@ -51,7 +51,7 @@ class Plan:
 
     def __init__(self, alg: int, cells: int, ms, ns, a_offs, b_offs, match=1, mismatch=0, gap_open=1,
                  gap_extend=1, start_type=-1, band=-1, track_end=False, single=None, sub=None):
-        """``sub`` (NW_SCORED, NW_FIT, NW_OVERLAP and SW_SCORED only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code
+        """``sub`` (NW_SCORED, NW_FIT, NW_OVERLAP, NW_EXTEND and SW_SCORED only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code
         a against column code b (msa_plan_create_scored); None scores ``match`` on the diagonal and ``mismatch``
         elsewhere.  A 32 x 32 ``sub`` makes a plan over 5-bit codes (msa_plan_create_scored32: inputs in [0, 32), always the
         stripe kernel); any other shape is a ValueError.
@@ -61,6 +61,10 @@ class Plan:
         An NW_OVERLAP plan (a suffix of one sequence against a prefix of the other: NW_FIT's rules) reports the score
         and its end cell ``end = (end_i, end_j)`` on the last row or column -- ``(m, 0)`` with score 0 for the empty
         overlap --; the same two walks start there, append nothing, and their ``stop`` is where the alignment begins.
+        An NW_EXTEND plan (the best pair of prefixes: NW_FIT's rules, an unbanded NW_SCORED plan's cells and bytes)
+        reports the score and its end cell ``end = (a_end, b_end)``, the first maximum over the interior -- ``(0, 0)``
+        with score 0 for the empty extension --, and in ``fin[0]`` the global score H(m, n); the same two walks start
+        at the end cell and append the global border gap.
         An SW_SCORED plan (SW_AFFINE's recurrence under the table: ``band`` -1, CELLS_DIR or CELLS_NONE) keeps the
         highest code, 7 or 31, as the kernels' out-of-matrix sentinel: inputs are codes 0..6 / 0..30 and ``sub``'s last
         row and column are ignored.  It always tracks its end cell and runs the stripe kernel; ``traceback``,
@@ -306,7 +310,8 @@ class Plan:
         """The ops a global walk that stopped on the matrix border at (i, j) still lacks: i x 'I' or j x 'D'.  An
         NW_FIT plan's alignment starts at reference column j for free: only the 'I' gap (the query overhangs the
         reference's start) is appended, and ``stop[1]`` is where the aligned substring begins.  An NW_OVERLAP plan's
-        alignment starts at the stop cell itself: nothing is appended."""
+        alignment starts at the stop cell itself: nothing is appended.  An NW_EXTEND plan's starts at (0, 0): the global
+        gap."""
         if self.alg == LB.NW_OVERLAP:
             return b""
         if i > 0:
@@ -369,7 +374,7 @@ class Plan:
             LB.check(int(inf[k, 3]), "msa_plan_traceback_batch")
             o = oh[off[k]:off[k] + int(inf[k, 0])].tobytes()
             stats = dict(switches=int(inf[k, 4]), staged=int(inf[k, 5]), ticks=int(inf[k, 6]))
-            if self.alg in (LB.NW_ALIGN, LB.NW_SCORED, LB.NW_FIT, LB.NW_OVERLAP):
+            if self.alg in (LB.NW_ALIGN, LB.NW_SCORED, LB.NW_FIT, LB.NW_OVERLAP, LB.NW_EXTEND):
                 i, j = int(inf[k, 1]) - 1, int(inf[k, 2]) - 1
                 o += self._border_gap(i, j)
                 out.append(dict(ops=o, stop=(i, j), cigar=cigar_of(o), stats=stats))

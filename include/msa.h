@@ -49,6 +49,10 @@
  *   msa_overlap_align, msa_overlap_align_batch, msa_overlap_align32, msa_overlap_align_batch32
  *                        overlap ("dovetail", "ends-free") alignment: a suffix of one sequence against a prefix
  *                        of the other, or one inside the other (build extension: MSA_NW_OVERLAP plans)
+ *   msa_extend_align, msa_extend_align_batch, msa_extend_align32, msa_extend_align_batch32
+ *                        extension alignment (anchored start, free end: what a seed-and-extend pipeline runs on
+ *                        each flank of a seed): the best-scoring pair of prefixes, with the end-to-end score
+ *                        beside it (build extension: MSA_NW_EXTEND plans)
  *   msa_plan_create_scored32, msa_nw_align_scored32, msa_nw_align_batch_scored32, msa_fit_align32,
  *   msa_fit_align_batch32
  *                        MSA_NW_SCORED and MSA_NW_FIT over alphabets of up to 32 symbols (proteins, IUPAC DNA):
@@ -258,9 +262,12 @@ typedef enum msa_alg_e {
                          (msa_plan_create_scored: 8 x 8, inputs are codes 0..6; msa_plan_create_scored32: 32 x 32,
                          codes 0..30 -- the highest code is the out-of-matrix sentinel's).  The contract is at
                          msa_plan_create_scored below */
-  MSA_NW_OVERLAP = 9  /* overlap ("dovetail", "ends-free") alignment: MSA_NW_FIT's cells under zero borders on the top
+  MSA_NW_OVERLAP = 9, /* overlap ("dovetail", "ends-free") alignment: MSA_NW_FIT's cells under zero borders on the top
                          AND the left, ending anywhere on the last row or the last column; the contract is at
                          msa_overlap_align below.  band = -1, MSA_CELLS_DIR or MSA_CELLS_NONE */
+  MSA_NW_EXTEND = 10  /* extension alignment: an unbanded MSA_NW_SCORED plan's cells, borders and bytes, ending at the
+                         first maximum over all interior cells (the best pair of prefixes) or nowhere; the contract is
+                         at msa_extend_align below.  band = -1, MSA_CELLS_DIR or MSA_CELLS_NONE */
 } msa_alg_e;
 
 typedef enum msa_out_e { MSA_CELLS_NONE = 0, MSA_CELLS_H = 1, MSA_CELLS_DIR = 2, MSA_CELLS_TAB = 3 } msa_out_e;
@@ -286,9 +293,11 @@ typedef struct msa_pair_result {
   int32_t score;
   int32_t status;
   int64_t end_i, end_j;  /* SW: end cell; Gotoh: (m, n); MSA_NW_FIT: (m, first column of row m's maximum);
-                            MSA_NW_OVERLAP: the end cell on row m or column n, or (m, 0) with score 0 */
+                            MSA_NW_OVERLAP: the end cell on row m or column n, or (m, 0) with score 0;
+                            MSA_NW_EXTEND: the first maximum over the interior, or (0, 0) with score 0 */
   int32_t fin[3];        /* Gotoh: state at (m, n) (T1,T2,T3 / H,E,F); MSA_NW_FIT: the same cell's (H,E,F), which
-                            is not part of that algorithm's result */
+                            is not part of that algorithm's result; MSA_NW_EXTEND: the same, and part of the
+                            result -- fin[0] = H(m, n) is the end-to-end (global) score */
   int32_t pad;
 } msa_pair_result;
 
@@ -306,7 +315,8 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** plan);
  * band rule and its MSA_ERR_ARG are MSA_NW_ALIGN's.  MSA_NW_FIT takes a table (or NULL: match / mismatch) in the
  * same way and under the same inequality (its zero top border is within the bound); it is MSA_ERR_UNSUPPORTED
  * with any band but -1 and with cells other than MSA_CELLS_DIR / MSA_CELLS_NONE.  MSA_NW_OVERLAP: exactly
- * MSA_NW_FIT's rules and errors (its zero left border is within the bound too).
+ * MSA_NW_FIT's rules and errors (its zero left border is within the bound too).  MSA_NW_EXTEND: the same rules
+ * and errors again (its cells and borders are the unbanded MSA_NW_SCORED plan's: the same inequality).
  * MSA_SW_SCORED takes a table too (NULL: desc->match on the diagonal, desc->mismatch elsewhere, in [-128, 127]; the
  * results are then an MSA_SW_AFFINE plan's).  The kernels keep their out-of-matrix sentinel: code 7 is the virtual
  * column's, the inputs are codes 0..6 -- 7 symbols --, table entries with either index 7 are ignored, and the launch's
@@ -321,9 +331,9 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** plan);
  * msa_plan_traceback_nw and msa_plan_traceback_gotoh reject it with MSA_ERR_UNSUPPORTED.  A non-NULL sub with
  * MSA_SW_AFFINE stays MSA_ERR_UNSUPPORTED, and MSA_SW_AFFINE plans choose their kernels as before. */
 int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_plan** plan);
-/* MSA_NW_SCORED, MSA_NW_FIT and MSA_NW_OVERLAP over 5-bit codes: sub32 = 1,024 scores, row-major sub32[32*a + b] = the
- * score of A's code a against B's code b.  The inputs of msa_plan_run are codes in [0, 32).  desc->alg must be one of
- * those three (anything else but MSA_SW_SCORED, below: MSA_ERR_UNSUPPORTED); sub32 == NULL is MSA_ERR_ARG.  Cells, band and gap rules, the
+/* MSA_NW_SCORED, MSA_NW_FIT, MSA_NW_OVERLAP and MSA_NW_EXTEND over 5-bit codes: sub32 = 1,024 scores, row-major
+ * sub32[32*a + b] = the score of A's code a against B's code b.  The inputs of msa_plan_run are codes in [0, 32).  desc->alg must be one of
+ * those four (anything else but MSA_SW_SCORED, below: MSA_ERR_UNSUPPORTED); sub32 == NULL is MSA_ERR_ARG.  Cells, band and gap rules, the
  * value-range inequality (s = the largest |score| of the 1,024) and their errors are msa_plan_create_scored's.
  * Such a plan always launches the stripe kernel (msa_plan_launch_info mode 0): one pair, a batch, any band (a banded
  * single pair runs the exact masked stripe launch).  msa_plan_format_info reports it in its fourth word;
@@ -437,7 +447,11 @@ int msa_plan_traceback_gotoh(msa_plan* plan, int64_t pair, int end_type, const u
  * caller appends only the i x 'I' border gap, and the stop column j is where the aligned substring begins.
  * An MSA_NW_OVERLAP plan with direction bytes likewise, from its end cell (end_i, end_j) on the last row or column;
  * nothing is appended, and the stop cell (i, j) is where the alignment begins.  Its empty overlap -- end cell (m, 0)
- * -- is no walk: n_ops 0, stop cell (m, 0), status 0.  msa_plan_traceback and msa_plan_traceback_gotoh reject it. */
+ * -- is no walk: n_ops 0, stop cell (m, 0), status 0.  msa_plan_traceback and msa_plan_traceback_gotoh reject it.
+ * An MSA_NW_EXTEND plan with direction bytes likewise, from its end cell (end_i, end_j) anywhere in the interior (an
+ * end cell outside the matrix -- the plan has not run -- is status MSA_ERR_ARG); the caller appends the global
+ * border gap (i x 'I', else j x 'D': the start is anchored at (0, 0)).  Its empty extension -- end cell (0, 0) -- is
+ * no walk: n_ops 0, stop cell (0, 0), status 0.  msa_plan_traceback and msa_plan_traceback_gotoh reject it. */
 int msa_plan_traceback_nw(msa_plan* plan, int64_t pair, const uint8_t* dDir, uint8_t* d_ops, int64_t ops_cap,
                           int64_t* d_info, void* stream);
 /* Every pair's traceback ON THE DEVICE in ONE launch (msa_tbatch.hip), after msa_plan_run on the same
@@ -446,7 +460,8 @@ int msa_plan_traceback_nw(msa_plan* plan, int64_t pair, const uint8_t* dDir, uin
  * per pair).  Plans: MSA_SW_AFFINE with MSA_CELLS_DIR and track_end, or MSA_SW_SCORED with MSA_CELLS_DIR (msa_plan_traceback's walk, from each
  * pair's end cell; no walk for a score <= 0) or MSA_NW_ALIGN / MSA_NW_SCORED (msa_plan_traceback_nw's walk, from (m, n) to
  * the matrix border; the caller appends the border gap; MSA_NW_FIT: that walk from each pair's (m, end_j);
- * MSA_NW_OVERLAP: from each pair's (end_i, end_j), n_ops 0 for an empty overlap), laid
+ * MSA_NW_OVERLAP: from each pair's (end_i, end_j), n_ops 0 for an empty overlap; MSA_NW_EXTEND: the same, n_ops 0 for
+ * an empty extension, and the global border gap is the caller's to append), laid
  * out one row per lane with the stripe starts
  * in the stripe meta: the stripe kernel's batch, split-batch and single launches and the band kernel's.
  * MSA_ERR_UNSUPPORTED, before any launch, for the flow kernels' plans (msa_plan_launch_info mode 1: the
@@ -629,6 +644,60 @@ int msa_overlap_align_batch32(const char* A, size_t a_len, const char* B, size_t
                               const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
                               int32_t gap_extend, int32_t* score, int64_t* beg_ij, int64_t* end_ij, char* cigars,
                               size_t cigar_cap, int64_t* cigar_off);
+
+/* Extension alignment (build extension: MSA_NW_EXTEND plans; BWA-MEM's and minimap2's "extz", BLAST's gapped
+ * extension): the alignment STARTS at the first symbols of both sequences and may stop anywhere -- the best-scoring
+ * pair of prefixes A[0, a_end) against B[0, b_end).  A caller with a seed hit runs it twice per seed: rightwards on the
+ * two flanks, leftwards on the reversed ones.  The contract:
+ *   Inputs: A (m >= 1) and B (n >= 1); a score table S as for MSA_NW_SCORED (int8, 8 x 8 or 32 x 32, or match /
+ *   mismatch); g = gap_extend >= 0, h = gap_open - gap_extend >= 0, a gap of length L costs h + g L.
+ *     H(0, 0) = 0    H(0, j) = E(0, j) = -h - g j  (1 <= j <= n)    H(i, 0) = F(i, 0) = -h - g i  (1 <= i <= m)
+ *     E, F, H of interior cells, the direction byte and every tie rule: msa_plan_traceback_nw's text above -- exactly an
+ *     unbanded MSA_NW_SCORED plan's, so the direction bytes of the two plans on one input are equal byte for byte
+ *     (where that plan's bytes mean anything)
+ *     best = max of H(i, j) over 1 <= i <= m, 1 <= j <= n
+ *     end cell = the FIRST maximum in row-major order: the smallest i, then the smallest j (Smith-Waterman's rule)
+ *     if best <= 0: the empty extension -- score 0, end cell (0, 0), no walk, empty CIGAR.  (Border cells are never
+ *                   candidates: they are <= 0, and the empty extension stands for them)
+ *     else:         score = best
+ *   The walk is msa_plan_traceback_nw's, started at the end cell in state H; it stops as soon as i == 0 or j == 0, and
+ *   the caller appends the global border gap (i x 'I', else j x 'D'): the start is anchored at (0, 0).
+ *   The result is (score, a_end = end_i, b_end = end_j); the CIGAR (start -> end, run-length M/I/D, I consumes A)
+ *   consumes exactly a_end and b_end.  The empty extension is (0, 0, 0) with the CIGAR "".
+ *   A plan reports PairResult{score, status, end_i, end_j}; fin[] holds (H, E, F) at (m, n) as a global plan's does,
+ *   and here it IS part of the result: fin[0] = H(m, n) is the end-to-end score -- what msa_nw_align_scored returns --
+ *   so a caller decides between clipping and aligning to the end without a second fill.
+ *   Out of scope, each MSA_ERR_UNSUPPORTED at plan creation: any band other than -1 (the global plans' |m - n| <= band
+ *   does not fit a free end), cells other than MSA_CELLS_DIR / MSA_CELLS_NONE, gap_extend < 0 or gap_open <
+ *   gap_extend.  No Z-drop / X-drop termination: every cell is computed.  Such plans always run the stripe kernel
+ *   (msa_plan_launch_info mode 0), one pair or a batch, never a split batch; msa_plan_format_info reports end-cell
+ *   tracking 1 (compare-select: the tracked values may be negative, which the packed key cannot hold); and the
+ *   value-range inequality of msa_plan_create_scored holds unchanged (the same sources, steps and -inf; the tracked
+ *   maximum is a copy of a cell).
+ * The entries behave as msa_overlap_align / msa_overlap_align_batch and their *32 twins in everything else, in the
+ * order documented there: argument, gap, alphabet and range errors decided on the host; admission with the full
+ * m x n bytes; chunks of consecutive pairs within a quarter of the budget; a B shared by every pair uploaded once;
+ * MSA_ERR_CAPACITY, the batch with the needed size in cigar_off[n_pairs]; n_sym <= 8 under a *32 entry builds exactly
+ * the plain entry's plans.  *score, end_ij[2] = {a_end, b_end}, *global_score = H(m, n) (each may be NULL) / score
+ * (n_pairs), end_ij (2 n_pairs, required), global_score (n_pairs, or NULL).  cigar(s) == NULL: scores, end cells and
+ * global scores from plans without direction bytes. */
+int msa_extend_align(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                     const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_ij,
+                     int32_t* global_score, char* cigar, size_t cigar_cap);
+int msa_extend_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                           const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                           const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                           int32_t gap_extend, int32_t* score, int64_t* end_ij, int32_t* global_score, char* cigars,
+                           size_t cigar_cap, int64_t* cigar_off);
+/* ... for alphabets of up to 32 symbols, as msa_fit_align32 is to msa_fit_align (9..32 symbols: MSA_ALG_EXT32 plans) */
+int msa_extend_align32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                       const int8_t* sub, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_ij,
+                       int32_t* global_score, char* cigar, size_t cigar_cap);
+int msa_extend_align_batch32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                             const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                             const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                             int32_t gap_extend, int32_t* score, int64_t* end_ij, int32_t* global_score,
+                             char* cigars, size_t cigar_cap, int64_t* cigar_off);
 
 /* The four matrix-scored entries above for alphabets of up to 32 symbols (proteins with B Z X *, IUPAC DNA): the
  * signatures of their 8-symbol twins, 1 <= n_sym <= 32, sub = n_sym x n_sym.  With n_sym <= 8 a call builds exactly
