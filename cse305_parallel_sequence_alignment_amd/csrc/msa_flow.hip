@@ -12,8 +12,13 @@
 // v_perm'd profile word) and one v_max3:
 //     G(i,j) = max3(G(i-1,j-1) + s + 2g, G(i-1,j), G(i,j-1)),   G = H + g(i+j)
 // (X-space, X = H - g with a zero floor, when scores can be negative).  The
-// step time is the DPP -> v_max3 latency (~21 cycles measured on one wave);
-// nothing else sits on the chain:
+// step is bound by what its one wave can issue, not by the DPP -> v_max3
+// latency: every instruction of the phase costs the wave ~4.5 cycles, whether
+// it reads the result of the one before it or not (mbench/mb_chain.hip,
+// DESIGN.md section 8), so an s_nop in front of a DPP costs like a v_max3.  The
+// two-row G-space step is therefore one hand-ordered block (fl_step2_gs: add,
+// add, DPP, v_max3, v_max3 -- the adds are the DPP's wait states), and nothing
+// else sits on the chain:
 //   * waves 0..W-1 compute (one per SIMD), wave W io-in, wave W+1 io-out;
 //   * no s_barrier: a producer's lane 63 writes each 16-column block of its
 //     bottom row to an LDS ring and then bumps its phase counter; the consumer
@@ -321,6 +326,36 @@ __device__ __forceinline__ int fl_step(int in, int s, int& X, int& U, int g) {
   U = up;
   X = GS ? h : h - g;
   return h;
+}
+
+// One G-space DP step of a lane's two rows (pass 1, scores >= 0) as one ordered block: the two SDWA
+// adds (diagonal + score of either row; byte KK of the rows' profile words) stand between the
+// previous step's row-2 v_max3 and this step's DPP, which reads that v_max3's result and needs two
+// wait states behind it.  The compiler's own order sometimes has one add there and pads with an
+// s_nop; a lone wave pays an issue slot for it like for any instruction.
+//   in: U diagonal of row 1, X / X2 left neighbours, `in` the ring value (lane 0's cell above)
+//   out: X = row 1, X2 = row 2, U = `in` = the cell above (the next step's diagonal)
+#define FL_STEP2_ASM(SEL)                                                                             \
+  asm("v_add_u32_sdwa %[a], %[u], sext(%[sw]) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD "   \
+      "src1_sel:BYTE_" #SEL "\n\t"                                                                    \
+      "v_add_u32_sdwa %[b], %[x], sext(%[swb]) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD "  \
+      "src1_sel:BYTE_" #SEL "\n\t"                                                                    \
+      "v_mov_b32_dpp %[in], %[x2] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"                          \
+      "v_max3_i32 %[h1], %[a], %[in], %[x]\n\t"                                                       \
+      "v_max3_i32 %[h2], %[b], %[h1], %[x2]"                                                          \
+      : [a] "=&v"(a), [b] "=&v"(b), [in] "+v"(in), [h1] "=&v"(h1), [h2] "=&v"(h2)                    \
+      : [u] "v"(U), [x] "v"(X), [x2] "v"(X2), [sw] "v"(sw), [swb] "v"(swb))
+__device__ __forceinline__ void fl_step2_gs(int kk, int in, unsigned sw, unsigned swb, int& X, int& X2, int& U) {
+  int a, b, h1, h2;
+  switch (kk) {  // (a constant after unrolling)
+    case 0: FL_STEP2_ASM(0); break;
+    case 1: FL_STEP2_ASM(1); break;
+    case 2: FL_STEP2_ASM(2); break;
+    default: FL_STEP2_ASM(3); break;
+  }
+  U = in;
+  X = h1;
+  X2 = h2;
 }
 
 // FLOOR: scores may be negative (zero floor, X-space); otherwise G-space.  Affine SW: the
@@ -1292,6 +1327,9 @@ __global__ __launch_bounds__((FL_W + 2) * 64) __attribute__((amdgpu_waves_per_eu
               const int h = fl_step<GS, FLOOR>(IN[kx >> 2][kx & 3], s, X, U, g);
               xo[kx] = X;
               if constexpr (BEST) hv[kx] = GS ? h + negct + gk[kx] : h;
+            } else if constexpr (GS) {
+              fl_step2_gs(kk, IN[kx >> 2][kx & 3], s4, s4b, X, X2, U);
+              xo[kx] = X2;
             } else {
               // row 1's up = the previous lane's row 2 (lane 0: the producer's value);
               // row 2's up = row 1's new value, its diagonal = row 1's previous value
