@@ -318,12 +318,7 @@ def _entry(name: str, max_symbols: int) -> str:
     """The library entry of a matrix-scored call: ``name`` itself, or its twin for up to 32 symbols."""
     if max_symbols not in (8, 32):
         raise ValueError("max_symbols must be 8 or 32")
-    if max_symbols == 8:
-        return name
-    return {"msa_nw_align_scored": "msa_nw_align_scored32", "msa_nw_align_batch_scored": "msa_nw_align_batch_scored32",
-            "msa_fit_align": "msa_fit_align32", "msa_fit_align_batch": "msa_fit_align_batch32",
-            "msa_overlap_align": "msa_overlap_align32", "msa_overlap_align_batch": "msa_overlap_align_batch32",
-            "msa_extend_align": "msa_extend_align32", "msa_extend_align_batch": "msa_extend_align_batch32"}[name]
+    return name if max_symbols == 8 else name + "32"
 
 
 def _nw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols=8):

@@ -61,16 +61,17 @@ AlignSpec spec_sw(int match, int mismatch, const char* preset) {
   return AlignSpec{MSA_OK, MSA_SW_AFFINE, MSA_SW_AFFINE, match, mismatch, 0, 1, false, {}, SymbolMap(7, preset),
                    GAPS_LOCAL, false, FOOT_MATRIX, msa_plan_traceback, BORDER_NONE, true};
 }
-// Smith-Waterman under the caller's alphabet -- a symbol's code is its index -- and its n_sym x n_sym matrix
-// (MSA_SW_SCORED).  The highest code is the sentinel's, so max_sym is 7, or 31 (the *32 entries); up to 7 symbols make
-// the same spec under either, 8..31 a wide one.  status MSA_ERR_ARG as for spec_scored
-AlignSpec spec_sw_scored(const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym) {
-  AlignSpec s = spec_sw(0, 0, "");
-  s.alg_walk = s.alg_score = MSA_SW_SCORED;
+// A spec scored by the caller's alphabet -- a symbol's code is its index -- and its n_sym x n_sym matrix, under plan
+// kind alg.  reserved: the codes at the top that the kernels keep for themselves, so 8 - reserved symbols fit 3-bit
+// codes and up to 32 - reserved make a wide spec.  status MSA_ERR_ARG for a NULL alphabet or matrix, n_sym outside
+// 1..max_sym or a duplicate symbol
+AlignSpec with_matrix(AlignSpec s, int alg, const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym,
+                      size_t reserved) {
+  s.alg_walk = s.alg_score = alg;
   s.scored = true;
   if (!alphabet || !sub || n_sym < 1 || n_sym > max_sym) s.status = MSA_ERR_ARG;
-  s.wide = s.status == MSA_OK && n_sym > 7;
-  if (s.wide) s.symbols = SymbolMap(31);
+  s.wide = s.status == MSA_OK && n_sym > 8 - reserved;
+  if (s.wide) s.symbols = SymbolMap((int)(32 - reserved));
   const size_t stride = s.wide ? 32 : 8;
   for (size_t a = 0; s.status == MSA_OK && a < n_sym; ++a) {
     if (!s.symbols.add(alphabet[a])) s.status = MSA_ERR_ARG;
@@ -78,29 +79,21 @@ AlignSpec spec_sw_scored(const char* alphabet, size_t n_sym, const int8_t* sub, 
   }
   s.symbols.fix();
   return s;
+}
+// Smith-Waterman under the caller's matrix (MSA_SW_SCORED).  The highest code is the sentinel's, so max_sym is 7, or
+// 31 (the *32 entries); up to 7 symbols make the same spec under either, 8..31 a wide one
+AlignSpec spec_sw_scored(const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym) {
+  return with_matrix(spec_sw(0, 0, ""), MSA_SW_SCORED, alphabet, n_sym, sub, max_sym, 1);
 }
 // global, +1 / 0 over the call's own symbols
 AlignSpec spec_nw(const char* preset) {
   return AlignSpec{MSA_OK, MSA_NW_ALIGN, MSA_NW_BANDED, 1, 0, -1, 0, false, {}, SymbolMap(8, preset),
                    GAPS_GLOBAL, true, FOOT_BAND, msa_plan_traceback_nw, BORDER_GLOBAL, false};
 }
-// global under the caller's alphabet -- a symbol's code is its index -- and its n_sym x n_sym matrix;
-// status MSA_ERR_ARG for a NULL alphabet or matrix, n_sym outside 1..max_sym or a duplicate symbol.  max_sym: 8, or 32
-// (the *32 entries); up to 8 symbols make the same spec under either, 9..32 a wide one
+// global under the caller's matrix.  max_sym: 8, or 32 (the *32 entries); up to 8 symbols make the same spec under
+// either, 9..32 a wide one
 AlignSpec spec_scored(const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym = 8) {
-  AlignSpec s = spec_nw("");
-  s.alg_walk = s.alg_score = MSA_NW_SCORED;
-  s.scored = true;
-  if (!alphabet || !sub || n_sym < 1 || n_sym > max_sym) s.status = MSA_ERR_ARG;
-  s.wide = s.status == MSA_OK && n_sym > 8;
-  if (s.wide) s.symbols = SymbolMap(32);
-  const size_t stride = s.wide ? 32 : 8;
-  for (size_t a = 0; s.status == MSA_OK && a < n_sym; ++a) {
-    if (!s.symbols.add(alphabet[a])) s.status = MSA_ERR_ARG;
-    for (size_t b = 0; b < n_sym; ++b) s.tab[stride * a + b] = sub[n_sym * a + b];
-  }
-  s.symbols.fix();
-  return s;
+  return with_matrix(spec_nw(""), MSA_NW_SCORED, alphabet, n_sym, sub, max_sym, 0);
 }
 // ... and with free ends on B: all of A in a substring of B
 AlignSpec spec_fit(const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym = 8) {

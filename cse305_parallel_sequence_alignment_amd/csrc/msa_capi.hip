@@ -349,16 +349,6 @@ StreamPool& stream_pool() {
   return *p;
 }
 
-int nc_of(int alg) {
-  switch (alg) {
-    case MSA_ALG_SWL: case MSA_ALG_SWL0: case MSA_ALG_SWLP: return 1;
-    case MSA_ALG_SWA: case MSA_ALG_NWA: case MSA_ALG_REF1: case MSA_ALG_FIT: case MSA_ALG_NWA32: case MSA_ALG_FIT32:
-    case MSA_ALG_SWS: case MSA_ALG_SWS32: case MSA_ALG_OVL: case MSA_ALG_OVL32: case MSA_ALG_EXT: case MSA_ALG_EXT32:
-      return 2;
-    default: return 3;
-  }
-}
-
 typedef void (*kfn_t)(KArgs);
 
 // Per-process caches of what plan creation asks the runtime: compute units per device
@@ -419,8 +409,11 @@ int kernel_shape(kfn_t fn, int threads, size_t lds) {
 
 // single-pair phase length: 32 steps for one carried value (SW linear); 16 when
 // two or three values per cell are carried (register pressure: no spills)
-constexpr int ks_single(int alg) { return (alg == MSA_ALG_SWL || alg == MSA_ALG_SWL0) ? MSA_KS_SINGLE : 16; }
-constexpr int ks_batch(int alg) { return (alg == MSA_ALG_SWLP) ? MSA_KS_BATCH_SWLP : MSA_KS_BATCH; }
+constexpr int ks_single(int alg) {
+  const msa_alg_info t = msa_alg_info_of(alg);
+  return (t.linear() && !t.packed()) ? MSA_KS_SINGLE : 16;
+}
+constexpr int ks_batch(int alg) { return msa_alg_info_of(alg).packed() ? MSA_KS_BATCH_SWLP : MSA_KS_BATCH; }
 
 template <int ALG, int OUT, int TP>
 kfn_t kf(bool sgl) {
@@ -429,6 +422,15 @@ kfn_t kf(bool sgl) {
                                : stripe_kernel<ALG, OUT, TP, MSA_WAVES_BATCH, ks_batch(ALG), false>;
 }
 
+// the score-only and the direction-byte instantiation of one algorithm under one tracking mode
+template <int ALG, int TP>
+kfn_t kf_nd(int out, bool sgl) {
+  if (out == MSA_OUT_NONE) return kf<ALG, MSA_OUT_NONE, TP>(sgl);
+  if (out == MSA_OUT_DIR) return kf<ALG, MSA_OUT_DIR, TP>(sgl);
+  return nullptr;
+}
+
+// names every stripe_kernel instantiation the library holds (what each algorithm is: msa_alg.h)
 kfn_t pick_kernel(int alg, int out, int tp, bool sgl) {
 #define K3(A, O) return tp == 2 ? kf<A, O, 2>(sgl) : (tp ? kf<A, O, 1>(sgl) : kf<A, O, 0>(sgl))
   switch (alg) {
@@ -449,73 +451,31 @@ kfn_t pick_kernel(int alg, int out, int tp, bool sgl) {
       if (out == MSA_OUT_DIR) K3(MSA_ALG_SWA, MSA_OUT_DIR);
       break;
     case MSA_ALG_NWA:
-      if (out == MSA_OUT_NONE) return kf<MSA_ALG_NWA, MSA_OUT_NONE, 0>(sgl);
       if (out == MSA_OUT_H) return kf<MSA_ALG_NWA, MSA_OUT_H, 0>(sgl);
       // (direction bytes: MSA_NW_ALIGN plans only -- msa_plan_create keeps (MSA_NW_BANDED, DIR) unsupported)
-      if (out == MSA_OUT_DIR) return kf<MSA_ALG_NWA, MSA_OUT_DIR, 0>(sgl);
-      break;
+      return kf_nd<MSA_ALG_NWA, 0>(out, sgl);
     case MSA_ALG_REF:
-      if (out == MSA_OUT_NONE) return kf<MSA_ALG_REF, MSA_OUT_NONE, 0>(sgl);
       if (out == MSA_OUT_TAB) return kf<MSA_ALG_REF, MSA_OUT_TAB, 0>(sgl);
-      if (out == MSA_OUT_DIR) return kf<MSA_ALG_REF, MSA_OUT_DIR, 0>(sgl);
       if (out == MSA_OUT_H) return kf<MSA_ALG_REF, MSA_OUT_H, 0>(sgl);
-      break;
-    case MSA_ALG_REF1:
-      if (out == MSA_OUT_NONE) return kf<MSA_ALG_REF1, MSA_OUT_NONE, 0>(sgl);
-      if (out == MSA_OUT_DIR) return kf<MSA_ALG_REF1, MSA_OUT_DIR, 0>(sgl);
-      break;
+      return kf_nd<MSA_ALG_REF, 0>(out, sgl);
+    case MSA_ALG_REF1: return kf_nd<MSA_ALG_REF1, 0>(out, sgl);
     case MSA_ALG_PART:
       if (out == MSA_OUT_TAB) return kf<MSA_ALG_PART, MSA_OUT_TAB, 0>(sgl);
       break;
-    case MSA_ALG_FIT:
-      // (instantiations of their own: the MSA_ALG_NWA kernels' code is unchanged)
-      if (out == MSA_OUT_NONE) return kf<MSA_ALG_FIT, MSA_OUT_NONE, 0>(sgl);
-      if (out == MSA_OUT_DIR) return kf<MSA_ALG_FIT, MSA_OUT_DIR, 0>(sgl);
-      break;
-    // 5-bit codes under a 32 x 32 table (msa_plan_create_scored32): instantiations of their own again
-    case MSA_ALG_NWA32:
-      if (out == MSA_OUT_NONE) return kf<MSA_ALG_NWA32, MSA_OUT_NONE, 0>(sgl);
-      if (out == MSA_OUT_DIR) return kf<MSA_ALG_NWA32, MSA_OUT_DIR, 0>(sgl);
-      break;
-    case MSA_ALG_FIT32:
-      if (out == MSA_OUT_NONE) return kf<MSA_ALG_FIT32, MSA_OUT_NONE, 0>(sgl);
-      if (out == MSA_OUT_DIR) return kf<MSA_ALG_FIT32, MSA_OUT_DIR, 0>(sgl);
-      break;
-    // MSA_NW_OVERLAP: the fit kernels' cell and row search under zero borders on both sides, with the last
-    // column's search in every stripe; instantiations of their own, the MSA_ALG_FIT kernels' code is unchanged
-    case MSA_ALG_OVL:
-      if (out == MSA_OUT_NONE) return kf<MSA_ALG_OVL, MSA_OUT_NONE, 0>(sgl);
-      if (out == MSA_OUT_DIR) return kf<MSA_ALG_OVL, MSA_OUT_DIR, 0>(sgl);
-      break;
-    case MSA_ALG_OVL32:
-      if (out == MSA_OUT_NONE) return kf<MSA_ALG_OVL32, MSA_OUT_NONE, 0>(sgl);
-      if (out == MSA_OUT_DIR) return kf<MSA_ALG_OVL32, MSA_OUT_DIR, 0>(sgl);
-      break;
-    // MSA_NW_EXTEND: the unbanded global kernels' cell, borders and bytes with the first maximum over all interior
-    // cells tracked by compare-select (1; never the packed key, whose values must be non-negative); instantiations
-    // of their own, the MSA_ALG_NWA kernels' code is unchanged
-    case MSA_ALG_EXT:
-      if (tp != 1) break;
-      if (out == MSA_OUT_NONE) return kf<MSA_ALG_EXT, MSA_OUT_NONE, 1>(sgl);
-      if (out == MSA_OUT_DIR) return kf<MSA_ALG_EXT, MSA_OUT_DIR, 1>(sgl);
-      break;
-    case MSA_ALG_EXT32:
-      if (tp != 1) break;
-      if (out == MSA_OUT_NONE) return kf<MSA_ALG_EXT32, MSA_OUT_NONE, 1>(sgl);
-      if (out == MSA_OUT_DIR) return kf<MSA_ALG_EXT32, MSA_OUT_DIR, 1>(sgl);
-      break;
-    // MSA_SW_SCORED: the SW-affine cell under the plan's table.  Such a plan always tracks its end cell, so
-    // compare-select (1) or the packed key (2) only; the MSA_ALG_SWA kernels' code is unchanged
-    case MSA_ALG_SWS:
-      if (tp != 1 && tp != 2) break;
-      if (out == MSA_OUT_NONE) return tp == 2 ? kf<MSA_ALG_SWS, MSA_OUT_NONE, 2>(sgl) : kf<MSA_ALG_SWS, MSA_OUT_NONE, 1>(sgl);
-      if (out == MSA_OUT_DIR) return tp == 2 ? kf<MSA_ALG_SWS, MSA_OUT_DIR, 2>(sgl) : kf<MSA_ALG_SWS, MSA_OUT_DIR, 1>(sgl);
-      break;
+    // instantiations of their own each: the MSA_ALG_NWA kernels' code is unchanged by them
+    case MSA_ALG_FIT: return kf_nd<MSA_ALG_FIT, 0>(out, sgl);
+    case MSA_ALG_NWA32: return kf_nd<MSA_ALG_NWA32, 0>(out, sgl);
+    case MSA_ALG_FIT32: return kf_nd<MSA_ALG_FIT32, 0>(out, sgl);
+    case MSA_ALG_OVL: return kf_nd<MSA_ALG_OVL, 0>(out, sgl);
+    case MSA_ALG_OVL32: return kf_nd<MSA_ALG_OVL32, 0>(out, sgl);
+    // the first maximum over all interior cells is tracked by compare-select (1; never the packed key, whose values
+    // must be non-negative)
+    case MSA_ALG_EXT: return tp == 1 ? kf_nd<MSA_ALG_EXT, 1>(out, sgl) : nullptr;
+    case MSA_ALG_EXT32: return tp == 1 ? kf_nd<MSA_ALG_EXT32, 1>(out, sgl) : nullptr;
+    // an MSA_SW_SCORED plan always tracks its end cell: compare-select (1) or the packed key (2) only
+    case MSA_ALG_SWS: return tp == 2 ? kf_nd<MSA_ALG_SWS, 2>(out, sgl) : tp == 1 ? kf_nd<MSA_ALG_SWS, 1>(out, sgl) : nullptr;
     case MSA_ALG_SWS32:
-      if (tp != 1 && tp != 2) break;
-      if (out == MSA_OUT_NONE) return tp == 2 ? kf<MSA_ALG_SWS32, MSA_OUT_NONE, 2>(sgl) : kf<MSA_ALG_SWS32, MSA_OUT_NONE, 1>(sgl);
-      if (out == MSA_OUT_DIR) return tp == 2 ? kf<MSA_ALG_SWS32, MSA_OUT_DIR, 2>(sgl) : kf<MSA_ALG_SWS32, MSA_OUT_DIR, 1>(sgl);
-      break;
+      return tp == 2 ? kf_nd<MSA_ALG_SWS32, 2>(out, sgl) : tp == 1 ? kf_nd<MSA_ALG_SWS32, 1>(out, sgl) : nullptr;
   }
 #undef K3
   return nullptr;
@@ -688,14 +648,14 @@ int msa_plan_run(msa_plan* P, const uint8_t* dA, const uint8_t* dB, void* c0, vo
   a.nblk = P->nblk;
   {
     // (the SW kernels' virtual code: 7, or 31 over 5-bit codes)
-    const unsigned virt = (is_linear(P->main.kp.alg) || swaf(P->main.kp.alg))
-                              ? (wide(P->main.kp.alg) ? MSA_VIRT_CODE32 : MSA_VIRT_CODE) : 0u;
+    const msa_alg_info t = msa_alg_info_of(P->main.kp.alg);
+    const unsigned virt = t.local() ? (t.wide ? MSA_VIRT_CODE32 : MSA_VIRT_CODE) : 0u;
     // about two output words per thread for one long pair (64 x 256 threads took 22 us for
     // C3's 97k columns, 24 dependent rounds each), at least 64 workgroups per segment
     const int64_t words = MSA_NCOPY * (P->cod_copy / 4) / std::max<int64_t>(1, (int64_t)P->segs.size());
     const unsigned gx = (unsigned)std::min<int64_t>(1024, std::max<int64_t>(64, words / 512));
     hipLaunchKernelGGL(stage_codes_kernel, dim3(gx, (unsigned)P->segs.size()), dim3(256), 0, st, dB, P->d_segs,
-                       (int)P->segs.size(), P->d_cod, (long long)P->cod_copy, virt, wide(P->main.kp.alg) ? 31u : 7u,
+                       (int)P->segs.size(), P->d_cod, (long long)P->cod_copy, virt, t.wide ? 31u : 7u,
                        P->d_ticket);
     HIPCHK(hipGetLastError());
   }
@@ -741,14 +701,9 @@ int msa_plan_run(msa_plan* P, const uint8_t* dA, const uint8_t* dB, void* c0, vo
     }
     return MSA_OK;
   }
-  // (2: a fit plan's pair result is the first maximum of row m, from the meta of the stripe that holds it; 3: an
-  // overlap plan's, that maximum against the last column's, from every stripe's meta; 4: an extension plan's, the
-  // first maximum of every stripe's best, or the empty extension, with the global final state kept in fin[])
-  const int sw = (is_linear(P->main.kp.alg) || swaf(P->main.kp.alg)) ? 1
-                 : extk(P->main.kp.alg) ? 4 : ovlk(P->main.kp.alg) ? 3 : (fitk(P->main.kp.alg) ? 2 : 0);
   const int np = (int)P->d.n_pairs;
-  hipLaunchKernelGGL(reduce_pairs_kernel, dim3(np), dim3(64), 0, st, P->d_pairs, P->d_meta, np, sw,
-                     P->d_res);
+  hipLaunchKernelGGL(reduce_pairs_kernel, dim3(np), dim3(64), 0, st, P->d_pairs, P->d_meta, np,
+                     (int)msa_alg_info_of(P->main.kp.alg).result, P->d_res);
   HIPCHK(hipGetLastError());
   return MSA_OK;
 }
@@ -825,7 +780,7 @@ int msa_plan_format_info(const msa_plan* P, int32_t* out4) {
   out4[0] = alg == MSA_ALG_SWLP ? 1 : (alg == MSA_ALG_REF1 ? 2 : 0);
   out4[1] = P->tp;
   out4[2] = P->h16 ? 1 : 0;
-  out4[3] = wide(alg) ? 1 : 0;
+  out4[3] = msa_alg_info_of(alg).wide ? 1 : 0;
   return MSA_OK;
 }
 
@@ -872,7 +827,7 @@ int msa_plan_traceback(msa_plan* P, int64_t pair, const uint8_t* dDir, uint8_t* 
   if (!P || !dDir || !d_ops || !d_info || ops_cap < 0 || pair < 0 || pair >= P->d.n_pairs) return MSA_ERR_ARG;
   // the walk starts at the fill's end cell: plans without track_end have none
   // (an MSA_SW_SCORED plan always has one: plan_create sets its track_end)
-  if (!swaf(P->main.kp.alg) || P->d.cells != MSA_CELLS_DIR || !P->d.track_end) return MSA_ERR_UNSUPPORTED;
+  if (walker_of(P) != TB_SW) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   P->note_stream(st);
   hipLaunchKernelGGL((P->R == 2 ? traceback_kernel<TB_SW, 2> : traceback_kernel<TB_SW>), dim3(1), dim3(384), 0, st, dDir, P->d_pairs, P->d_meta,
@@ -887,13 +842,13 @@ int msa_plan_traceback_gotoh(msa_plan* P, int64_t pair, int end_type, const uint
                              int64_t ops_cap, int64_t* d_info, void* stream) {
   if (!P || !dDir || !d_ops || !d_info || ops_cap < 0 || pair < 0 || pair >= P->d.n_pairs) return MSA_ERR_ARG;
   if (end_type < -3 || end_type > 3 || end_type == 0) return MSA_ERR_ARG;
-  if ((P->main.kp.alg != MSA_ALG_REF && P->main.kp.alg != MSA_ALG_REF1) || P->d.cells != MSA_CELLS_DIR)
-    return MSA_ERR_UNSUPPORTED;
+  const msa_walk kind = walker_of(P);
+  if (kind != TB_REF && kind != TB_REF_TAG) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   P->note_stream(st);
   // REF1 bytes hold tags (3 / 2 / 1 = T1 / T2 / T3), REF bytes the table numbers
-  hipLaunchKernelGGL(P->main.kp.alg == MSA_ALG_REF1 ? (P->R == 2 ? traceback_kernel<TB_REF_TAG, 2> : traceback_kernel<TB_REF_TAG>)
-                                               : traceback_kernel<TB_REF>, dim3(1),
+  hipLaunchKernelGGL(kind == TB_REF_TAG ? (P->R == 2 ? traceback_kernel<TB_REF_TAG, 2> : traceback_kernel<TB_REF_TAG>)
+                                        : traceback_kernel<TB_REF>, dim3(1),
                      dim3(384), 0, st, dDir, P->d_pairs, P->d_meta, (const PairResult*)P->d_res, (int)pair, end_type,
                      (int)P->main.kp.h, d_ops, (long long)ops_cap, (long long*)d_info, P->mode == PM_FLOW ? 1 : 0,
                      (const unsigned long long*)nullptr);
@@ -904,15 +859,15 @@ int msa_plan_traceback_gotoh(msa_plan* P, int64_t pair, int end_type, const uint
 int msa_plan_traceback_nw(msa_plan* P, int64_t pair, const uint8_t* dDir, uint8_t* d_ops, int64_t ops_cap,
                           int64_t* d_info, void* stream) {
   if (!P || !dDir || !d_ops || !d_info || ops_cap < 0 || pair < 0 || pair >= P->d.n_pairs) return MSA_ERR_ARG;
-  const bool fit = fit_bytes(P) || overlap_bytes(P) || extend_bytes(P);
-  if (!nw_bytes(P) && !fit) return MSA_ERR_UNSUPPORTED;
+  const msa_walk kind = walker_of(P);
+  if (kind != TB_NW && kind != TB_FIT) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   P->note_stream(st);
   // stripe starts from the stripe meta (band geometry); the walk needs no end type and no PairResult (a fit plan's
   // walk, TB_FIT: the same walk from the run's end cell (m, end_j) in its PairResult; an overlap plan's end cell
   // may lie on the last column instead, (end_i, n), or be the empty overlap's (m, 0), which ends the walk at once;
   // an extension plan's is any interior cell, or the empty extension's (0, 0), no walk either)
-  hipLaunchKernelGGL((fit ? traceback_kernel<TB_FIT> : traceback_kernel<TB_NW>), dim3(1), dim3(384), 0, st, dDir, P->d_pairs, P->d_meta,
+  hipLaunchKernelGGL((kind == TB_FIT ? traceback_kernel<TB_FIT> : traceback_kernel<TB_NW>), dim3(1), dim3(384), 0, st, dDir, P->d_pairs, P->d_meta,
                      (const PairResult*)P->d_res, (int)pair, 0, 0, d_ops, (long long)ops_cap, (long long*)d_info, 0,
                      (const unsigned long long*)nullptr);
   HIPCHK(hipGetLastError());
@@ -925,19 +880,17 @@ int msa_plan_traceback_batch(msa_plan* P, const uint8_t* dDir, uint8_t* d_ops, c
   // one row per lane, stripe starts in the stripe meta, a PairResult per pair: the flow kernels' plans (two rows
   // per lane, computed stripe starts, the fused best-cell key) stay with the single walker
   if (P->mode == PM_FLOW || P->R == 2 || P->fused_reduce) return MSA_ERR_UNSUPPORTED;
-  const bool nw = nw_bytes(P);
-  // (the SW walk starts at the fill's end cell: plans without track_end have none)
-  const bool sw = ((P->d.alg == MSA_SW_AFFINE && P->main.kp.alg == MSA_ALG_SWA) || P->d.alg == MSA_SW_SCORED) &&
-                  P->d.cells == MSA_CELLS_DIR && P->d.track_end;
-  // (the global walk from each pair's end cell: fit (m, end_j); overlap (end_i, end_j), one of them on the last row
-  // or column -- or (m, 0), the empty overlap, whose walk the kernel's own `j > 0` ends before its first step;
+  // (TB_FIT: the global walk from each pair's end cell: fit (m, end_j); overlap (end_i, end_j), one of them on the last
+  // row or column -- or (m, 0), the empty overlap, whose walk the kernel's own `j > 0` ends before its first step;
   // extension (end_i, end_j) anywhere inside -- or (0, 0), the empty extension, ended by `i > 0` likewise)
-  const bool fit = fit_bytes(P) || overlap_bytes(P) || extend_bytes(P);
-  if (!nw && !sw && !fit) return MSA_ERR_UNSUPPORTED;
+  const msa_walk kind = walker_of(P);
+  if (kind != TB_NW && kind != TB_SW && kind != TB_FIT) return MSA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   P->note_stream(st);
   const int np = (int)P->d.n_pairs;
-  hipLaunchKernelGGL((fit ? traceback_batch_kernel<TB_FIT> : nw ? traceback_batch_kernel<TB_NW> : traceback_batch_kernel<TB_SW>),
+  hipLaunchKernelGGL((kind == TB_FIT  ? traceback_batch_kernel<TB_FIT>
+                      : kind == TB_NW ? traceback_batch_kernel<TB_NW>
+                                      : traceback_batch_kernel<TB_SW>),
                      dim3((unsigned)((np + TBB_WPB - 1) / TBB_WPB)), dim3(64 * TBB_WPB), 0, st, dDir, P->d_pairs,
                      P->d_meta, (const PairResult*)P->d_res, np, d_ops, (const long long*)d_ops_off,
                      (long long*)d_info);

@@ -51,7 +51,7 @@
 
 #include <type_traits>
 
-#include "msa_types.h"
+#include "msa_alg.h"
 
 #ifndef MSA_WAVES_SINGLE
 #define MSA_WAVES_SINGLE 4  // single pair: one compute wave per SIMD (latency-bound wavefront)
@@ -82,48 +82,6 @@
 #define MSA_VIRT_SCORE (-100)  // its profile byte (s + 2g space for SWL; < 0 is all that matters)
 
 namespace msa {
-
-template <int ALG> struct Tr;
-template <> struct Tr<MSA_ALG_SWL> { static constexpr int NC = 1; };
-template <> struct Tr<MSA_ALG_SWL0> { static constexpr int NC = 1; };
-template <> struct Tr<MSA_ALG_SWLP> { static constexpr int NC = 1; };
-// SW linear in shifted space (any of the three kernel ids)
-constexpr bool swlin(int alg) { return alg == MSA_ALG_SWL || alg == MSA_ALG_SWL0 || alg == MSA_ALG_SWLP; }
-// two pairs per lane: every carried value is two int16 (pair 2c low, pair 2c+1 high)
-constexpr bool pk16(int alg) { return alg == MSA_ALG_SWLP; }
-template <> struct Tr<MSA_ALG_SWA> { static constexpr int NC = 2; };
-template <> struct Tr<MSA_ALG_NWA> { static constexpr int NC = 2; };
-template <> struct Tr<MSA_ALG_FIT> { static constexpr int NC = 2; };
-template <> struct Tr<MSA_ALG_NWA32> { static constexpr int NC = 2; };
-template <> struct Tr<MSA_ALG_FIT32> { static constexpr int NC = 2; };
-template <> struct Tr<MSA_ALG_SWS> { static constexpr int NC = 2; };
-template <> struct Tr<MSA_ALG_SWS32> { static constexpr int NC = 2; };
-template <> struct Tr<MSA_ALG_OVL> { static constexpr int NC = 2; };
-template <> struct Tr<MSA_ALG_OVL32> { static constexpr int NC = 2; };
-template <> struct Tr<MSA_ALG_EXT> { static constexpr int NC = 2; };
-template <> struct Tr<MSA_ALG_EXT32> { static constexpr int NC = 2; };
-// 5-bit codes: the lane's profile is a 32-byte row of the plan's 32 x 32 table (score4_wide)
-constexpr bool wide(int alg) {
-  return alg == MSA_ALG_NWA32 || alg == MSA_ALG_FIT32 || alg == MSA_ALG_SWS32 || alg == MSA_ALG_OVL32 ||
-         alg == MSA_ALG_EXT32;
-}
-// the SW-affine cell with scores from the plan's table (swsc), with those or match / mismatch (swaf): the zero floor,
-// zero borders, best tracking and the virtual columns are the same
-constexpr bool swsc(int alg) { return alg == MSA_ALG_SWS || alg == MSA_ALG_SWS32; }
-constexpr bool swaf(int alg) { return alg == MSA_ALG_SWA || swsc(alg); }
-// the banded Gotoh cell under the global borders (nwg), the same cell under the fit alignment's zero top border
-// (fitk), either (nwa) -- over 3-bit or 5-bit codes.  The overlap kernels (ovlk) are fit kernels -- the zero top border
-// and the row-m maximum are theirs unchanged -- with a zero left border and the last column's maximum besides
-constexpr bool nwg(int alg) { return alg == MSA_ALG_NWA || alg == MSA_ALG_NWA32; }
-constexpr bool ovlk(int alg) { return alg == MSA_ALG_OVL || alg == MSA_ALG_OVL32; }
-constexpr bool fitk(int alg) { return alg == MSA_ALG_FIT || alg == MSA_ALG_FIT32 || ovlk(alg); }
-// The extension kernels (extk) are the unbanded global kernels -- cell, both borders, bytes -- and keep, beside them,
-// the first maximum of H over ALL interior cells (values may be negative: no zero floor, no packed key)
-constexpr bool extk(int alg) { return alg == MSA_ALG_EXT || alg == MSA_ALG_EXT32; }
-constexpr bool nwa(int alg) { return nwg(alg) || fitk(alg) || extk(alg); }
-template <> struct Tr<MSA_ALG_REF> { static constexpr int NC = 3; };
-template <> struct Tr<MSA_ALG_REF1> { static constexpr int NC = 2; };
-template <> struct Tr<MSA_ALG_PART> { static constexpr int NC = 3; };
 
 // packed int16 helpers (v_pk_add_u16 / v_pk_max_i16 on gfx950)
 typedef short msa_s2 __attribute__((ext_vector_type(2)));
@@ -219,10 +177,10 @@ struct KArgs {
   // two-pass SW single pair: the pass-2 blocks fold the pair result into this key themselves
   // (fl_block_result, msa_flow.hip) when set; else reduce_blocks_kernel runs after the launch
   unsigned long long* best_key;
-  // MSA_ALG_NWA, MSA_ALG_FIT: the plan's substitution table, one 8-byte profile per row code (byte b of entry a = the
-  // score of row code a against column code b, in the launch's own space: msa_plan.inc, sub_table).
-  // MSA_ALG_NWA32, MSA_ALG_FIT32, MSA_ALG_OVL32, MSA_ALG_EXT32: 1,024 raw scores, byte 32 a + b.
-  // MSA_ALG_SWS / MSA_ALG_SWS32: the same two layouts, the virtual code's column (7 / 31) holding MSA_VIRT_SCORE
+  // algorithms that score from a table: the plan's substitution table, one 8-byte profile per row code (byte b of
+  // entry a = the score of row code a against column code b, in the launch's own space: msa_plan.inc, alloc_buffers).
+  // 5-bit codes: 1,024 raw scores, byte 32 a + b.
+  // Smith-Waterman: the same two layouts, the virtual code's column (7 / 31) holding MSA_VIRT_SCORE
   const uint2* sub;
 };
 #ifndef MSA_H16_PAIRED
@@ -234,23 +192,21 @@ __device__ __forceinline__ void border_top(const msa_kparams& kp, int c, int (&v
   // Row 0 of the DP at column c (c may be < 0: unused, return NEG).  Banded Gotoh,
   // r0 > 0 (chunked mode): the GUESSED row r0 a chunk's warm-up starts from -- the
   // row-0 border's tent moved to the diagonal, H = -h - g*|c - r0| inside the band.
-  if constexpr (swlin(ALG)) {
-    // G(0,c) = H(0,c) + g*c = g*c; SWL0 also on the virtual columns c < 0
-    v[0] = (c >= 0 || ALG == MSA_ALG_SWL0 || ALG == MSA_ALG_SWLP) ? kp.gap_open * c : MSA_NEG;
-    if constexpr (pk16(ALG)) v[0] = pk2(v[0]);
+  constexpr msa_alg_info TR = msa_alg_info_of(ALG);
+  if constexpr (TR.linear()) {
+    // G(0,c) = H(0,c) + g*c = g*c; without the floor also on the virtual columns c < 0
+    v[0] = (c >= 0 || TR.cell != CELL_LIN_FLOOR) ? kp.gap_open * c : MSA_NEG;
+    if constexpr (TR.packed()) v[0] = pk2(v[0]);
     v[1] = MSA_NEG;
     v[2] = MSA_NEG;
-  } else if constexpr (swaf(ALG)) {
+  } else if constexpr (TR.top == BORDER_FREE) {
+    // SW affine; the Gotoh cell of a fit or overlap alignment, where the reference's symbols before the aligned
+    // substring are free: H(0,c) = 0 on every column c >= 0 (columns past n are masked where they are read, as the
+    // global kernels' are); E = F = -inf
     v[0] = c >= 0 ? 0 : MSA_NEG;  // H
     v[1] = MSA_NEG;               // F
     v[2] = MSA_NEG;
-  } else if constexpr (fitk(ALG)) {
-    // the reference's symbols before the aligned substring are free: H(0,c) = 0 on every column c >= 0 (columns
-    // past n are masked where they are read, as MSA_ALG_NWA's are); E = F = -inf
-    v[0] = c >= 0 ? 0 : MSA_NEG;
-    v[1] = MSA_NEG;
-    v[2] = MSA_NEG;
-  } else if constexpr (nwg(ALG) || extk(ALG)) {  // (extk: kp.band = -1, r0 = 0)
+  } else if constexpr (TR.cell == CELL_GOTOH) {  // (no band accepted: kp.band = -1, r0 = 0)
     if (r0 > 0) {
       const int d = c > r0 ? c - r0 : r0 - c;
       v[0] = (d <= kp.band) ? -kp.h - kp.gap_ext * d : MSA_NEG;
@@ -261,7 +217,7 @@ __device__ __forceinline__ void border_top(const msa_kparams& kp, int c, int (&v
     }
     v[1] = MSA_NEG;
     v[2] = MSA_NEG;
-  } else if constexpr (ALG == MSA_ALG_REF1) {
+  } else if constexpr (TR.cell == CELL_REF_TAG) {
     // row 0 for start type -1 (:212-227): T1(0,0) = 0, T2(0,c) = -h-g*c (c >= 1), rest -inf;
     // tagged (see step<REF1>): v[0] = max(T1,T2,T3)~, v[1] = the row below's T3 candidates~
     const int GH = kp.gap_open, G = kp.gap_ext;
@@ -275,7 +231,7 @@ __device__ __forceinline__ void border_top(const msa_kparams& kp, int c, int (&v
       v[1] = 4 * (t2 - GH) + 2;
     }
     v[2] = MSA_NEG;
-  } else if constexpr (ALG == MSA_ALG_REF) {
+  } else if constexpr (TR.cell == CELL_REF3) {
     // compute_row(0) / ComputeFirstRowMapThread (subproblem_alignment.cpp:212-227,259-280)
     const int st = kp.start_type;
     const int g = kp.gap_ext, h = kp.h;
@@ -300,27 +256,28 @@ __device__ __forceinline__ void border_top(const msa_kparams& kp, int c, int (&v
 template <int ALG>
 __device__ __forceinline__ void border_left(const msa_kparams& kp, int i, int (&v)[3]) {
   // Column 0 of row i (i >= 1), state order of each algorithm.
-  if constexpr (swlin(ALG)) {
-    v[0] = pk16(ALG) ? pk2(kp.gap_open * i) : kp.gap_open * i;  // G(i,0) = H(i,0) + g*i
+  constexpr msa_alg_info TR = msa_alg_info_of(ALG);
+  if constexpr (TR.linear()) {
+    v[0] = TR.packed() ? pk2(kp.gap_open * i) : kp.gap_open * i;  // G(i,0) = H(i,0) + g*i
     v[1] = MSA_NEG;
     v[2] = MSA_NEG;
-  } else if constexpr (swaf(ALG) || ovlk(ALG)) {
+  } else if constexpr (TR.left == BORDER_FREE) {
     // (overlap: A's symbols before the aligned suffix are free, as the fit top border's are on B)
     v[0] = 0;        // H
     v[1] = MSA_NEG;  // E
     v[2] = MSA_NEG;  // F
-  } else if constexpr (nwa(ALG)) {  // (FIT, EXT: kp.band = -1)
+  } else if constexpr (TR.cell == CELL_GOTOH) {  // (no band accepted: kp.band = -1)
     const bool inb = (kp.band < 0) || (i <= kp.band);
     v[0] = inb ? -kp.h - kp.gap_ext * i : MSA_NEG;  // H
     v[1] = MSA_NEG;                                 // T2 (E)
     v[2] = v[0];                                    // T3 (F) = -h-g*i
-  } else if constexpr (ALG == MSA_ALG_REF1) {
+  } else if constexpr (TR.cell == CELL_REF_TAG) {
     // column 0 for start type -1 (:282-292): T1 = T2 = -inf, T3 = -h-g*i; state (H~, R~, D~)
     const int t3 = -kp.h - kp.gap_ext * i;
     v[0] = 4 * t3 + 1;
     v[1] = 4 * (t3 - kp.gap_open) + 1;
     v[2] = 4 * (t3 - kp.gap_ext) + 1;
-  } else if constexpr (ALG == MSA_ALG_REF) {
+  } else if constexpr (TR.cell == CELL_REF3) {
     // compute_row(i>0) borders (subproblem_alignment.cpp:282-292)
     const int st = kp.start_type;
     v[0] = MSA_NEG;
@@ -346,7 +303,8 @@ struct LaneState {
   int pb;        // SWLP: max over the current phase's steps k of G - g k (both pairs, int16)
   int fin[3];
   unsigned plo, phi;  // substitution profile (8 int8 scores by column code)
-  unsigned pw[wide(ALG) ? 8 : 1];  // 5-bit codes: the profile, 32 int8 scores by column code (plo / phi unused)
+  // 5-bit codes: the profile, 32 int8 scores by column code (plo / phi unused)
+  unsigned pw[msa_alg_info_of(ALG).wide ? 8 : 1];
   int i;              // DP row
 };
 
@@ -365,10 +323,11 @@ struct LaneState {
 template <int ALG, int OUT, bool MASKED, int TRACKPOS, bool FIN = false>
 __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& L, const int (&in)[3], int s,
                                          int t, int ct, int (&carry)[3], int& hout) {
+  constexpr msa_alg_info TR = msa_alg_info_of(ALG);
   unsigned dir = 0;
   int nS[3];
   int fin_tab[3];  // REF1: the cell's untagged T1, T2, T3 (the final state at (m, n))
-  if constexpr (ALG == MSA_ALG_SWL) {
+  if constexpr (TR.cell == CELL_LIN_FLOOR) {
     // ct = g*(i+j) is the same for every lane (one anti-diagonal): an SGPR
     const int up = dpp_shr1(in[0], L.S[0]);
     const int x = imax(L.U[0] + s, ct);
@@ -377,14 +336,14 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
     // running max3 chain and distributes the "- ct" over every term)
     asm("" : "+v"(nS[0]));
     L.U[0] = up;
-  } else if constexpr (ALG == MSA_ALG_SWLP) {
-    // MSA_ALG_SWL0 on two pairs at once: s holds both pairs' score + 2g as int16.  The cell above (the
+  } else if constexpr (TR.cell == CELL_LIN_PK16) {
+    // CELL_LIN on two pairs at once: s holds both pairs' score + 2g as int16.  The cell above (the
     // DPP from lane r-1) enters last: the loop-carried path per step is DPP -> one v_pk_max_i16, the
     // diagonal-left max runs in the DPP's wait states
     const int up = dpp_shr1(in[0], L.S[0]);
     nS[0] = pk_max(pk_max(pk_add(L.U[0], s), L.S[0]), up);
     L.U[0] = up;
-  } else if constexpr (ALG == MSA_ALG_SWL0) {
+  } else if constexpr (TR.cell == CELL_LIN) {
     // all scores >= 0: G(i-1,j-1) + s + 2g >= g*(i+j) whenever the diagonal
     // cell satisfies its own floor, so (by induction from the borders) the
     // zero floor never binds and is dropped.  Virtual columns score 0, which
@@ -393,7 +352,7 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
     nS[0] = imax3(L.U[0] + s, up, L.S[0]);
     asm("" : "+v"(nS[0]));
     L.U[0] = up;
-  } else if constexpr (swaf(ALG)) {
+  } else if constexpr (TR.cell == CELL_SWAFF) {
     const int upH = dpp_shr1(in[0], L.S[0]);
     const int upF = dpp_shr1(in[1], L.S[2]);
     const int f = imax(upF - kp.gap_ext, upH - kp.gap_open);
@@ -410,7 +369,7 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
     nS[1] = e;
     nS[2] = f;
     L.U[0] = upH;
-  } else if constexpr (nwa(ALG)) {
+  } else if constexpr (TR.cell == CELL_GOTOH) {
     const int upH = dpp_shr1(in[0], L.S[0]);
     const int upF = dpp_shr1(in[1], L.S[2]);
     const int t3 = imax(upH - kp.gap_open, upF - kp.gap_ext);
@@ -428,7 +387,7 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
     nS[1] = t2;
     nS[2] = t3;
     L.U[0] = upH;
-  } else if constexpr (ALG == MSA_ALG_REF1) {
+  } else if constexpr (TR.cell == CELL_REF_TAG) {
     // Start type -1: every table value of every cell with i, j >= 1 is finite (each has a
     // finite predecessor), so -inf needs no exact emulation and the three first-maximum
     // selections of find_alignment (:130-145) fold into the maxima: a value of table k is
@@ -455,7 +414,7 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
     fin_tab[1] = t2 >> 2;
     fin_tab[2] = t3 >> 2;
     L.U[0] = uH;
-  } else if constexpr (ALG == MSA_ALG_REF) {
+  } else if constexpr (TR.cell == CELL_REF3) {
     const int u0 = dpp_shr1(in[0], L.S[0]);
     const int u1 = dpp_shr1(in[1], L.S[1]);
     const int u2 = dpp_shr1(in[2], L.S[2]);
@@ -489,15 +448,15 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
     L.U[1] = u1;
     L.U[2] = u2;
   }
-  constexpr int NS = swlin(ALG) ? 1 : 3;
+  constexpr int NS = TR.linear() ? 1 : 3;
   (void)fin_tab;
   if constexpr (MASKED) {
     const bool before = t < L.tmin;
     const bool after = t > L.tmax;
 #pragma unroll
     for (int v = 0; v < NS; ++v) nS[v] = before ? L.LB[v] : (after ? MSA_NEG : nS[v]);
-    if constexpr (swlin(ALG) || swaf(ALG)) {
-      const int hv = swlin(ALG) ? nS[0] - ct : nS[0];
+    if constexpr (TR.local()) {
+      const int hv = TR.linear() ? nS[0] - ct : nS[0];
       hout = hv;
       if constexpr (TRACKPOS == 2) {
         L.best = imax(L.best, (!before && !after) ? (hv << 15) + (32767 - t) : 0);
@@ -511,11 +470,11 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
     } else if constexpr (FIN) {  // only the stripe holding row m
       if (t == L.tmax) {
 #pragma unroll
-        for (int v = 0; v < 3; ++v) L.fin[v] = (ALG == MSA_ALG_REF1) ? fin_tab[v] : nS[v];
+        for (int v = 0; v < 3; ++v) L.fin[v] = (TR.cell == CELL_REF_TAG) ? fin_tab[v] : nS[v];
       }
     }
   } else {
-    if constexpr (pk16(ALG)) {
+    if constexpr (TR.packed()) {
       // ct = pk2(-g k) for step k of the phase (an SGPR fixed for the whole launch): the phase's best
       // of G - g k in both halves; the phase's g (i + j) at its step 0 is subtracted once per phase
       // (run_phase), so no scalar arithmetic runs per step
@@ -524,8 +483,8 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
       // values, and these updates are dead code there)
       L.pb = pk_max(L.pb, pk_add(nS[0], ct));
       hout = 0;
-    } else if constexpr (swlin(ALG) || swaf(ALG)) {
-      const int hv = swlin(ALG) ? nS[0] - ct : nS[0];
+    } else if constexpr (TR.local()) {
+      const int hv = TR.linear() ? nS[0] - ct : nS[0];
       hout = hv;
       if constexpr (TRACKPOS == 2) {
         L.best = imax(L.best, (hv << 15) + (32767 - t));
@@ -539,9 +498,9 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
 #pragma unroll
   for (int v = 0; v < NS; ++v) L.S[v] = nS[v];
   // carried values (what the lane below / next stripe needs)
-  if constexpr (swlin(ALG)) {
+  if constexpr (TR.nc == 1) {
     carry[0] = nS[0];
-  } else if constexpr (swaf(ALG) || nwa(ALG) || ALG == MSA_ALG_REF1) {
+  } else if constexpr (TR.nc == 2) {
     carry[0] = nS[0];
     carry[1] = nS[2];
   } else {
@@ -574,7 +533,7 @@ __device__ __forceinline__ unsigned step(const msa_kparams& kp, LaneState<ALG>& 
 // last-column candidate in the stripes that do not hold row m).
 template <int FIN, int ALG>
 __device__ __forceinline__ void band_fix(LaneState<ALG>& L, int t, int (&carry)[3]) {
-  static_assert(nwa(ALG), "the Gotoh cell's state order");
+  static_assert(msa_alg_info_of(ALG).cell == CELL_GOTOH, "the Gotoh cell's state order");
   const bool fl = (t == L.tmin - 1);
 #pragma unroll
   for (int v = 0; v < 3; ++v) L.S[v] = fl ? L.LB[v] : L.S[v];
@@ -694,11 +653,12 @@ template <int ALG, int OUT, int TRACKPOS, int W, int KS, bool SGL>
 __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KArgs a) {
   static_assert(KS % 16 == 0 && KS <= 64, "phases are whole 16-step layout blocks");
   constexpr int CPP = KS / 16;  // 16-column chunks per phase
-  constexpr int NC = Tr<ALG>::NC;
+  constexpr msa_alg_info TR = msa_alg_info_of(ALG);
+  constexpr int NC = TR.nc;
   // Smith-Waterman kernels never mask: columns outside [1, n] carry the
   // virtual code whose score (MSA_VIRT_SCORE) keeps every out-of-matrix cell
   // strictly below a real cell, so the plain recurrence runs over them.
-  constexpr bool SWK = (swlin(ALG) || swaf(ALG));
+  constexpr bool SWK = TR.local();
   extern __shared__ __attribute__((aligned(16))) int smem[];
   const msa_kparams& kp = a.kp;
   const int lane = threadIdx.x & 63;
@@ -728,7 +688,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
   // two HBM latencies in a row in front of the workgroup's barriers at every round of stripes, or on the stripe's
   // start if issued behind them; 32 rows are too many for the 8-code kernels' uniform loads and select chain.
   unsigned* subl = cring + (LDSCODE ? 4 * CRW : 0);
-  if constexpr (wide(ALG)) {
+  if constexpr (TR.wide) {
     if (threadIdx.x < 256) subl[threadIdx.x] = reinterpret_cast<const unsigned*>(a.sub)[threadIdx.x];
   }
 
@@ -755,7 +715,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
       // chained through granules; inside an item the waves cycle as in batch mode
       const int pidx = item / kp.groups;
       group = item - pidx * kp.groups;
-      pair = pk16(ALG) ? 2 * pidx : pidx;
+      pair = TR.packed() ? 2 * pidx : pidx;
       k0 = group * kp.chunk_c;
       const int S = (a.pairs[pair].m + 63) / 64;
       ns = min(kp.chunk_c, S - k0);
@@ -773,14 +733,14 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
       ns = ke - kb;
       nwarm = ks0 - kb;
     } else {
-      pair = pk16(ALG) ? 2 * item : item;  // SWLP: item c = pairs 2c (low halves) and 2c+1 (high)
+      pair = TR.packed() ? 2 * item : item;  // SWLP: item c = pairs 2c (low halves) and 2c+1 (high)
       group = 0;
       k0 = 0;
       ns = (a.pairs[pair].m + 63) / 64;
     }
     const msa_pair_desc pd = a.pairs[pair];
     // SWLP: the pair in the high halves (the last item of an odd count repeats its low pair)
-    const msa_pair_desc pd2 = pk16(ALG) ? a.pairs[min(pair + 1, kp.n_pairs - 1)] : pd;
+    const msa_pair_desc pd2 = TR.packed() ? a.pairs[min(pair + 1, kp.n_pairs - 1)] : pd;
     const int m = pd.m, n = pd.n;
     const int S_pair = (m + 63) / 64;
 
@@ -1034,15 +994,15 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
       // (on the critical path of the wavefront if it waited for the stripe start)
       const int ks = k0 + cur;  // pair-local stripe index
       const int row_i = 64 * ks + lane + 1;
-      constexpr unsigned CMASK = wide(ALG) ? 31u : 7u;
+      constexpr unsigned CMASK = TR.wide ? 31u : 7u;
       const unsigned ac = (row_i <= m) ? (a.A[pd.a_off + row_i - 1] & CMASK) : 0u;
-      const unsigned ac2 = (pk16(ALG) && row_i <= m) ? (a.A[pd2.a_off + row_i - 1] & 7u) : 0u;
+      const unsigned ac2 = (TR.packed() && row_i <= m) ? (a.A[pd2.a_off + row_i - 1] & 7u) : 0u;
       // banded Gotoh: the row's profile is row ac of the plan's table.  The whole 64-byte table is loaded here at
       // wave-uniform addresses, independent of the row code's load and like it ahead of the idle phases; the lane's
       // row is taken by selects at the stripe's start (a load at a.sub[ac] would wait for ac here, in front of the
       // workgroup's barriers)
       uint2 tab[8] = {};
-      if constexpr ((nwa(ALG) || swsc(ALG)) && !wide(ALG)) {
+      if constexpr (TR.table && !TR.wide) {
 #pragma unroll
         for (int c = 0; c < 8; ++c) tab[c] = a.sub[c];
       }
@@ -1061,7 +1021,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         for (int v = 0; v < 3; ++v) { L.LB[v] = lb[v]; L.S[v] = lb[v]; L.U[v] = MSA_NEG; L.fin[v] = 0; }
       }
       // (FIT: every H(m, j) is finite, > MSA_NEG; EXT: so is every interior H, and it may well be negative)
-      L.best = (fitk(ALG) || extk(ALG)) ? INT32_MIN : 0;
+      L.best = TR.row_max() ? INT32_MIN : 0;
       L.bt = -1;
       L.pb = (int)0x80008000u;
       const int gdiag = kp.gap_open * (64 * ks + 1 + sg.cs);  // SWL: g*(i+j) at step 0, same for all lanes
@@ -1070,27 +1030,27 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
       int gkp[KS];
 #pragma unroll
       for (int k = 0; k < KS; ++k) {
-        gkp[k] = pk16(ALG) ? pk2(-kp.gap_open * k) : 0;
-        if constexpr (pk16(ALG)) asm("" : "+s"(gkp[k]));
+        gkp[k] = TR.packed() ? pk2(-kp.gap_open * k) : 0;
+        if constexpr (TR.packed()) asm("" : "+s"(gkp[k]));
       }
       // SWL: the lane starts left of the matrix on virtual cells with H = 0,
       // i.e. G = g*(i+j); its left neighbour at step 0 is G = gdiag - g
-      if constexpr (swlin(ALG)) {
+      if constexpr (TR.linear()) {
         L.S[0] = gdiag - kp.gap_open;      // G(i, cs-r-1)
         L.U[0] = gdiag - 2 * kp.gap_open;  // G(i-1, cs-r-1)
-        if constexpr (pk16(ALG)) {
+        if constexpr (TR.packed()) {
           L.S[0] = pk2(L.S[0]);
           L.U[0] = pk2(L.U[0]);
         }
       }
       // substitution profile of this row (codes 0..7; 5-bit codes: 0..31, row ac of the LDS table)
-      if constexpr (wide(ALG)) {
+      if constexpr (TR.wide) {
         const uint4* prow = reinterpret_cast<const uint4*>(subl + 8 * ac);
         const uint4 p0 = prow[0], p1 = prow[1];
         L.pw[0] = p0.x; L.pw[1] = p0.y; L.pw[2] = p0.z; L.pw[3] = p0.w;
         L.pw[4] = p1.x; L.pw[5] = p1.y; L.pw[6] = p1.z; L.pw[7] = p1.w;
         L.plo = L.phi = L.plo2 = L.phi2 = 0;
-      } else if constexpr (nwa(ALG) || swsc(ALG)) {  // (MSA_ALG_SWS: byte 7 of every row is MSA_VIRT_SCORE already)
+      } else if constexpr (TR.table) {  // (Smith-Waterman: byte 7 of every row is MSA_VIRT_SCORE already)
         L.plo = tab[0].x;
         L.phi = tab[0].y;
 #pragma unroll
@@ -1104,7 +1064,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         if constexpr (ALG == MSA_ALG_REF) { sm = 1; sx = 0; }
         else if constexpr (ALG == MSA_ALG_REF1) { sm = 4; sx = 0; }  // 4f: tagged values
         else if constexpr (ALG == MSA_ALG_PART) { sm = 0; sx = 1; }
-        else if constexpr (swlin(ALG)) { sm = kp.match + 2 * kp.gap_open; sx = kp.mismatch + 2 * kp.gap_open; }
+        else if constexpr (TR.linear()) { sm = kp.match + 2 * kp.gap_open; sx = kp.mismatch + 2 * kp.gap_open; }
         else { sm = kp.match; sx = kp.mismatch; }
         const unsigned bx = (unsigned)(sx & 0xff) * 0x01010101u;
         auto table = [&](unsigned c, unsigned& plo_, unsigned& phi_) __attribute__((always_inline)) {
@@ -1115,7 +1075,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
           // virtual columns: SWL0 scores them 0, so (floor-free) G = g*(i+j), i.e.
           // H = 0, holds exactly on every cell left of column 1 -- the border
           // column itself; right of column n they never beat a real cell
-          if constexpr (ALG == MSA_ALG_SWL0 || ALG == MSA_ALG_SWLP)
+          if constexpr (TR.linear() && TR.cell != CELL_LIN_FLOOR)
             hi = (hi & 0x00ffffffu) | ((unsigned)((2 * kp.gap_open) & 0xff) << 24);
           else if constexpr (SWK) hi = (hi & 0x00ffffffu) | ((unsigned)(MSA_VIRT_SCORE & 0xff) << 24);
           plo_ = lo;
@@ -1123,7 +1083,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         };
         table(ac, L.plo, L.phi);
         L.plo2 = L.phi2 = 0;
-        if constexpr (pk16(ALG)) table(ac2, L.plo2, L.phi2);
+        if constexpr (TR.packed()) table(ac2, L.plo2, L.phi2);
       }
       // code stream: lane r needs columns cs - r + t; column c sits in copy
       // (c-1+CPAD)&15 at byte (c-1+CPAD) & ~15, so every read is an aligned dwordx4
@@ -1139,7 +1099,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
       // packed batches (C4): codes two phases ahead (cwn = phase q+1, cwn2 = phase q+2): one phase of
       // lock-step computing did not cover a global load's latency (stamps: ~0.3 us of a 1.04 us phase
       // waited for the codes)
-      constexpr bool CPF2 = pk16(ALG) && !LDSCODE;
+      constexpr bool CPF2 = TR.packed() && !LDSCODE;
       unsigned cwn2[KS / 4];
       const int cj0 = sg.cs - lane;                // column of this lane at step 0
       const unsigned* cr_base = cring + (cj0 & 3) * CRW;
@@ -1258,7 +1218,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
               for (int k = 0; k < KS; ++k) {
                 const bool o = sg.cs + KS * q + k > out_chi;
 #pragma unroll
-                for (int v = 0; v < NC; ++v) IN[v][k] = o ? (pk16(ALG) ? (int)0x80008000u : MSA_NEG) : IN[v][k];
+                for (int v = 0; v < NC; ++v) IN[v][k] = o ? (TR.packed() ? (int)0x80008000u : MSA_NEG) : IN[v][k];
               }
             }
           }
@@ -1295,25 +1255,25 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
 #pragma unroll
         for (int u = 0; u < KS / 4; ++u) {
           unsigned s4;
-          if constexpr (wide(ALG)) s4 = score4_wide(L.pw, cw[u]);
+          if constexpr (TR.wide) s4 = score4_wide(L.pw, cw[u]);
           else s4 = __builtin_amdgcn_perm(L.phi, L.plo, cw[u]);
-          const unsigned s4b = pk16(ALG) ? __builtin_amdgcn_perm(L.phi2, L.plo2, cw[u]) : 0u;
+          const unsigned s4b = TR.packed() ? __builtin_amdgcn_perm(L.phi2, L.plo2, cw[u]) : 0u;
           unsigned dq = 0;
 #pragma unroll
           for (int kk = 0; kk < 4; ++kk) {
             const int k = 4 * u + kk;
             const int t = KS * q + k;
             // SWLP: {s4 byte kk, 0, s4b byte kk, 0} = both pairs' score + 2g as int16 (>= 0)
-            const int s = pk16(ALG) ? (int)__builtin_amdgcn_perm(s4b, s4, 0x0c000c00u | ((4u + kk) << 16) | (unsigned)kk)
+            const int s = TR.packed() ? (int)__builtin_amdgcn_perm(s4b, s4, 0x0c000c00u | ((4u + kk) << 16) | (unsigned)kk)
                                     : ((int)(s4 << (24 - 8 * kk))) >> 24;
             int inv[3];
 #pragma unroll
             for (int v = 0; v < NC; ++v) inv[v] = IN[v][k];
             int cr[3];
-            int ct = pk16(ALG) ? gkp[k] : gdiag + kp.gap_open * t;
-            if constexpr (swlin(ALG) && !pk16(ALG)) asm("" : "+s"(ct));  // one SGPR feeds both the floor and H
+            int ct = TR.packed() ? gkp[k] : gdiag + kp.gap_open * t;
+            if constexpr (TR.linear() && !TR.packed()) asm("" : "+s"(ct));  // one SGPR feeds both the floor and H
             unsigned d;
-            if constexpr (nwg(ALG) && MMODE >= 2) {
+            if constexpr (TR.band && MMODE >= 2) {
               d = step<ALG, OUT, false, TRACKPOS, false>(kp, L, inv, s, t, ct, cr, hv[k]);
               // one lane per two steps sits on the band's edge: its index is wave-uniform
               constexpr int PAR = MMODE & 1;
@@ -1337,13 +1297,13 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
                   cr[1] = L.S[2];
                 }
               }
-            } else if constexpr (nwa(ALG) && MASKED) {
+            } else if constexpr (TR.cell == CELL_GOTOH && MASKED) {
               d = step<ALG, OUT, false, TRACKPOS, false>(kp, L, inv, s, t, ct, cr, hv[k]);
               band_fix<FMODE>(L, t, cr);
             } else {
               d = step<ALG, OUT, MASKED, TRACKPOS, FIN>(kp, L, inv, s, t, ct, cr, hv[k]);
             }
-            if constexpr ((fitk(ALG) && FIN) || extk(ALG)) {
+            if constexpr ((TR.row_m() && FIN) || TR.result == RES_BEST_ANY) {
               // the stripe of row m (every phase of it, the unmasked body too: FIN): a lane keeps the first
               // maximum of its row's H over the row's own columns 1..n -- strict >, so the earliest step wins;
               // a step on column <= 0 or > n (t outside [tmin, tmax]) never counts, and in an unmasked phase
@@ -1397,12 +1357,12 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
           if (!outp) {
           } else if constexpr (OUT == MSA_OUT_H) {
             int4 h4;
-            if constexpr (ALG == MSA_ALG_REF || ALG == MSA_ALG_PART) {
+            if constexpr (NC == 3) {  // three tables: H is their maximum
               h4 = make_int4(imax3(hist[0][4 * u], hist[1][4 * u], hist[2][4 * u]),
                              imax3(hist[0][4 * u + 1], hist[1][4 * u + 1], hist[2][4 * u + 1]),
                              imax3(hist[0][4 * u + 2], hist[1][4 * u + 2], hist[2][4 * u + 2]),
                              imax3(hist[0][4 * u + 3], hist[1][4 * u + 3], hist[2][4 * u + 3]));
-            } else if constexpr (swlin(ALG) || swaf(ALG)) {
+            } else if constexpr (TR.local()) {
               h4 = make_int4(hv[4 * u], hv[4 * u + 1], hv[4 * u + 2], hv[4 * u + 3]);
             } else {
               h4 = make_int4(hist[0][4 * u], hist[0][4 * u + 1], hist[0][4 * u + 2], hist[0][4 * u + 3]);
@@ -1420,7 +1380,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
             ntstore(reinterpret_cast<int4*>(a.outDir + obase) + (size_t)(CPP * q + h) * 64 + lane,
                     make_int4((int)dirw[4 * h], (int)dirw[4 * h + 1], (int)dirw[4 * h + 2], (int)dirw[4 * h + 3]));
         }
-        if constexpr (pk16(ALG)) {
+        if constexpr (TR.packed()) {
           // both pairs' H = G - g (i + j): the phase's best of G - g k, minus g (i + j) at its step 0.
           // KS = 16, unmasked: max over k of G_k - g k as a four-level tree over the carried values
           // (independent ops, no serial chain of 16 dependent max with their wait states)
@@ -1480,10 +1440,10 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         run_range(qi, P, F_{}, T_{}, F_{});
       } else if (fin_stripe) {
         run_range(0, qa, T_{}, T_{}, T_{});
-        if constexpr (fitk(ALG)) run_range(qa, qb, F_{}, F_{}, T_{});  // (row m's maximum: every phase)
+        if constexpr (TR.row_m()) run_range(qa, qb, F_{}, F_{}, T_{});  // (row m's maximum: every phase)
         else run_range(qa, qb, F_{}, F_{}, F_{});
         run_range(qb, P, T_{}, T_{}, T_{});
-      } else if constexpr (ovlk(ALG)) {
+      } else if constexpr (TR.result == RES_ROW_M_COL) {
         // every stripe has column candidates: lane r's row reaches column n at t = tmax = n - cs + r.  mask_hi is
         // lane 0's tmax less 1 and tmax grows with the lane, so no unmasked phase [qa, qb) holds any row's last
         // step: the capture lives in the masked head (a short B ends there) and tail alone, and the body is fit's
@@ -1500,7 +1460,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         // and every other stripe, band_fix.
         bool regular = false;
         int A0 = 0, C0 = 0;
-        if constexpr (nwg(ALG)) {
+        if constexpr (TR.band) {
           const int i0 = 64 * ks + 1;
           regular = uni(kp.band >= 64 && i0 + 63 <= m && i0 - kp.band > 1 && i0 + 63 + kp.band < n);
           A0 = uni(jlo_of(i0, kp.band) - sg.cs);
@@ -1542,7 +1502,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
       // ---- stripe finalize ----
       msa_stripe_meta* md = a.meta + pd.stripe0 + ks;
       if (!outp) continue;  // a warm-up stripe: its meta belongs to the chunk that outputs it
-      if constexpr (pk16(ALG)) {
+      if constexpr (TR.packed()) {
         // each half separately: pair 2c's best (low halves), then pair 2c+1's (high halves)
         msa_stripe_meta* md2 = a.meta + pd2.stripe0 + ks;
 #pragma unroll
@@ -1565,7 +1525,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
             mh->phases = sg.P * CPP;
           }
         }
-      } else if constexpr (swlin(ALG) || swaf(ALG)) {
+      } else if constexpr (TR.local()) {
         // first max in row-major order: max best, then min row
         const int bv = (TRACKPOS == 2) ? (L.best >> 15) : L.best;
         const int bt = (TRACKPOS == 2) ? 32767 - (L.best & 32767) : L.bt;
@@ -1585,10 +1545,10 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
           md->best_j = TRACKPOS ? bj : -1;
         }
       } else {
-        if constexpr (extk(ALG)) {
+        if constexpr (TR.result == RES_BEST_ANY) {
           // the stripe's first maximum in row-major order, as the SW branch above finds it: max value, then min row
           // (a lane's own bt is already its row's smallest column).  Rows past m (the last stripe) never count;
-          // lane 0's row always does, so b is a cell's H.  No test against 0 here: reduce_pairs_kernel's mode 4
+          // lane 0's row always does, so b is a cell's H.  No test against 0 here: reduce_pairs_kernel's RES_BEST_ANY
           int b = (L.i <= m) ? L.best : INT32_MIN;
           int bi = L.i;
           int bj = sg.cs + L.bt - lane;
@@ -1605,7 +1565,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
             md->best_j = bj;
           }
         }
-        if constexpr (ovlk(ALG)) {
+        if constexpr (TR.result == RES_ROW_M_COL) {
           // the stripe's last-column candidate: max over its rows i <= m of H(i, n) (L.fin[0], captured at t == tmax
           // in a masked phase of every stripe), the smaller row on a tie.  Rows past m (the last stripe) never count
           int b = (L.i <= m) ? L.fin[0] : INT32_MIN;
@@ -1622,7 +1582,7 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
           }
         }
         if (L.i == m) {
-          if constexpr (fitk(ALG)) {
+          if constexpr (TR.row_m()) {
             md->best = L.best;
             md->best_i = m;
             md->best_j = sg.cs + L.bt - lane;
@@ -1854,10 +1814,8 @@ __global__ __launch_bounds__(256) void chunk_add_kernel(int32_t* H, const int16_
 }
 
 __global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* pairs, const msa_stripe_meta* meta,
-                                                         int n_pairs, int sw, PairResult* out) {
-  // sw: 1 Smith-Waterman (the best cell of any stripe), 0 global (the final state at (m, n)), 2 fit alignment,
-  // 3 overlap alignment (fit's row-m maximum against the best last-column candidate of any stripe), 4 extension
-  // alignment (the best cell of any stripe over values that may be negative, with the global final state beside it)
+                                                         int n_pairs, int rule, PairResult* out) {
+  // rule: the algorithm's msa_result (msa_alg.h)
   // one wave per pair: lanes stride over the pair's stripes (a serial loop of
   // dependent meta loads took ~27 us for a 157-stripe pair)
   const int p = blockIdx.x;
@@ -1869,7 +1827,7 @@ __global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* p
   r.status = 0;
   r.pad = 0;
   r.fin[0] = r.fin[1] = r.fin[2] = 0;
-  if (sw == 1) {
+  if (rule == RES_BEST) {
     // first max in row-major order; the empty alignment (score 0 at (0,0))
     // wins unless some stripe has a positive best
     int b = 0, bi = 0, bj = 0;
@@ -1894,13 +1852,13 @@ __global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* p
     r.end_i = pd.m;
     r.end_j = pd.n;
     r.status = md.has_fin ? 0 : -1;
-    if (sw == 2 || sw == 3) {
+    if (rule == RES_ROW_M || rule == RES_ROW_M_COL) {
       // fit alignment: the first maximum of row m, found by the stripe of row m (fin stays (H, E, F) at (m, n),
       // which is not part of this algorithm's result)
       r.score = md.best;
       r.end_j = md.best_j;
     }
-    if (sw == 3) {
+    if (rule == RES_ROW_M_COL) {
       // overlap alignment: the column candidates H(i, n), one per stripe (its maximum, its smallest row); lanes
       // stride over the stripes -- rows increase with s, so a lane keeps its first maximum with a strict > -- and
       // the smaller row wins a tie across lanes
@@ -1926,7 +1884,7 @@ __global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* p
         r.end_j = 0;
       }
     }
-    if (sw == 4) {
+    if (rule == RES_BEST_ANY) {
       // extension alignment: fin (H, E, F at (m, n), part of this result) stays as set above; the score and the end
       // cell are the first maximum over every stripe's best.  Every stripe has one (row 64 s + 1 <= m, n >= 1) and
       // it may be negative, so the search starts at INT32_MIN, not 0: lanes stride over the stripes -- rows increase

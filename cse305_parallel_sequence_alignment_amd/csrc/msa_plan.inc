@@ -48,10 +48,6 @@ bool env_is(const char* name, const char* value) {
   return e && std::strcmp(e, value) == 0;
 }
 
-// Smith-Waterman with a linear gap: one carried value per cell (int32, scores >= 0, packed int16 couples)
-constexpr bool is_linear(int alg) { return alg == MSA_ALG_SWL || alg == MSA_ALG_SWL0 || alg == MSA_ALG_SWLP; }
-// the flow kernels' two-value algorithms (SW affine, the reference's Gotoh in tagged form)
-constexpr bool is_affine_flow(int alg) { return alg == MSA_ALG_SWA || alg == MSA_ALG_REF1; }
 inline int stripes_of(int64_t m, int R = 1) { return (int)((m + 64 * R - 1) / (64 * R)); }
 
 // epochs are process-wide, so granules left in a pooled block by an earlier plan
@@ -120,10 +116,10 @@ struct msa_plan {
   int* d_skip = nullptr;  // 1: every chunk converged (the exact launch exits)
   bool h16 = false;       // band_kernel chunks >= 1 write int16 cells to d_h16 (chunk_add_kernel widens)
   int16_t* d_h16 = nullptr;
-  // MSA_ALG_NWA: the substitution scores S[8 a + b] (row code a, column code b; 1 / 0 unless MSA_NW_SCORED) and
-  // their device table, one 8-byte profile per row code in the launch's space (alloc_buffers)
-  // MSA_ALG_NWA32, MSA_ALG_FIT32 (msa_plan_create_scored32): S[32 a + b], uploaded as it is (1,024 bytes)
-  // MSA_ALG_SWS, MSA_ALG_SWS32 (MSA_SW_SCORED): either layout, MSA_VIRT_SCORE in the virtual code's row and column
+  // algorithms that score from a table: the substitution scores S[8 a + b] (row code a, column code b; 1 / 0 for
+  // MSA_NW_BANDED and MSA_NW_ALIGN) and their device table, one 8-byte profile per row code in the launch's space
+  // (alloc_buffers); 5-bit codes (msa_plan_create_scored32): S[32 a + b], uploaded as it is (1,024 bytes)
+  // MSA_SW_SCORED: either layout, MSA_VIRT_SCORE in the virtual code's row and column
   int8_t sub[1024] = {};
   uint2* d_sub = nullptr;
 
@@ -151,16 +147,12 @@ namespace {
 
 struct Extents { int S = 0, P = 0; };  // most stripes / most 16-step layout blocks of any pair
 
-// the plan wrote the global alignment's direction bytes (msa_plan_traceback_nw's and the batch walk's plans)
-bool nw_bytes(const msa_plan* P) {
-  return (P->d.alg == MSA_NW_ALIGN || P->d.alg == MSA_NW_SCORED) && P->d.cells == MSA_CELLS_DIR;
+// what walks the plan's direction bytes: its algorithm's walker if the plan wrote bytes -- and, for the walk that
+// starts at the fill's end cell, tracked one (an MSA_SW_SCORED plan always does) -- else TB_NONE
+msa_walk walker_of(const msa_plan* P) {
+  const msa_walk w = msa_alg_info_of(P->main.kp.alg).walker;
+  return (P->d.cells != MSA_CELLS_DIR || (w == TB_SW && !P->d.track_end)) ? TB_NONE : w;
 }
-// ... the fit alignment's (the same bytes; the walks start at each pair's end cell (m, end_j))
-bool fit_bytes(const msa_plan* P) { return P->d.alg == MSA_NW_FIT && P->d.cells == MSA_CELLS_DIR; }
-// ... the overlap alignment's (the same bytes again; the walks start at each pair's end cell on the last row or column)
-bool overlap_bytes(const msa_plan* P) { return P->d.alg == MSA_NW_OVERLAP && P->d.cells == MSA_CELLS_DIR; }
-// ... the extension alignment's (the global plan's bytes; the walks start at each pair's end cell, any interior cell)
-bool extend_bytes(const msa_plan* P) { return P->d.alg == MSA_NW_EXTEND && P->d.cells == MSA_CELLS_DIR; }
 // the algorithms that score as MSA_NW_SCORED does (table or match / mismatch) under free ends, on the stripe kernel alone
 bool free_ends(int alg) { return alg == MSA_NW_FIT || alg == MSA_NW_OVERLAP || alg == MSA_NW_EXTEND; }
 
@@ -192,10 +184,8 @@ int choose_algorithm(const msa_plan_desc* desc, bool wide32, int sw_smax, int& k
     case MSA_SW_AFFINE: kalg = MSA_ALG_SWA; break;
     case MSA_SW_SCORED:
       // MSA_SW_AFFINE with f = S[row code][column code] (the plan's table: plan_create): a kernel algorithm of its
-      // own (new stripe_kernel instantiations).  Direction bytes or the score alone, no band; the gap costs' and the
-      // table's sizes are check_ranges'
-      kalg = wide32 ? MSA_ALG_SWS32 : MSA_ALG_SWS;
-      if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->band != -1) return MSA_ERR_UNSUPPORTED;
+      // own (new stripe_kernel instantiations).  The gap costs' and the table's sizes are check_ranges'
+      kalg = MSA_ALG_SWS;
       break;
     case MSA_NW_BANDED: kalg = MSA_ALG_NWA; break;
     case MSA_NW_ALIGN:
@@ -207,40 +197,15 @@ int choose_algorithm(const msa_plan_desc* desc, bool wide32, int sw_smax, int& k
         return MSA_ERR_UNSUPPORTED;
       break;
     case MSA_NW_SCORED:
-      // MSA_NW_ALIGN with f = S[row code][column code] (the plan's table: plan_create), direction bytes or the
-      // score alone; the table's and the gaps' sizes are check_ranges'
-      kalg = wide32 ? MSA_ALG_NWA32 : MSA_ALG_NWA;
-      if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->gap_extend < 0 ||
-          desc->gap_open < desc->gap_extend)
-        return MSA_ERR_UNSUPPORTED;
+      // MSA_NW_ALIGN with f = S[row code][column code] (the plan's table: plan_create); the table's and the gaps'
+      // sizes are check_ranges'
+      kalg = MSA_ALG_NWA;
       break;
-    case MSA_NW_FIT:
-      // MSA_NW_SCORED's cell under a zero top border, with the first maximum of row m as the result: a kernel
-      // algorithm of its own (new stripe_kernel instantiations).  No band (|i - j| <= band means nothing when the
-      // reference's ends are free), direction bytes or the score alone
-      kalg = wide32 ? MSA_ALG_FIT32 : MSA_ALG_FIT;
-      if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->gap_extend < 0 ||
-          desc->gap_open < desc->gap_extend || desc->band != -1)
-        return MSA_ERR_UNSUPPORTED;
-      break;
-    case MSA_NW_OVERLAP:
-      // MSA_NW_FIT's cell and rules under zero borders on the top AND the left, with the better of row m's and
-      // column n's first maxima as the result: kernel algorithms of their own again.  No band, direction bytes or
-      // the score alone; which ends are free is not selectable
-      kalg = wide32 ? MSA_ALG_OVL32 : MSA_ALG_OVL;
-      if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->gap_extend < 0 ||
-          desc->gap_open < desc->gap_extend || desc->band != -1)
-        return MSA_ERR_UNSUPPORTED;
-      break;
-    case MSA_NW_EXTEND:
-      // an unbanded MSA_NW_SCORED plan's cell, borders and bytes with the first maximum over all interior cells as the
-      // result (the best pair of prefixes; nothing positive: the empty extension): kernel algorithms of their own.  No
-      // band (the global rule |m - n| <= band does not fit a free end), direction bytes or the score alone
-      kalg = wide32 ? MSA_ALG_EXT32 : MSA_ALG_EXT;
-      if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || desc->gap_extend < 0 ||
-          desc->gap_open < desc->gap_extend || desc->band != -1)
-        return MSA_ERR_UNSUPPORTED;
-      break;
+    // the free-end kinds: kernel algorithms of their own (msa_alg.h), none with a band -- |i - j| <= band means nothing
+    // when an end is free; which ends are free is not selectable
+    case MSA_NW_FIT: kalg = MSA_ALG_FIT; break;
+    case MSA_NW_OVERLAP: kalg = MSA_ALG_OVL; break;
+    case MSA_NW_EXTEND: kalg = MSA_ALG_EXT; break;
     case MSA_REF_GOTOH: {
       // start type -1 (main_alignment_function's single subproblem) with direction bytes or no
       // cells: the tagged-max form (every interior value is finite; values carried x4)
@@ -255,14 +220,24 @@ int choose_algorithm(const msa_plan_desc* desc, bool wide32, int sw_smax, int& k
     case MSA_PARTIAL: kalg = MSA_ALG_PART; break;
     default: return MSA_ERR_ARG;
   }
-  tp = (kalg == MSA_ALG_SWL || kalg == MSA_ALG_SWL0 || kalg == MSA_ALG_SWA) ? (desc->track_end ? 1 : 0) : 0;
-  if (swsc(kalg)) tp = 1;  // (an MSA_SW_SCORED plan always tracks its end cell)
+  if (wide32 && (kalg = msa_alg_info_of(kalg).twin32) == MSA_ALG_NONE) return MSA_ERR_UNSUPPORTED;
+  const msa_alg_info t = msa_alg_info_of(kalg);
+  if (desc->alg == MSA_SW_SCORED || desc->alg == MSA_NW_SCORED || free_ends(desc->alg)) {
+    // the kinds that score from a table: direction bytes or the score alone, a band only where the algorithm accepts
+    // one, and under the Gotoh cell gaps with g, h >= 0
+    if ((out_mode != MSA_OUT_DIR && out_mode != MSA_OUT_NONE) || (!t.band && desc->band != -1) ||
+        (t.cell == CELL_GOTOH && (desc->gap_extend < 0 || desc->gap_open < desc->gap_extend)))
+      return MSA_ERR_UNSUPPORTED;
+  }
+  // the best cell under the zero floor: its position on request (packed couples: score only; an MSA_SW_SCORED plan
+  // always tracks its end cell)
+  tp = (t.result == RES_BEST && !t.packed() && (desc->track_end || t.table)) ? 1 : 0;
   if (tp) {
     // the first-maximum position packs with the value into one int (TRACKPOS 2) when every local score is below 2^16
     // and a stripe has < 2^15 steps.  A local score gains at most max(0, match, mismatch) per diagonal step (gaps
     // only subtract), and a path has at most min(m, n) diagonal steps.  (MSA_SW_SCORED: the table's largest entry
     // over real codes in their place.)
-    const int64_t smax = swsc(kalg) ? sw_smax : std::max({0, desc->match, desc->mismatch});
+    const int64_t smax = t.table ? sw_smax : std::max({0, desc->match, desc->mismatch});
     bool pack = true;
     for (int64_t p = 0; p < desc->n_pairs && pack; ++p)
       pack = smax * std::min(desc->m[p], desc->n[p]) < 65536 && desc->n[p] + 512 < 32768;
@@ -270,7 +245,7 @@ int choose_algorithm(const msa_plan_desc* desc, bool wide32, int sw_smax, int& k
   }
   // (an MSA_NW_EXTEND plan always tracks its end cell, by compare-select: its values may be negative, which the
   // packed key cannot hold)
-  if (extk(kalg)) tp = 1;
+  if (t.result == RES_BEST_ANY) tp = 1;
   return MSA_OK;
 }
 
@@ -283,10 +258,10 @@ msa_kparams base_kparams(const msa_plan_desc* desc, int kalg) {
   kp.mismatch = desc->mismatch;
   kp.gap_open = desc->gap_open;
   kp.gap_ext = desc->gap_extend;
-  if (is_linear(kalg)) kp.gap_open = kp.gap_ext = desc->gap_extend;
+  if (msa_alg_info_of(kalg).linear()) kp.gap_open = kp.gap_ext = desc->gap_extend;
   kp.h = desc->gap_open - desc->gap_extend;
   kp.start_type = desc->start_type;
-  kp.band = nwg(kalg) ? desc->band : -1;
+  kp.band = msa_alg_info_of(kalg).band ? desc->band : -1;
   kp.single = desc->single ? 1 : 0;
   kp.n_pairs = (int)desc->n_pairs;
   return kp;
@@ -303,6 +278,7 @@ int sub_abs_max(const int8_t* sub, int count) {
 // 32-code kernels, 1,024
 // sw_smax: as for choose_algorithm
 int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t* scored, int sw_smax) {
+  const msa_alg_info t = msa_alg_info_of(kp.alg);
   for (int64_t p = 0; p < desc->n_pairs; ++p) {
     const int64_t m = desc->m[p], n = desc->n[p];
     if (m <= 0 || n <= 0 || m > (1 << 26) || n > (1 << 26)) return MSA_ERR_ARG;
@@ -339,10 +315,10 @@ int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t*
       // steps and -inf, and the tracked maximum is a copy of a cell: the same inequality holds.
       // The 32-code kernels (MSA_ALG_NWA32, MSA_ALG_FIT32, MSA_ALG_OVL32, MSA_ALG_EXT32: stripe_kernel, unshifted, raw S) differ in where a step's
       // S comes from, not in what a step is: the same inequality with s over the 1,024 scores.
-      const int64_t s = sub_abs_max(scored, wide(kp.alg) ? 1024 : 64), g = kp.gap_ext, h = kp.h, G = kp.gap_open;
+      const int64_t s = sub_abs_max(scored, t.wide ? 1024 : 64), g = kp.gap_ext, h = kp.h, G = kp.gap_open;
       if ((s + 2 * G + 2 * g) * (m + n + 256) + h >= (int64_t(1) << 28)) return MSA_ERR_UNSUPPORTED;
     }
-    if (is_linear(kp.alg)) {
+    if (t.linear()) {
       // shifted recurrence G = H + g*(i+j): G must stay far from the -2^30 sentinel
       // and from int32 overflow; the profile byte holds score + 2g
       const int64_t g = kp.gap_open;
@@ -351,14 +327,14 @@ int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t*
       if (g < 0 || top >= (int64_t(1) << 29) || sm > 127 || sm < -128 || sx > 127 || sx < -128)
         return MSA_ERR_UNSUPPORTED;
     }
-    if (kp.alg == MSA_ALG_SWA) {
+    if (t.cell == CELL_SWAFF && !t.table) {
       // int8 profile bytes; H stays far from the -2^30 sentinel and from int32 overflow
       const int64_t top = (int64_t)std::max({0, kp.match, kp.mismatch}) * std::min(m, n);
       if (kp.match < -128 || kp.match > 127 || kp.mismatch < -128 || kp.mismatch > 127 || kp.gap_open < 0 ||
           kp.gap_ext < 0 || top >= (int64_t(1) << 29))
         return MSA_ERR_UNSUPPORTED;
     }
-    if (swsc(kp.alg)) {
+    if (t.cell == CELL_SWAFF && t.table) {
       // MSA_SW_SCORED: MSA_ALG_SWA's bound with smax = max(0, the largest S over real codes) for max(0, match,
       // mismatch).  One inequality on the top suffices, unlike the global plans' two-sided K above, because the zero
       // floor stops every drift downwards: H >= 0 in every cell, virtual ones included, and E (F) is a max that
@@ -379,6 +355,7 @@ int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t*
 // ---- step 3: the kernel family, from the description alone ------------------------------------------
 // LDS of a flow workgroup without its pass-2 area: flags, link rings and the code copies -- whole rows
 // when they fit (*whole: kp.code_whole, no ring bookkeeping), else fixed-size rings, so any n fits
+// aff: the flow kernels' two-value algorithms (nc == 2: SW affine, the reference's Gotoh in tagged form)
 size_t flow_lds_bytes(const msa_plan_desc* desc, bool aff, bool* whole) {
   const size_t lds0 = (size_t)(FL_FLAGS + (FL_W + 1) * 256 * (aff ? 2 : 1)) * 4;
   const size_t all = lds0 + (size_t)(aff ? 4 : FL_NCOPY) * (fl_code_bytes((int)desc->n[0]) + 16);
@@ -410,12 +387,13 @@ int band_chunk() {
 // smax: the largest score of an MSA_NW_SCORED plan's table (unused by every other plan)
 PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp, int smax) {
   const int out_mode = desc->cells;
+  const msa_alg_info t = msa_alg_info_of(kalg);
   // 5-bit codes: stripe_kernel alone has the 32-code lookup -- a single pair (any band: the exact masked launch), a batch
-  if (wide(kalg)) return PM_STRIPE;
+  if (t.wide) return PM_STRIPE;
   // MSA_SW_SCORED: stripe_kernel alone scores the SW-affine cell from a table (the flow kernels build their profile
   // from match / mismatch, and the split launch is not instantiated for it) -- one pair or a batch
-  if (swsc(kalg)) return PM_STRIPE;
-  const int band = (kalg == MSA_ALG_NWA) ? desc->band : -1;
+  if (t.cell == CELL_SWAFF && t.table) return PM_STRIPE;
+  const int band = t.band ? desc->band : -1;
   if (desc->single) {
     // flow kernels: one SW-linear pair (8 byte-shifted LDS code rings), or one SW-affine / reference-Gotoh (start
     // type -1, tagged) pair with direction bytes (two values per link column, 4 code rings); the column codes stream
@@ -437,10 +415,8 @@ PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp, int smax) {
     const bool lin_ok = kalg == MSA_ALG_SWL0 ||
                         (kalg == MSA_ALG_SWL && std::min(desc->match, desc->mismatch) + desc->gap_extend >= -128);
     bool whole;
-    if (((kalg == MSA_ALG_SWL || kalg == MSA_ALG_SWL0)
-             ? (lin_ok && (out_mode == MSA_OUT_H || (out_mode == MSA_OUT_NONE && !tp)))
-             : (aff_ok || got_ok)) &&
-        flow_lds_bytes(desc, is_affine_flow(kalg), &whole) <= device_lds_max())
+    if ((lin_ok ? (out_mode == MSA_OUT_H || (out_mode == MSA_OUT_NONE && !tp)) : (aff_ok || got_ok)) &&
+        flow_lds_bytes(desc, t.nc == 2, &whole) <= device_lds_max())
       return PM_FLOW;
     // A banded pair has only ~(2*band+64)/(64*lag) stripes in flight at once: band_kernel's chains of
     // 4-stripe items, as long as its code rows fit LDS; chunked from 4 chunks up, when cells are written
@@ -494,7 +470,7 @@ void set_layout_mode(msa_plan& P, const msa_plan_desc* desc) {
     return;
   }
   P.KS = 16;
-  P.flow2 = desc->cells == MSA_OUT_H || is_affine_flow(kalg);
+  P.flow2 = desc->cells == MSA_OUT_H || P.nc == 2;
   // SW two-pass plans reduce their pair result inside the launch when the cell index fits 32 bits
   // (MSA_FUSED_REDUCE=0: the reduce_blocks_kernel launch, for A/B; read per plan)
   const char* fr = std::getenv("MSA_FUSED_REDUCE");
@@ -582,7 +558,7 @@ int row_words(const Extents& ex) { return ((ex.P * MSA_K + MSA_ROWOFF + 32) + 15
 // 32 x 32 table
 size_t stripe_lds_bytes(const msa_kparams& kp, int W, int nc) {
   return 4 * (16 + (size_t)kp.sched_cap * 8 + (size_t)(2 * W + 1) * nc * MSA_RING + (size_t)nc * kp.lds_row_words +
-              (kp.single == 1 ? (size_t)4 * (MSA_CRING / 4 + 16) : 0) + (wide(kp.alg) ? 256 : 0));
+              (kp.single == 1 ? (size_t)4 * (MSA_CRING / 4 + 16) : 0) + (msa_alg_info_of(kp.alg).wide ? 256 : 0));
 }
 
 // PM_STRIPE, PM_SPLIT: stripe_kernel over a batch's pairs (one workgroup walks a pair's whole stripe chain,
@@ -676,7 +652,7 @@ int shape_flow(msa_plan& P, const msa_plan_desc* desc, int tp) {
   msa_kparams& kp = l.kp;
   const bool nneg = desc->match >= 0 && desc->mismatch >= 0;
   bool whole;
-  const size_t flow_lds = flow_lds_bytes(desc, is_affine_flow(kp.alg), &whole);
+  const size_t flow_lds = flow_lds_bytes(desc, P.nc == 2, &whole);
   l.fn = pick_flow(kp.alg, kp.out == MSA_OUT_NONE, P.flow2, tp, P.R, nneg);
   if (!l.fn) return MSA_ERR_UNSUPPORTED;
   l.threads = (FL_W + 2) * 64;
@@ -798,13 +774,13 @@ int alloc_buffers(msa_plan& P) {
   // (the walks of a fit, overlap or extension plan start at the run's end cell: until a run has written one it is
   // (-1, -1), outside the matrix, which both walkers answer with MSA_ERR_ARG whatever the pooled block held before)
   if (free_ends(P.d.alg)) HIPCHK(hipMemset(P.d_res, 0xff, sizeof(PairResult) * np));
-  if (wide(P.main.kp.alg)) {
+  const msa_alg_info t = msa_alg_info_of(P.main.kp.alg);
+  if (t.wide) {
     // the 32 x 32 table as it is: stripe_kernel's bytes are the raw S (each workgroup copies it to LDS)
     if (!P.alloc(&P.d_sub, sizeof(P.sub))) return MSA_ERR_HIP;
     HIPCHK(hipMemcpy(P.d_sub, P.sub, sizeof(P.sub), hipMemcpyHostToDevice));
-  } else if (P.main.kp.alg == MSA_ALG_NWA || P.main.kp.alg == MSA_ALG_FIT || P.main.kp.alg == MSA_ALG_OVL ||
-             P.main.kp.alg == MSA_ALG_EXT || P.main.kp.alg == MSA_ALG_SWS) {
-    // (MSA_ALG_SWS: stripe_kernel, so the raw S -- with plan_create's MSA_VIRT_SCORE in column 7)
+  } else if (t.table) {
+    // (Smith-Waterman: stripe_kernel, so the raw S -- with plan_create's MSA_VIRT_SCORE in column 7)
     // the substitution table, one 8-byte profile per row code: band_kernel's bytes are S + 2g + h (its values are
     // shifted by g (i + j); wrapped to a byte as the kernel's own arithmetic did for the 1 / 0 plans), stripe_kernel's S
     const bool bandk = P.mode == PM_BAND || P.mode == PM_BAND_CHUNKED;
@@ -835,7 +811,7 @@ int alloc_buffers(msa_plan& P) {
     }
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return key[x] < key[y]; });
     // (affine: the F~ bottom rows follow the Z rows; a snapshot is 4 values per lane)
-    const bool two = is_affine_flow(P.main.kp.alg);
+    const bool two = P.nc == 2;
     const size_t brb = sizeof(unsigned long long) * (size_t)S * P.brw * (two ? 2 : 1);
     const size_t snb = sizeof(unsigned long long) * (size_t)P.nblk * (two ? 128 * (P.R + 1) : 128 * P.R);
     if (!P.alloc_set(&P.d_br, brb) || !P.alloc_set(&P.d_snap, snb)) return MSA_ERR_HIP;
@@ -921,8 +897,8 @@ static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32
   // (direction bytes of the banded recurrence are MSA_NW_ALIGN's: their stripe kernel instantiation exists for it alone)
   if (desc->alg == MSA_NW_BANDED && desc->cells == MSA_CELLS_DIR) return MSA_ERR_UNSUPPORTED;
   P->main.kp = base_kparams(desc, kalg);
-  P->nc = nc_of(kalg);
-  if (nwg(kalg) && P->main.kp.h < 0) return MSA_ERR_UNSUPPORTED;
+  P->nc = msa_alg_info_of(kalg).nc;
+  if (msa_alg_info_of(kalg).band && P->main.kp.h < 0) return MSA_ERR_UNSUPPORTED;
   // the substitution scores of the banded recurrence: MSA_NW_SCORED's table, or its match / mismatch; 1 / 0 for
   // MSA_NW_BANDED and MSA_NW_ALIGN, whatever their description says; MSA_NW_FIT, MSA_NW_OVERLAP and MSA_NW_EXTEND
   // score as MSA_NW_SCORED does

@@ -60,6 +60,8 @@
 
 #include <cstdint>
 
+#include "msa_alg.h"
+
 namespace msa {
 
 // Group loads are LDS-DMA (global_load_lds_dwordx4: each lane's 16 bytes land at
@@ -131,12 +133,7 @@ __device__ __forceinline__ int ref_end_state(const int32_t (&fin)[3], int end_ty
   return 2;
 }
 
-// Walk kinds: Smith-Waterman affine; the reference's Gotoh walk over table numbers (REF
-// fill) or over tags (REF1 fill, tag = 4 - table); the global walk over SW-affine bytes (MSA_NW_ALIGN).
-// TB_FIT (MSA_NW_FIT plans): TB_NW's walk -- words, state machine, stop rule -- started at the run's end cell
-// (m, end_j) from the pair's PairResult instead of (m, n).  MSA_NW_OVERLAP plans walk as TB_FIT too: their end cell
-// is (m, end_j) or (end_i, n), or the empty overlap's (m, 0), where the walk loop's `j > 0` ends the walk at once.
-enum { TB_SW = 0, TB_REF = 1, TB_REF_TAG = 2, TB_NW = 3, TB_FIT = 4 };
+// (the walk kinds, TB_*: enum msa_walk, msa_alg.h)
 
 // The transition word of a cell (see the window comment in traceback_kernel): three 10-bit
 // fields, field s (bits 10s..) = 10 x the next state (30 = stop) | the lane step of leaving

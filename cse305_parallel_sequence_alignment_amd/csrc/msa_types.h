@@ -7,41 +7,27 @@
 extern "C" {
 #endif
 
-// Algorithms the stripe kernel implements.
+// Algorithms the stripe kernel implements.  What an id IS -- cell, borders, result rule, code width, walker -- is its
+// row of the table in msa_alg.h; the comments here only name the plans that use it.
 enum msa_alg {
-  MSA_ALG_SWL = 0,   // Smith-Waterman, linear gap        (config C2, C4)
-  MSA_ALG_SWA = 1,   // Smith-Waterman, affine gap        (config C5)
-  MSA_ALG_NWA = 2,   // reference Gotoh, start type -1, h>=0 (banded, C3): values, or with MSA_OUT_DIR
-                     // (MSA_NW_ALIGN / MSA_NW_SCORED plans only) direction bytes in the SW-affine format;
-                     // substitution scores from the plan's 8 x 8 table (KArgs::sub; 1 / 0 unless MSA_NW_SCORED)
-  MSA_ALG_REF = 3,   // reference Gotoh T1/T2/T3, any start type, exact -inf
-  MSA_ALG_PART = 4,  // partial.cpp Gotoh with int32 wrap semantics
-  MSA_ALG_SWL0 = 5,  // Smith-Waterman, linear gap, every substitution score >= 0 (plan's
-                     // choice for MSA_SW_LINEAR when match, mismatch >= 0: no zero floor)
-  MSA_ALG_REF1 = 6,  // reference Gotoh, start type -1 (main_alignment_function's subproblem),
-                     // direction bytes: the tagged-max form of MSA_ALG_REF (msa_kernels.hip)
-  MSA_ALG_SWLP = 7,  // MSA_ALG_SWL0 for TWO pairs per lane as packed int16 (batch, score only:
-                     // pairs 2c and 2c+1 share rows/columns counts and the column sequence)
-  MSA_ALG_FIT = 8,   // MSA_ALG_NWA's cell (no band) under a zero top border, H(0, j) = 0: all of A against a
-                     // substring of B (MSA_NW_FIT plans).  The lane of row m keeps the first maximum of
-                     // H(m, 1..n): the stripe meta's best / best_i = m / best_j
-  MSA_ALG_NWA32 = 9,   // MSA_ALG_NWA over 5-bit codes: scores from the plan's 32 x 32 table (KArgs::sub, raw int8 S),
-                       // the lane's 32-byte row of it in eight registers (msa_plan_create_scored32, stripe_kernel only)
-  MSA_ALG_FIT32 = 10,  // MSA_ALG_FIT over 5-bit codes, likewise
-  MSA_ALG_SWS = 11,    // MSA_ALG_SWA's cell, borders, best tracking and virtual columns with substitution scores from
-                       // the plan's 8 x 8 table (MSA_SW_SCORED plans, stripe_kernel only): real codes 0..6, column 7
-                       // of every row = MSA_VIRT_SCORE (the host-side table builder fills it in)
-  MSA_ALG_SWS32 = 12,  // MSA_ALG_SWS over 5-bit codes under the 32 x 32 table: real codes 0..30, the virtual code 31
-  MSA_ALG_OVL = 13,    // MSA_ALG_FIT's cell, zero top border and row-m maximum under a zero LEFT border too, H(i, 0) = 0
-                       // (MSA_NW_OVERLAP plans): a suffix of one sequence against a prefix of the other.  Every lane of
-                       // every stripe also keeps H of its row at column n; the stripe's maximum of them (the smaller
-                       // row on a tie) goes to the stripe meta's col_best / col_i
-  MSA_ALG_OVL32 = 14,  // MSA_ALG_OVL over 5-bit codes, as MSA_ALG_FIT32
-  MSA_ALG_EXT = 15,    // the unbanded MSA_ALG_NWA's cell, borders and bytes (MSA_NW_EXTEND plans): the best pair of
-                       // prefixes.  Every lane of every stripe keeps the first maximum of its row's H over columns
-                       // 1..n (it may be negative); the stripe's first maximum in row-major order goes to the stripe
-                       // meta's best / best_i / best_j, and the stripe of row m still writes fin[] (H, E, F at (m, n))
-  MSA_ALG_EXT32 = 16,  // MSA_ALG_EXT over 5-bit codes, as MSA_ALG_NWA32
+  MSA_ALG_SWL = 0,     // Smith-Waterman, linear gap (config C2, C4)
+  MSA_ALG_SWA = 1,     // Smith-Waterman, affine gap (config C5)
+  MSA_ALG_NWA = 2,     // banded Gotoh (C3; MSA_NW_BANDED values, MSA_NW_ALIGN / MSA_NW_SCORED direction bytes)
+  MSA_ALG_REF = 3,     // reference Gotoh T1/T2/T3, any start type
+  MSA_ALG_PART = 4,    // partial.cpp Gotoh
+  MSA_ALG_SWL0 = 5,    // MSA_SW_LINEAR when match, mismatch >= 0
+  MSA_ALG_REF1 = 6,    // reference Gotoh, start type -1 (main_alignment_function's subproblem)
+  MSA_ALG_SWLP = 7,    // MSA_ALG_SWL0 for two pairs per lane (batch, score only: pairs 2c and 2c+1 share rows/columns
+                       // counts and the column sequence)
+  MSA_ALG_FIT = 8,     // MSA_NW_FIT
+  MSA_ALG_NWA32 = 9,   // every X32: X over 5-bit codes (msa_plan_create_scored32)
+  MSA_ALG_FIT32 = 10,
+  MSA_ALG_SWS = 11,    // MSA_SW_SCORED
+  MSA_ALG_SWS32 = 12,
+  MSA_ALG_OVL = 13,    // MSA_NW_OVERLAP
+  MSA_ALG_OVL32 = 14,
+  MSA_ALG_EXT = 15,    // MSA_NW_EXTEND
+  MSA_ALG_EXT32 = 16,
 };
 
 // Per-cell outputs.
@@ -52,8 +38,7 @@ enum msa_out {
   MSA_OUT_TAB = 3,   // three int32 planes T1,T2,T3 per cell (skewed stripe layout)
 };
 
-// One pair of sequences inside a launch.  Codes are uint8 in [0,8) ([0,32): MSA_ALG_NWA32, MSA_ALG_FIT32,
-// MSA_ALG_OVL32, MSA_ALG_EXT32, MSA_ALG_SWS32).
+// One pair of sequences inside a launch.  Codes are uint8 in [0,8) ([0,32): the 5-bit algorithms, msa_alg.h).
 typedef struct msa_pair_desc {
   int64_t a_off;       // offset of row codes (A[0] = row 1) in the A code array
   int64_t b_off;       // offset of column codes (B[0] = column 1) in the B code array
