@@ -29,6 +29,8 @@ SW_SCORED = 8
 NW_OVERLAP = 9
 NW_EXTEND = 10
 CELLS_NONE, CELLS_H, CELLS_DIR, CELLS_TAB = 0, 1, 2, 3
+# msa_profile_align's modes
+PROFILE_LOCAL, PROFILE_GLOBAL, PROFILE_FIT = 0, 1, 2
 
 
 class MsaError(RuntimeError):
@@ -101,6 +103,7 @@ def lib() -> C.CDLL:
     L.msa_plan_create.argtypes = [C.POINTER(PlanDesc), C.POINTER(P)]
     L.msa_plan_create_scored.argtypes = [C.POINTER(PlanDesc), P, C.POINTER(P)]
     L.msa_plan_create_scored32.argtypes = [C.POINTER(PlanDesc), P, C.POINTER(P)]
+    L.msa_plan_create_profile.argtypes = [C.POINTER(PlanDesc), P, i64, C.POINTER(P)]
     L.msa_plan_destroy.argtypes = [P]
     L.msa_plan_destroy.restype = None
     L.msa_plan_cells_size.argtypes = [P, C.POINTER(i64)]
@@ -156,6 +159,9 @@ def lib() -> C.CDLL:
     L.msa_sw_align_batch_scored.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, P, P, P, P, sz, P]
     L.msa_sw_align_scored32.argtypes = L.msa_sw_align_scored.argtypes
     L.msa_sw_align_batch_scored32.argtypes = L.msa_sw_align_batch_scored.argtypes
+    # profile alignment: (mode, prof, m) for A; two cells {i, j} per pair
+    L.msa_profile_align.argtypes = [C.c_int, P, sz, P, sz, P, sz, i32, i32, C.POINTER(i32), P, P, P, sz]
+    L.msa_profile_align_batch.argtypes = [C.c_int, P, sz, P, sz, i64, P, P, P, sz, i32, i32, P, P, P, P, sz, P]
     _lib = L.lib
     return _lib
 
@@ -189,4 +195,5 @@ EXPORTED = [
     "msa_sw_align_scored", "msa_sw_align_batch_scored", "msa_sw_align_scored32", "msa_sw_align_batch_scored32",
     "msa_overlap_align", "msa_overlap_align_batch", "msa_overlap_align32", "msa_overlap_align_batch32",
     "msa_extend_align", "msa_extend_align_batch", "msa_extend_align32", "msa_extend_align_batch32",
+    "msa_plan_create_profile", "msa_profile_align", "msa_profile_align_batch",
 ]

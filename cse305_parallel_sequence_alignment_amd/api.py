@@ -690,3 +690,95 @@ def extend_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=N
                                      _i64p(coff) if traceback else None), name)
     return [_extend_dict(sc[p], end[p], gs[p], traceback,
                          cig.raw[coff[p]:coff[p + 1] - 1].decode() if traceback else None) for p in range(k)]
+
+
+_PROFILE_MODES = {"local": LB.PROFILE_LOCAL, "global": LB.PROFILE_GLOBAL, "fit": LB.PROFILE_FIT}
+
+
+def profile_from_matrix(A, alphabet, matrix) -> np.ndarray:
+    """The ``len(A) x len(alphabet)`` int8 profile whose row i is ``matrix[code(A_i)]``, a symbol's code being its
+    index in ``alphabet``: the profile under which profile_align gives exactly what the matrix-scored call gives for
+    A -- the starting profile of an iterated search.  A symbol of A outside the alphabet, a matrix that is not
+    len(alphabet) x len(alphabet) or not int8-representable: ValueError."""
+    A, alphabet = _buf(A), _buf(alphabet)
+    S = np.asarray(matrix)
+    if S.ndim != 2 or S.shape != (len(alphabet), len(alphabet)) or (S != S.astype(np.int8)).any():
+        raise ValueError("matrix must be len(alphabet) x len(alphabet) scores in [-128, 127]")
+    if len(set(alphabet)) != len(alphabet):
+        raise ValueError("alphabet holds a symbol twice")
+    code = np.full(256, -1, dtype=np.int64)
+    code[np.frombuffer(alphabet, dtype=np.uint8)] = np.arange(len(alphabet))
+    ca = code[np.frombuffer(A, dtype=np.uint8)]
+    if (ca < 0).any():
+        raise ValueError("A holds a symbol outside the alphabet")
+    return np.ascontiguousarray(S.astype(np.int8)[ca].reshape(len(A), len(alphabet)))
+
+
+def _profile_in(profile, alphabet, mode):
+    """(mode number, contiguous int8 profile, alphabet bytes) of a profile call, or its ValueError."""
+    if mode not in _PROFILE_MODES:
+        raise ValueError("mode must be 'local', 'global' or 'fit'")
+    alphabet = _buf(alphabet)
+    P = np.asarray(profile)
+    if P.ndim != 2 or P.dtype == object or (P != P.astype(np.int8)).any():
+        raise ValueError("profile must be a 2-D array of scores in [-128, 127]")
+    if P.shape[1] != len(alphabet):
+        raise ValueError("profile must have len(alphabet) columns")
+    return _PROFILE_MODES[mode], np.ascontiguousarray(P, dtype=np.int8), alphabet
+
+
+def _profile_dict(score, beg, end, traceback, cigar):
+    r = dict(score=int(score), beg=(int(beg[0]), int(beg[1])) if traceback else None, end=(int(end[0]), int(end[1])))
+    if traceback:
+        r["cigar"] = cigar
+    return r
+
+
+def profile_align(profile, seq, alphabet, mode="local", gap_open=3, gap_extend=1, traceback=True):
+    """A position-specific score profile (a PSSM) against a sequence (build extension, msa_profile_align) ->
+    dict(score, beg, end[, cigar]).
+
+    ``profile``: rows x len(alphabet) scores in [-128, 127], ``profile[r][c]`` = profile position r against
+    ``alphabet[c]``; ``alphabet``: the distinct symbols of ``seq``, at most 31 for ``mode="local"`` and 32 otherwise.
+    ``mode``: "local" (sw_align's recurrence and cells: ``beg`` the start cell, ``end`` the end cell), "global"
+    (nw_align's, unbanded: ``(0, 0)`` and ``(rows, len(seq))``) or "fit" (fit_align's, the whole profile in a substring
+    of ``seq``: ``(0, beg_j)`` and ``(rows, end_j)``).  The CIGAR (start -> end) has I consuming a profile row and D a
+    symbol of ``seq``.  ``traceback=False`` gives the score and ``end`` only (``beg`` is None).  A gap of L costs
+    (gap_open - gap_extend) + gap_extend * L.  Building the profile from a multiple alignment is the caller's job;
+    profile_from_matrix gives the one a single sequence has under a substitution matrix."""
+    mo, P, alphabet = _profile_in(profile, alphabet, mode)
+    B = _buf(seq)
+    sc = C.c_int32()
+    beg, end = np.zeros(2, dtype=np.int64), np.zeros(2, dtype=np.int64)
+    cap = 4 * (P.shape[0] + len(B)) + 16
+    cig = C.create_string_buffer(cap) if traceback else None
+    LB.check(LB.lib().msa_profile_align(mo, P.ctypes.data_as(C.c_void_p), P.shape[0], B, len(B), alphabet,
+                                        len(alphabet), gap_open, gap_extend, C.byref(sc),
+                                        _i64p(beg) if traceback else None, _i64p(end), cig, cap if traceback else 0),
+             "msa_profile_align")
+    return _profile_dict(sc.value, beg, end, traceback, cig.value.decode() if traceback else None)
+
+
+def profile_align_batch(profile, seqs, alphabet, mode="local", gap_open=3, gap_extend=1, traceback=True):
+    """One profile against many sequences (msa_profile_align_batch) -> a list of profile_align()'s dicts: the search
+    case, every pair using all rows of ``profile``, which each plan of the call holds once."""
+    mo, P, alphabet = _profile_in(profile, alphabet, mode)
+    seqs = [_buf(b) for b in seqs]
+    k = len(seqs)
+    if k == 0:
+        return []
+    B = b"".join(seqs)
+    n = np.array([len(b) for b in seqs], dtype=np.int64)
+    b_off = np.concatenate(([0], np.cumsum(n)[:-1])).astype(np.int64)
+    sc = np.zeros(k, dtype=np.int32)
+    beg, end = np.zeros((k, 2), dtype=np.int64), np.zeros((k, 2), dtype=np.int64)
+    coff = np.zeros(k + 1, dtype=np.int64)
+    cap = int(4 * (k * P.shape[0] + n.sum()) + 16 * k) if traceback else 0
+    cig = C.create_string_buffer(cap) if traceback else None
+    LB.check(LB.lib().msa_profile_align_batch(mo, P.ctypes.data_as(C.c_void_p), P.shape[0], B, len(B), k, _i64p(b_off),
+                                              _i64p(n), alphabet, len(alphabet), gap_open, gap_extend,
+                                              sc.ctypes.data_as(C.c_void_p), _i64p(beg) if traceback else None,
+                                              _i64p(end), cig, cap, _i64p(coff) if traceback else None),
+             "msa_profile_align_batch")
+    return [_profile_dict(sc[p], beg[p], end[p], traceback,
+                          cig.raw[coff[p]:coff[p + 1] - 1].decode() if traceback else None) for p in range(k)]

@@ -46,6 +46,8 @@ struct msa_alg_info {
   msa_result result;
   bool wide;          // 5-bit codes (a 32-byte profile per row, score4_wide); else 3-bit
   bool table;         // substitution scores from the plan's table (KArgs::sub); else match / mismatch
+  bool profile;       // ... from the plan's profile instead (KArgs::prof): one 32-byte row of scores per ROW OF THE
+                      // MATRIX, not per row code -- the lane's registers hold what they hold under a 32 x 32 table
   bool band;          // |i - j| <= band is accepted
   msa_walk walker;    // what walks its direction bytes
   int twin32;         // the same row over 5-bit codes, or MSA_ALG_NONE
@@ -64,48 +66,53 @@ struct msa_alg_info {
 constexpr msa_alg_info msa_alg_info_of(int alg) {
   constexpr msa_border RAMP = BORDER_RAMP, FREE = BORDER_FREE;
   switch (alg) {
-    //                          nc cell            top   left  result         wide   table  band   walker      twin32
-    case MSA_ALG_SWL:   return {1, CELL_LIN_FLOOR, FREE, FREE, RES_BEST,      false, false, false, TB_NONE,    MSA_ALG_NONE};
-    case MSA_ALG_SWL0:  return {1, CELL_LIN,       FREE, FREE, RES_BEST,      false, false, false, TB_NONE,    MSA_ALG_NONE};
-    case MSA_ALG_SWLP:  return {1, CELL_LIN_PK16,  FREE, FREE, RES_BEST,      false, false, false, TB_NONE,    MSA_ALG_NONE};
-    case MSA_ALG_SWA:   return {2, CELL_SWAFF,     FREE, FREE, RES_BEST,      false, false, false, TB_SW,      MSA_ALG_NONE};
-    case MSA_ALG_SWS:   return {2, CELL_SWAFF,     FREE, FREE, RES_BEST,      false, true,  false, TB_SW,      MSA_ALG_SWS32};
-    case MSA_ALG_SWS32: return {2, CELL_SWAFF,     FREE, FREE, RES_BEST,      true,  true,  false, TB_SW,      MSA_ALG_NONE};
-    case MSA_ALG_NWA:   return {2, CELL_GOTOH,     RAMP, RAMP, RES_FINAL,     false, true,  true,  TB_NW,      MSA_ALG_NWA32};
-    case MSA_ALG_NWA32: return {2, CELL_GOTOH,     RAMP, RAMP, RES_FINAL,     true,  true,  true,  TB_NW,      MSA_ALG_NONE};
-    case MSA_ALG_FIT:   return {2, CELL_GOTOH,     FREE, RAMP, RES_ROW_M,     false, true,  false, TB_FIT,     MSA_ALG_FIT32};
-    case MSA_ALG_FIT32: return {2, CELL_GOTOH,     FREE, RAMP, RES_ROW_M,     true,  true,  false, TB_FIT,     MSA_ALG_NONE};
-    case MSA_ALG_OVL:   return {2, CELL_GOTOH,     FREE, FREE, RES_ROW_M_COL, false, true,  false, TB_FIT,     MSA_ALG_OVL32};
-    case MSA_ALG_OVL32: return {2, CELL_GOTOH,     FREE, FREE, RES_ROW_M_COL, true,  true,  false, TB_FIT,     MSA_ALG_NONE};
-    case MSA_ALG_EXT:   return {2, CELL_GOTOH,     RAMP, RAMP, RES_BEST_ANY,  false, true,  false, TB_FIT,     MSA_ALG_EXT32};
-    case MSA_ALG_EXT32: return {2, CELL_GOTOH,     RAMP, RAMP, RES_BEST_ANY,  true,  true,  false, TB_FIT,     MSA_ALG_NONE};
-    case MSA_ALG_REF:   return {3, CELL_REF3,      RAMP, RAMP, RES_FINAL,     false, false, false, TB_REF,     MSA_ALG_NONE};
-    case MSA_ALG_REF1:  return {2, CELL_REF_TAG,   RAMP, RAMP, RES_FINAL,     false, false, false, TB_REF_TAG, MSA_ALG_NONE};
-    case MSA_ALG_PART:  return {3, CELL_PART,      RAMP, RAMP, RES_FINAL,     false, false, false, TB_NONE,    MSA_ALG_NONE};
+    //                          nc cell            top   left  result         wide   table  prof   band   walker      twin32
+    case MSA_ALG_SWL:   return {1, CELL_LIN_FLOOR, FREE, FREE, RES_BEST,      false, false, false, false, TB_NONE,    MSA_ALG_NONE};
+    case MSA_ALG_SWL0:  return {1, CELL_LIN,       FREE, FREE, RES_BEST,      false, false, false, false, TB_NONE,    MSA_ALG_NONE};
+    case MSA_ALG_SWLP:  return {1, CELL_LIN_PK16,  FREE, FREE, RES_BEST,      false, false, false, false, TB_NONE,    MSA_ALG_NONE};
+    case MSA_ALG_SWA:   return {2, CELL_SWAFF,     FREE, FREE, RES_BEST,      false, false, false, false, TB_SW,      MSA_ALG_NONE};
+    case MSA_ALG_SWS:   return {2, CELL_SWAFF,     FREE, FREE, RES_BEST,      false, true,  false, false, TB_SW,      MSA_ALG_SWS32};
+    case MSA_ALG_SWS32: return {2, CELL_SWAFF,     FREE, FREE, RES_BEST,      true,  true,  false, false, TB_SW,      MSA_ALG_NONE};
+    case MSA_ALG_NWA:   return {2, CELL_GOTOH,     RAMP, RAMP, RES_FINAL,     false, true,  false, true,  TB_NW,      MSA_ALG_NWA32};
+    case MSA_ALG_NWA32: return {2, CELL_GOTOH,     RAMP, RAMP, RES_FINAL,     true,  true,  false, true,  TB_NW,      MSA_ALG_NONE};
+    case MSA_ALG_FIT:   return {2, CELL_GOTOH,     FREE, RAMP, RES_ROW_M,     false, true,  false, false, TB_FIT,     MSA_ALG_FIT32};
+    case MSA_ALG_FIT32: return {2, CELL_GOTOH,     FREE, RAMP, RES_ROW_M,     true,  true,  false, false, TB_FIT,     MSA_ALG_NONE};
+    case MSA_ALG_OVL:   return {2, CELL_GOTOH,     FREE, FREE, RES_ROW_M_COL, false, true,  false, false, TB_FIT,     MSA_ALG_OVL32};
+    case MSA_ALG_OVL32: return {2, CELL_GOTOH,     FREE, FREE, RES_ROW_M_COL, true,  true,  false, false, TB_FIT,     MSA_ALG_NONE};
+    case MSA_ALG_EXT:   return {2, CELL_GOTOH,     RAMP, RAMP, RES_BEST_ANY,  false, true,  false, false, TB_FIT,     MSA_ALG_EXT32};
+    case MSA_ALG_EXT32: return {2, CELL_GOTOH,     RAMP, RAMP, RES_BEST_ANY,  true,  true,  false, false, TB_FIT,     MSA_ALG_NONE};
+    case MSA_ALG_REF:   return {3, CELL_REF3,      RAMP, RAMP, RES_FINAL,     false, false, false, false, TB_REF,     MSA_ALG_NONE};
+    case MSA_ALG_REF1:  return {2, CELL_REF_TAG,   RAMP, RAMP, RES_FINAL,     false, false, false, false, TB_REF_TAG, MSA_ALG_NONE};
+    case MSA_ALG_PART:  return {3, CELL_PART,      RAMP, RAMP, RES_FINAL,     false, false, false, false, TB_NONE,    MSA_ALG_NONE};
+    case MSA_ALG_SWP:   return {2, CELL_SWAFF,     FREE, FREE, RES_BEST,      true,  true,  true,  false, TB_SW,      MSA_ALG_NONE};
+    case MSA_ALG_NWP:   return {2, CELL_GOTOH,     RAMP, RAMP, RES_FINAL,     true,  true,  true,  false, TB_NW,      MSA_ALG_NONE};
+    case MSA_ALG_FITP:  return {2, CELL_GOTOH,     FREE, RAMP, RES_ROW_M,     true,  true,  true,  false, TB_FIT,     MSA_ALG_NONE};
   }
-  return {0, CELL_PART, RAMP, RAMP, RES_FINAL, false, false, false, TB_NONE, MSA_ALG_NONE};  // no such id
+  return {0, CELL_PART, RAMP, RAMP, RES_FINAL, false, false, false, false, TB_NONE, MSA_ALG_NONE};  // no such id
 }
 // clang-format on
 
 // ---- the table checks itself -------------------------------------------------------------------------------------
 namespace msa_alg_check {
-enum { NC = 1, CELL = 2, TOP = 4, LEFT = 8, RESULT = 16, WIDE = 32, TABLE = 64, BAND = 128, WALKER = 256, TWIN = 512 };
+enum { NC = 1, CELL = 2, TOP = 4, LEFT = 8, RESULT = 16, WIDE = 32, TABLE = 64, BAND = 128, WALKER = 256, TWIN = 512,
+       PROFILE = 1024 };
 // the fields in which two ids differ
 constexpr unsigned diff(int x, int y) {
   const msa_alg_info a = msa_alg_info_of(x), b = msa_alg_info_of(y);
   return (a.nc != b.nc ? NC : 0) | (a.cell != b.cell ? CELL : 0) | (a.top != b.top ? TOP : 0) |
          (a.left != b.left ? LEFT : 0) | (a.result != b.result ? RESULT : 0) | (a.wide != b.wide ? WIDE : 0) |
          (a.table != b.table ? TABLE : 0) | (a.band != b.band ? BAND : 0) | (a.walker != b.walker ? WALKER : 0) |
-         (a.twin32 != b.twin32 ? TWIN : 0);
+         (a.twin32 != b.twin32 ? TWIN : 0) | (a.profile != b.profile ? PROFILE : 0);
 }
 constexpr int nc_of_cell(msa_cell c) {
   return (c == CELL_REF3 || c == CELL_PART) ? 3 : (c == CELL_SWAFF || c == CELL_GOTOH || c == CELL_REF_TAG) ? 2 : 1;
 }
-// every id: nc agrees with the cell; its twin, if any, is itself but for the code width (and has no twin of its own)
+// every id: nc agrees with the cell; its twin, if any, is itself but for the code width (and has no twin of its own);
+// a profile row is a row of a plan-owned table over 5-bit codes
 constexpr bool rows_ok() {
-  for (int alg = 0; alg <= MSA_ALG_EXT32; ++alg) {
+  for (int alg = 0; alg <= MSA_ALG_FITP; ++alg) {
     const msa_alg_info t = msa_alg_info_of(alg);
-    if (t.nc != nc_of_cell(t.cell) || (t.wide && !t.table)) return false;
+    if (t.nc != nc_of_cell(t.cell) || (t.wide && !t.table) || (t.profile && !t.wide)) return false;
     if (t.twin32 != MSA_ALG_NONE && (t.wide || diff(alg, t.twin32) != (WIDE | TWIN))) return false;
   }
   return true;
@@ -121,4 +128,9 @@ static_assert(diff(MSA_ALG_OVL, MSA_ALG_FIT) == (LEFT | RESULT | TWIN), "OVL = F
 static_assert(diff(MSA_ALG_EXT, MSA_ALG_NWA) == (RESULT | BAND | WALKER | TWIN), "EXT = unbanded NWA but for the result");
 // scored local is SW affine under the plan's table
 static_assert(diff(MSA_ALG_SWS, MSA_ALG_SWA) == (TABLE | TWIN), "SWS = SWA under a table");
+// a profile id is a 32-code id whose 32 scores belong to the row of the matrix (the global one takes no band: its
+// launch is the stripe kernel's, and nothing of a band's geometry is position-specific)
+static_assert(diff(MSA_ALG_SWP, MSA_ALG_SWS32) == PROFILE, "SWP = SWS32 under a profile");
+static_assert(diff(MSA_ALG_NWP, MSA_ALG_NWA32) == (PROFILE | BAND), "NWP = unbanded NWA32 under a profile");
+static_assert(diff(MSA_ALG_FITP, MSA_ALG_FIT32) == PROFILE, "FITP = FIT32 under a profile");
 }  // namespace msa_alg_check

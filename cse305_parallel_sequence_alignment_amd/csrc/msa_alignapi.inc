@@ -7,6 +7,7 @@
 //     msa_fit_align, msa_fit_align_batch, *32           all of A in a substring of B
 //     msa_overlap_align, msa_overlap_align_batch, *32   a suffix of one sequence against a prefix of the other
 //     msa_extend_align, msa_extend_align_batch, *32     the best pair of prefixes (anchored start, free end)
+//     msa_profile_align, msa_profile_align_batch        a position-specific profile: local, global, fit
 // The host encodes the inputs, runs plans (the flow / band kernels behind msa_plan_run) and the device walks
 // (traceback_kernel, msa_plan_traceback_batch), and turns a walk's O(m + n) ops into a CIGAR.
 namespace {
@@ -54,6 +55,8 @@ struct AlignSpec {
   bool wide = false;        // more than 8 symbols: 5-bit codes, tab is 32 x 32
   bool stop_is_beg = false; // the walk's stop cell (i, j) is the alignment's 0-based start, reported through
                             // AlignOut::beg where a walk ran (-1, -1 where none did); never a reason to walk
+  const int8_t* prof = nullptr;  // the rows are positions of this profile, a_len rows of 32 scores, not symbols of A
+                                 // (msa_plan_create_profile; A is unused, tab too)
 };
 
 // Smith-Waterman: code 7 is the kernels' out-of-matrix sentinel, so 7 codes
@@ -118,6 +121,28 @@ AlignSpec spec_extend(const char* alphabet, size_t n_sym, const int8_t* sub, siz
   AlignSpec s = spec_fit(alphabet, n_sym, sub, max_sym);
   s.alg_walk = s.alg_score = MSA_NW_EXTEND;
   s.border = BORDER_GLOBAL;
+  return s;
+}
+
+// A profile's positions against the caller's alphabet -- a symbol's code is its index --, local (the highest code is
+// the sentinel's: 31 symbols), global or fit (32).  prof32: the caller's m x n_sym scores padded to 32 columns (the
+// entry owns it).  status MSA_ERR_ARG for a NULL alphabet, n_sym out of range or a duplicate symbol
+AlignSpec spec_profile(int mode, const int8_t* prof32, const char* alphabet, size_t n_sym) {
+  AlignSpec s = mode == MSA_PROFILE_LOCAL ? spec_sw(0, 0, "") : spec_nw("");
+  s.alg_walk = s.alg_score = mode == MSA_PROFILE_LOCAL ? MSA_SW_SCORED
+                             : mode == MSA_PROFILE_FIT ? MSA_NW_FIT
+                                                       : MSA_NW_SCORED;
+  const size_t max_sym = mode == MSA_PROFILE_LOCAL ? 31 : 32;
+  s.match = s.mismatch = 0;
+  s.banded = false;
+  if (mode == MSA_PROFILE_FIT) s.border = BORDER_FIT;
+  s.wide = true;
+  s.prof = prof32;
+  s.symbols = SymbolMap((int)max_sym);
+  if (!alphabet || !prof32 || n_sym < 1 || n_sym > max_sym) s.status = MSA_ERR_ARG;
+  for (size_t a = 0; s.status == MSA_OK && a < n_sym; ++a)
+    if (!s.symbols.add(alphabet[a])) s.status = MSA_ERR_ARG;
+  s.symbols.fix();
   return s;
 }
 
@@ -189,9 +214,11 @@ int align_range(const AlignSpec& spec, int single, const GapBand& gb, bool want_
   int rc;
   DeviceCall dc(bytes);
   if ((rc = dc.status()) != MSA_OK) return rc;
-  void *dA = dc.alloc((size_t)(a_hi - a_lo)), *dB = dc.alloc((size_t)(b_hi - b_lo));
-  if (!dA || !dB) return MSA_ERR_NOMEM;
-  if ((rc = dc.upload(dA, ca + a_lo, (size_t)(a_hi - a_lo))) || (rc = dc.upload(dB, cb + b_lo, (size_t)(b_hi - b_lo))))
+  // (a profile call has no row codes: the plan takes its rows [a_lo, a_hi) of the profile and owns their device copy)
+  void *dA = spec.prof ? nullptr : dc.alloc((size_t)(a_hi - a_lo)), *dB = dc.alloc((size_t)(b_hi - b_lo));
+  if ((!dA && !spec.prof) || !dB) return MSA_ERR_NOMEM;
+  if ((dA && (rc = dc.upload(dA, ca + a_lo, (size_t)(a_hi - a_lo)))) ||
+      (rc = dc.upload(dB, cb + b_lo, (size_t)(b_hi - b_lo))))
     return rc;
   msa_plan_desc d;
   std::memset(&d, 0, sizeof(d));
@@ -211,7 +238,9 @@ int align_range(const AlignSpec& spec, int single, const GapBand& gb, bool want_
   d.a_off = ao.data();
   d.b_off = bo.data();
   msa_plan* P = nullptr;
-  if ((rc = dc.create_plan(d, spec.scored ? spec.tab : nullptr, &P, spec.wide)) != MSA_OK) return rc;
+  rc = spec.prof ? dc.create_profile_plan(d, spec.prof + 32 * a_lo, a_hi - a_lo, &P)
+                 : dc.create_plan(d, spec.scored ? spec.tab : nullptr, &P, spec.wide);
+  if (rc != MSA_OK) return rc;
   void *dDir = nullptr, *dOps = nullptr, *dOff = nullptr, *dInfo = nullptr;
   const hipStream_t st = dc.stream();
   if (want_tb) {
@@ -281,8 +310,8 @@ const int64_t kPairLimit = int64_t(1) << 26;  // rows / columns of a pair (msa_s
 int align_pairs(AlignSpec spec, int single, const AlignIn& in, int64_t size_lim, int32_t gap_open,
                 int32_t gap_extend, int64_t band_in, const AlignOut& out) {
   if (spec.status != MSA_OK) return spec.status;
-  if (!in.A || !in.B || !in.a_off || !in.m || !in.b_off || !in.n || in.np < 1 || (out.cigars && !out.cigar_off) ||
-      band_in < -1)
+  if ((!in.A && !spec.prof) || !in.B || !in.a_off || !in.m || !in.b_off || !in.n || in.np < 1 ||
+      (out.cigars && !out.cigar_off) || band_in < -1)
     return MSA_ERR_ARG;
   int64_t span_max = 0;
   for (int64_t p = 0; p < in.np; ++p) {
@@ -302,15 +331,17 @@ int align_pairs(AlignSpec spec, int single, const AlignIn& in, int64_t size_lim,
       if (std::llabs(in.m[p] - in.n[p]) > band_in) return MSA_ERR_ARG;
   // (a band that holds every cell of every pair is no band)
   const GapBand gb{gap_open, gap_extend, (band_in < 0 || band_in >= span_max) ? -1 : (int)band_in};
-  std::vector<uint8_t> ca(in.a_len), cb(in.b_len);
-  int rc = spec.symbols.encode(in.A, in.a_len, ca.data());
+  std::vector<uint8_t> ca(spec.prof ? 0 : in.a_len), cb(in.b_len);
+  int rc = spec.prof ? MSA_OK : spec.symbols.encode(in.A, in.a_len, ca.data());
   if (rc == MSA_OK) rc = spec.symbols.encode(in.B, in.b_len, cb.data());
   if (rc != MSA_OK) return rc;
   if ((rc = ensure_device()) != MSA_OK) return rc;
   const bool want_tb = out.cigars || (spec.walk_for_beg && (out.beg.i || out.beg.j));
+  // (a profile call: every plan of it holds its pairs' rows of the profile, 32 B each)
   auto fp = [&](int64_t p) -> size_t {
-    if (spec.footprint == FOOT_BAND) return footprint_nw(in.m[p], in.n[p], gb.band, want_tb);
-    return want_tb ? footprint_dir(in.m[p], in.n[p]) : footprint_planes(in.m[p], in.n[p], 0, 1);
+    const size_t rows = spec.prof ? 32 * (size_t)in.m[p] : 0;
+    if (spec.footprint == FOOT_BAND) return rows + footprint_nw(in.m[p], in.n[p], gb.band, want_tb);
+    return rows + (want_tb ? footprint_dir(in.m[p], in.n[p]) : footprint_planes(in.m[p], in.n[p], 0, 1));
   };
   int64_t binfo[5];
   admission().info(current_device(), binfo);
@@ -617,6 +648,55 @@ int msa_sw_align_batch_scored32(const char* A, size_t a_len, const char* B, size
                                 size_t cigar_cap, int64_t* cigar_off) {
   return sw_align_batch_scored(A, a_len, B, b_len, n_pairs, a_off, m, b_off, n, alphabet, n_sym, sub, 31, gap_open,
                                gap_extend, score, end_ij, beg_ij, cigars, cigar_cap, cigar_off);
+}
+
+// ---- profile alignment: the rows are the m positions of a position-specific profile (msa_plan_create_profile), every
+// pair all of them against one sequence of B; the three modes are MSA_SW_SCORED, MSA_NW_SCORED and MSA_NW_FIT plans
+// and their entries' walks, with one result shape: a start and an end cell
+static int profile_align(int mode, int single, const int8_t* prof, size_t m, const char* B, size_t b_len,
+                         int64_t n_pairs, const int64_t* b_off, const int64_t* n, const char* alphabet, size_t n_sym,
+                         int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_ij, int64_t* end_ij,
+                         char* cigars, size_t cigar_cap, int64_t* cigar_off) {
+  if (mode != MSA_PROFILE_LOCAL && mode != MSA_PROFILE_GLOBAL && mode != MSA_PROFILE_FIT) return MSA_ERR_ARG;
+  // the caller's m x n_sym rows padded to the plan's 32 columns (codes no symbol has score 0; a local plan puts
+  // its sentinel's score into column 31 itself)
+  const bool sized = prof && n_sym >= 1 && n_sym <= 32 && m >= 1 && m <= (size_t)kPairLimit;
+  std::vector<int8_t> prof32(sized ? 32 * m : 0);
+  for (size_t r = 0; sized && r < m; ++r) std::copy(prof + n_sym * r, prof + n_sym * (r + 1), &prof32[32 * r]);
+  const AlignSpec spec = spec_profile(mode, sized ? prof32.data() : nullptr, alphabet, n_sym);
+  if (spec.status != MSA_OK || !sized || n_pairs < 1 || n_pairs > kPairLimit) return MSA_ERR_ARG;
+  const std::vector<int64_t> zero((size_t)n_pairs, 0), ms((size_t)n_pairs, (int64_t)m);
+  std::vector<int64_t> span(mode == MSA_PROFILE_FIT ? 2 * (size_t)n_pairs : 0, -1);
+  const AlignIn in{nullptr, B, m, b_len, n_pairs, zero.data(), ms.data(), b_off, n};
+  const bool local = mode == MSA_PROFILE_LOCAL;
+  const AlignOut out{score, local ? PairOut(end_ij) : PairOut(), local ? PairOut(beg_ij) : PairOut(),
+                     mode == MSA_PROFILE_FIT ? PairOut(span.data()) : PairOut(), cigars, cigar_cap, cigar_off};
+  const int rc = align_pairs(spec, single, in, kPairLimit, gap_open, gap_extend, -1, out);
+  // (a cigar buffer too small still has its scores and cells)
+  if (!local && (rc == MSA_OK || rc == MSA_ERR_CAPACITY))
+    for (int64_t p = 0; p < n_pairs; ++p) {
+      const bool fit = mode == MSA_PROFILE_FIT;
+      PairOut(beg_ij).put(p, 0, fit ? span[2 * (size_t)p] : 0);
+      PairOut(end_ij).put(p, (int64_t)m, fit ? span[2 * (size_t)p + 1] : n[p]);
+    }
+  return rc;
+}
+
+int msa_profile_align(int mode, const int8_t* prof, size_t m, const char* B0, size_t n, const char* alphabet,
+                      size_t n_sym, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_ij,
+                      int64_t* end_ij, char* cigar, size_t cigar_cap) {
+  const int64_t zero = 0, n1 = (int64_t)n;
+  int64_t coff[2];
+  return profile_align(mode, 1, prof, m, B0, n, 1, &zero, &n1, alphabet, n_sym, gap_open, gap_extend, score, beg_ij,
+                       end_ij, cigar, cigar_cap, coff);
+}
+
+int msa_profile_align_batch(int mode, const int8_t* prof, size_t m, const char* B, size_t b_len, int64_t n_pairs,
+                            const int64_t* b_off, const int64_t* n, const char* alphabet, size_t n_sym,
+                            int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_ij, int64_t* end_ij,
+                            char* cigars, size_t cigar_cap, int64_t* cigar_off) {
+  return profile_align(mode, 0, prof, m, B, b_len, n_pairs, b_off, n, alphabet, n_sym, gap_open, gap_extend, score,
+                       beg_ij, end_ij, cigars, cigar_cap, cigar_off);
 }
 
 }  // extern "C"

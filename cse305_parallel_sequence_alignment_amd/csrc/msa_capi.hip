@@ -476,6 +476,11 @@ kfn_t pick_kernel(int alg, int out, int tp, bool sgl) {
     case MSA_ALG_SWS: return tp == 2 ? kf_nd<MSA_ALG_SWS, 2>(out, sgl) : tp == 1 ? kf_nd<MSA_ALG_SWS, 1>(out, sgl) : nullptr;
     case MSA_ALG_SWS32:
       return tp == 2 ? kf_nd<MSA_ALG_SWS32, 2>(out, sgl) : tp == 1 ? kf_nd<MSA_ALG_SWS32, 1>(out, sgl) : nullptr;
+    // the profile plans: their 32-code twins' instantiations under the other score source
+    case MSA_ALG_NWP: return kf_nd<MSA_ALG_NWP, 0>(out, sgl);
+    case MSA_ALG_FITP: return kf_nd<MSA_ALG_FITP, 0>(out, sgl);
+    case MSA_ALG_SWP:
+      return tp == 2 ? kf_nd<MSA_ALG_SWP, 2>(out, sgl) : tp == 1 ? kf_nd<MSA_ALG_SWP, 1>(out, sgl) : nullptr;
   }
 #undef K3
   return nullptr;
@@ -612,7 +617,8 @@ int msa_plan_pair_layout(const msa_plan* P, int64_t pair, int64_t* out4) {
 }
 
 int msa_plan_run(msa_plan* P, const uint8_t* dA, const uint8_t* dB, void* c0, void* c1, void* c2, void* stream) {
-  if (!P || !dA || !dB) return MSA_ERR_ARG;
+  // (a profile plan's rows are its own: it reads no row codes)
+  if (!P || !dB || (!dA && !P->d_prof)) return MSA_ERR_ARG;
   if (P->d.cells != MSA_CELLS_NONE && !c0) return MSA_ERR_ARG;
   if (P->d.cells == MSA_CELLS_TAB && (!c1 || !c2)) return MSA_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
@@ -636,6 +642,7 @@ int msa_plan_run(msa_plan* P, const uint8_t* dA, const uint8_t* dB, void* c0, vo
   a.cod = P->d_cod;
   a.cod_copy = P->cod_copy;
   a.sub = P->d_sub;
+  a.prof = P->d_prof;
   a.br = P->d_br;
   a.snap = P->d_snap;
   a.blk = P->d_blk;
@@ -780,7 +787,7 @@ int msa_plan_format_info(const msa_plan* P, int32_t* out4) {
   out4[0] = alg == MSA_ALG_SWLP ? 1 : (alg == MSA_ALG_REF1 ? 2 : 0);
   out4[1] = P->tp;
   out4[2] = P->h16 ? 1 : 0;
-  out4[3] = msa_alg_info_of(alg).wide ? 1 : 0;
+  out4[3] = (msa_alg_info_of(alg).wide ? 1 : 0) | (msa_alg_info_of(alg).profile ? 2 : 0);
   return MSA_OK;
 }
 

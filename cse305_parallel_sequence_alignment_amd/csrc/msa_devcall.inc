@@ -140,6 +140,13 @@ class DeviceCall {
     if (rc == MSA_OK) plans_.v[plans_.n++] = *out;
     return rc;
   }
+  // ... scored by prof_rows rows of a profile (msa_plan_create_profile)
+  int create_profile_plan(const msa_plan_desc& d, const int8_t* prof, int64_t prof_rows, msa_plan** out) {
+    if (plans_.n == kMaxPlans) return MSA_ERR_NOMEM;
+    const int rc = msa_plan_create_profile(&d, prof, prof_rows, out);
+    if (rc == MSA_OK) plans_.v[plans_.n++] = *out;
+    return rc;
+  }
   // the idle plan of this shape from the plan cache, or a new one; it goes (back) to the cache if succeeded()
   int cached_plan(const PlanKey& k, const msa_plan_desc& d, msa_plan** out) {
     const int rc = cached_.acquire(k, d);

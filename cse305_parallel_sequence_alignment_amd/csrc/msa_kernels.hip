@@ -182,6 +182,10 @@ struct KArgs {
   // 5-bit codes: 1,024 raw scores, byte 32 a + b.
   // Smith-Waterman: the same two layouts, the virtual code's column (7 / 31) holding MSA_VIRT_SCORE
   const uint2* sub;
+  // algorithms that score from a profile (msa_alg.h): the plan's position-specific scores, 32 int8 per profile row
+  // (two uint4), column 31 of every row holding MSA_VIRT_SCORE for Smith-Waterman as a table's does; row r of pair
+  // p's matrix scores from profile row pairs[p].a_off + r - 1.  A and sub are unused (A may be null)
+  const uint4* prof;
 };
 #ifndef MSA_H16_PAIRED
 #define MSA_H16_PAIRED 1  // int16 chunk cells: two u-blocks of a lane per 16 B (msa_band.hip)
@@ -687,8 +691,9 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
   // stripe's start with two ds_read_b128.  A per-lane global load at a.sub + 32 ac would need the row code first:
   // two HBM latencies in a row in front of the workgroup's barriers at every round of stripes, or on the stripe's
   // start if issued behind them; 32 rows are too many for the 8-code kernels' uniform loads and select chain.
+  // (a profile plan has no table and no such copy: its lanes load their own rows, below)
   unsigned* subl = cring + (LDSCODE ? 4 * CRW : 0);
-  if constexpr (TR.wide) {
+  if constexpr (TR.wide && !TR.profile) {
     if (threadIdx.x < 256) subl[threadIdx.x] = reinterpret_cast<const unsigned*>(a.sub)[threadIdx.x];
   }
 
@@ -995,7 +1000,25 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
       const int ks = k0 + cur;  // pair-local stripe index
       const int row_i = 64 * ks + lane + 1;
       constexpr unsigned CMASK = TR.wide ? 31u : 7u;
-      const unsigned ac = (row_i <= m) ? (a.A[pd.a_off + row_i - 1] & CMASK) : 0u;
+      unsigned ac = 0u;
+      if constexpr (!TR.profile) ac = (row_i <= m) ? (a.A[pd.a_off + row_i - 1] & CMASK) : 0u;
+      // a profile: the row's 32 scores ARE the profile's row a_off + row_i - 1, an address that needs no row code --
+      // so the two 16-byte loads go out here, where the row code's load goes out for a table, and nothing waits on
+      // a second, dependent access at the stripe's start (the plan's copy is 16-byte aligned and rows are 32 bytes).
+      // A row past m (the pair's last stripe only) loads nothing: the pair's last row may be the allocation's last.
+      // It scores 0 against everything instead, which is harmless for the reason row code 0's table row is harmless
+      // today: a score enters its own lane's diagonal term and nothing else, values move only downwards (DPP to the
+      // next lane; the last stripe hands nothing on), and the stripe finalize reads lanes with L.i <= m alone -- the
+      // best cell, row m's maximum and the final state all drop such rows, and no walk enters a row below its start.
+      // (Zero scores also keep such a lane's values at or below the cells above it: inside the plan's ranges.)
+      uint4 pq0 = make_uint4(0u, 0u, 0u, 0u), pq1 = pq0;
+      if constexpr (TR.profile) {
+        if (row_i <= m) {
+          const uint4* prow = a.prof + 2 * (pd.a_off + row_i - 1);
+          pq0 = prow[0];
+          pq1 = prow[1];
+        }
+      }
       const unsigned ac2 = (TR.packed() && row_i <= m) ? (a.A[pd2.a_off + row_i - 1] & 7u) : 0u;
       // banded Gotoh: the row's profile is row ac of the plan's table.  The whole 64-byte table is loaded here at
       // wave-uniform addresses, independent of the row code's load and like it ahead of the idle phases; the lane's
@@ -1044,7 +1067,11 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
         }
       }
       // substitution profile of this row (codes 0..7; 5-bit codes: 0..31, row ac of the LDS table)
-      if constexpr (TR.wide) {
+      if constexpr (TR.profile) {
+        L.pw[0] = pq0.x; L.pw[1] = pq0.y; L.pw[2] = pq0.z; L.pw[3] = pq0.w;
+        L.pw[4] = pq1.x; L.pw[5] = pq1.y; L.pw[6] = pq1.z; L.pw[7] = pq1.w;
+        L.plo = L.phi = L.plo2 = L.phi2 = 0;
+      } else if constexpr (TR.wide) {
         const uint4* prow = reinterpret_cast<const uint4*>(subl + 8 * ac);
         const uint4 p0 = prow[0], p1 = prow[1];
         L.pw[0] = p0.x; L.pw[1] = p0.y; L.pw[2] = p0.z; L.pw[3] = p0.w;

@@ -122,6 +122,13 @@ struct msa_plan {
   // MSA_SW_SCORED: either layout, MSA_VIRT_SCORE in the virtual code's row and column
   int8_t sub[1024] = {};
   uint2* d_sub = nullptr;
+  // a profile plan (msa_plan_create_profile) scores from this instead: prof_rows rows of 32 int8, row r = the scores of
+  // profile position r by column code, the plan's own device copy (16-byte aligned: a pooled block; a lane loads its
+  // row as two dwordx4).  MSA_SW_SCORED: MSA_VIRT_SCORE in column 31 of every row.  The host copy lives until the
+  // upload (alloc_buffers)
+  std::vector<int8_t> prof;
+  int64_t prof_rows = 0;
+  uint4* d_prof = nullptr;
 
   bool chunked() const { return mode == PM_CHUNKED || mode == PM_BAND_CHUNKED; }
   void note_stream(hipStream_t s) {
@@ -160,7 +167,8 @@ bool free_ends(int alg) { return alg == MSA_NW_FIT || alg == MSA_NW_OVERLAP || a
 // wide32: a 32 x 32 table over 5-bit codes (msa_plan_create_scored32: MSA_NW_SCORED, MSA_NW_FIT, MSA_NW_OVERLAP,
 // MSA_NW_EXTEND only)
 // sw_smax: max(0, the largest table entry over real codes) of an MSA_SW_SCORED plan (unused by every other plan)
-int choose_algorithm(const msa_plan_desc* desc, bool wide32, int sw_smax, int& kalg, int& tp) {
+// profile: the 32-code id's profile twin (msa_plan_create_profile: MSA_SW_SCORED, MSA_NW_SCORED, MSA_NW_FIT only)
+int choose_algorithm(const msa_plan_desc* desc, bool wide32, bool profile, int sw_smax, int& kalg, int& tp) {
   const int out_mode = desc->cells;
   switch (desc->alg) {
     case MSA_SW_LINEAR:
@@ -221,6 +229,11 @@ int choose_algorithm(const msa_plan_desc* desc, bool wide32, int sw_smax, int& k
     default: return MSA_ERR_ARG;
   }
   if (wide32 && (kalg = msa_alg_info_of(kalg).twin32) == MSA_ALG_NONE) return MSA_ERR_UNSUPPORTED;
+  if (profile) {
+    // (no band under a profile: MSA_ALG_NWP accepts none, so any band but -1 is unsupported below)
+    if (kalg != MSA_ALG_SWS && kalg != MSA_ALG_NWA && kalg != MSA_ALG_FIT) return MSA_ERR_UNSUPPORTED;
+    kalg = kalg == MSA_ALG_SWS ? MSA_ALG_SWP : kalg == MSA_ALG_NWA ? MSA_ALG_NWP : MSA_ALG_FITP;
+  }
   const msa_alg_info t = msa_alg_info_of(kalg);
   if (desc->alg == MSA_SW_SCORED || desc->alg == MSA_NW_SCORED || free_ends(desc->alg)) {
     // the kinds that score from a table: direction bytes or the score alone, a band only where the algorithm accepts
@@ -277,12 +290,13 @@ int sub_abs_max(const int8_t* sub, int count) {
 // `scored`: the table of an MSA_NW_SCORED or MSA_NW_FIT plan (nullptr for every other plan), 64 scores or, for the
 // 32-code kernels, 1,024
 // sw_smax: as for choose_algorithm
-int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t* scored, int sw_smax) {
+// prof_abs: the largest |entry| of a profile plan's profile (-1: no profile plan), in the table's place
+int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t* scored, int sw_smax, int prof_abs) {
   const msa_alg_info t = msa_alg_info_of(kp.alg);
   for (int64_t p = 0; p < desc->n_pairs; ++p) {
     const int64_t m = desc->m[p], n = desc->n[p];
     if (m <= 0 || n <= 0 || m > (1 << 26) || n > (1 << 26)) return MSA_ERR_ARG;
-    if (scored) {
+    if (scored || (prof_abs >= 0 && t.cell == CELL_GOTOH)) {
       // MSA_NW_SCORED (MSA_ALG_NWA in band_kernel or stripe_kernel).  With s = the largest |S|, g, h >= 0, G = g + h:
       //   K = (s + 2 G + 2 g) T + h < 2^28,   T = m + n + 256.
       // Every value either kernel forms -- in or out of a row's band, E / F / H, stripe_kernel's H or band_kernel's
@@ -315,7 +329,10 @@ int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t*
       // steps and -inf, and the tracked maximum is a copy of a cell: the same inequality holds.
       // The 32-code kernels (MSA_ALG_NWA32, MSA_ALG_FIT32, MSA_ALG_OVL32, MSA_ALG_EXT32: stripe_kernel, unshifted, raw S) differ in where a step's
       // S comes from, not in what a step is: the same inequality with s over the 1,024 scores.
-      const int64_t s = sub_abs_max(scored, t.wide ? 1024 : 64), g = kp.gap_ext, h = kp.h, G = kp.gap_open;
+      // The profile kernels (MSA_ALG_NWP, MSA_ALG_FITP) are those kernels again with a row's 32 bytes taken from the
+      // profile: the same inequality with s over the whole profile (a row past m scores 0: within s).
+      const int64_t s = prof_abs >= 0 ? prof_abs : sub_abs_max(scored, t.wide ? 1024 : 64);
+      const int64_t g = kp.gap_ext, h = kp.h, G = kp.gap_open;
       if ((s + 2 * G + 2 * g) * (m + n + 256) + h >= (int64_t(1) << 28)) return MSA_ERR_UNSUPPORTED;
     }
     if (t.linear()) {
@@ -555,10 +572,11 @@ int size_grid(Launch& l, int per_cu) {
 // stripe_kernel's wrap row buffer entries per carried value (batch mode)
 int row_words(const Extents& ex) { return ((ex.P * MSA_K + MSA_ROWOFF + 32) + 15) & ~15; }
 // stripe_kernel's LDS: schedule, link rings, row buffer, for a single pair the code ring, and for 5-bit codes the
-// 32 x 32 table
+// 32 x 32 table (a profile plan has none)
 size_t stripe_lds_bytes(const msa_kparams& kp, int W, int nc) {
   return 4 * (16 + (size_t)kp.sched_cap * 8 + (size_t)(2 * W + 1) * nc * MSA_RING + (size_t)nc * kp.lds_row_words +
-              (kp.single == 1 ? (size_t)4 * (MSA_CRING / 4 + 16) : 0) + (msa_alg_info_of(kp.alg).wide ? 256 : 0));
+              (kp.single == 1 ? (size_t)4 * (MSA_CRING / 4 + 16) : 0) +
+              (msa_alg_info_of(kp.alg).wide && !msa_alg_info_of(kp.alg).profile ? 256 : 0));
 }
 
 // PM_STRIPE, PM_SPLIT: stripe_kernel over a batch's pairs (one workgroup walks a pair's whole stripe chain,
@@ -775,7 +793,12 @@ int alloc_buffers(msa_plan& P) {
   // (-1, -1), outside the matrix, which both walkers answer with MSA_ERR_ARG whatever the pooled block held before)
   if (free_ends(P.d.alg)) HIPCHK(hipMemset(P.d_res, 0xff, sizeof(PairResult) * np));
   const msa_alg_info t = msa_alg_info_of(P.main.kp.alg);
-  if (t.wide) {
+  if (t.profile) {
+    // the profile as plan_create made it: stripe_kernel's bytes are the raw scores, loaded by the lanes themselves
+    if (!P.alloc(&P.d_prof, P.prof.size())) return MSA_ERR_HIP;
+    HIPCHK(hipMemcpy(P.d_prof, P.prof.data(), P.prof.size(), hipMemcpyHostToDevice));
+    std::vector<int8_t>().swap(P.prof);
+  } else if (t.wide) {
     // the 32 x 32 table as it is: stripe_kernel's bytes are the raw S (each workgroup copies it to LDS)
     if (!P.alloc(&P.d_sub, sizeof(P.sub))) return MSA_ERR_HIP;
     HIPCHK(hipMemcpy(P.d_sub, P.sub, sizeof(P.sub), hipMemcpyHostToDevice));
@@ -845,24 +868,41 @@ int alloc_buffers(msa_plan& P) {
 }  // namespace
 
 // ---- the C entry points (C linkage by their declarations in msa.h; msa_plan_destroy: msa_capi.hip) ------
-static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32, msa_plan** out);
+static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32, const int8_t* prof,
+                       int64_t prof_rows, msa_plan** out);
 
-int msa_plan_create(const msa_plan_desc* desc, msa_plan** out) { return plan_create(desc, nullptr, false, out); }
+int msa_plan_create(const msa_plan_desc* desc, msa_plan** out) {
+  return plan_create(desc, nullptr, false, nullptr, 0, out);
+}
 
 int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_plan** out) {
-  return plan_create(desc, sub, false, out);
+  return plan_create(desc, sub, false, nullptr, 0, out);
 }
 
 int msa_plan_create_scored32(const msa_plan_desc* desc, const int8_t* sub32, msa_plan** out) {
   if (!sub32) return MSA_ERR_ARG;
-  return plan_create(desc, sub32, true, out);
+  return plan_create(desc, sub32, true, nullptr, 0, out);
+}
+
+int msa_plan_create_profile(const msa_plan_desc* desc, const int8_t* prof, int64_t prof_rows, msa_plan** out) {
+  if (!prof || prof_rows < 1) return MSA_ERR_ARG;
+  return plan_create(desc, nullptr, false, prof, prof_rows, out);
 }
 
 // sub: 64 scores S[8 a + b] or nullptr, or with wide32 1,024 scores S[32 a + b]
-static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32, msa_plan** out) {
+// prof: nullptr, or (without sub) prof_rows x 32 scores, row r = profile position r by column code
+static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32, const int8_t* prof,
+                       int64_t prof_rows, msa_plan** out) {
   if (!desc || !out || desc->n_pairs <= 0 || !desc->m || !desc->n || !desc->a_off || !desc->b_off) return MSA_ERR_ARG;
   const bool sw_scored = desc->alg == MSA_SW_SCORED;
   if (sub && desc->alg != MSA_NW_SCORED && !free_ends(desc->alg) && !sw_scored) return MSA_ERR_UNSUPPORTED;
+  if (prof) {
+    if (!sw_scored && desc->alg != MSA_NW_SCORED && desc->alg != MSA_NW_FIT) return MSA_ERR_UNSUPPORTED;
+    // every pair's rows lie inside the profile (many pairs may name the same rows)
+    for (int64_t p = 0; p < desc->n_pairs; ++p)
+      if (desc->a_off[p] < 0 || desc->a_off[p] > prof_rows || desc->m[p] > prof_rows - desc->a_off[p])
+        return MSA_ERR_ARG;
+  }
   int rc = ensure_device();
   if (rc != MSA_OK) return rc;
   // (a plan without device buffers yet destroys cleanly: no streams, no blocks, null events)
@@ -874,8 +914,22 @@ static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32
   // MSA_SW_SCORED: the launch's own table.  The highest code (7, or 31 over 5-bit codes) is the virtual column's, so
   // the caller's entries with either index equal to it are ignored: that column carries MSA_VIRT_SCORE in every row
   // (and so does its row, which no input selects); smax is taken over the real codes alone
-  int sw_smax = 0;
-  if (sw_scored) {
+  int sw_smax = 0, prof_abs = -1;
+  if (prof) {
+    // the launch's own profile.  MSA_SW_SCORED: column 31 is the virtual column's in every row, as in a table (the
+    // caller's entries there are ignored), and smax is taken over the real codes; s is the largest |entry| of all
+    P->prof.assign(prof, prof + 32 * prof_rows);
+    P->prof_rows = prof_rows;
+    prof_abs = 0;
+    for (int64_t r = 0; r < prof_rows; ++r)
+      for (int b = 0; b < 32; ++b) {
+        int8_t& v = P->prof[(size_t)(32 * r + b)];
+        if (sw_scored && b == 31) { v = (int8_t)MSA_VIRT_SCORE; continue; }
+        prof_abs = std::max(prof_abs, std::abs((int)v));
+        sw_smax = std::max(sw_smax, (int)v);
+      }
+    if (sw_scored) P->d.track_end = 1;  // (always tracked, as under a table)
+  } else if (sw_scored) {
     if (!sub && (desc->match < -128 || desc->match > 127 || desc->mismatch < -128 || desc->mismatch > 127))
       return MSA_ERR_UNSUPPORTED;
     const int nc = wide32 ? 32 : 8;
@@ -889,7 +943,7 @@ static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32
     P->d.track_end = 1;  // (always tracked: the walkers' check)
   }
   int kalg, tp;
-  if ((rc = choose_algorithm(desc, wide32, sw_smax, kalg, tp)) != MSA_OK) return rc;
+  if ((rc = choose_algorithm(desc, wide32, prof != nullptr, sw_smax, kalg, tp)) != MSA_OK) return rc;
   P->tp = tp;
   if (desc->single && desc->n_pairs != 1) return MSA_ERR_ARG;
   // (alg, cells, tracking) combinations no kernel computes: every family takes a subset of the stripe kernel's
@@ -904,15 +958,17 @@ static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32
   // score as MSA_NW_SCORED does
   const bool scored = desc->alg == MSA_NW_SCORED || free_ends(desc->alg);
   int smax = 0;
-  if (scored && !sub && (desc->match < -128 || desc->match > 127 || desc->mismatch < -128 || desc->mismatch > 127))
+  if (scored && !sub && !prof &&
+      (desc->match < -128 || desc->match > 127 || desc->mismatch < -128 || desc->mismatch > 127))
     return MSA_ERR_UNSUPPORTED;
   if (wide32 && !sw_scored) std::memcpy(P->sub, sub, sizeof(P->sub));
-  for (int k = 0; k < 64 && !wide32 && !sw_scored; ++k) {
+  for (int k = 0; k < 64 && !wide32 && !sw_scored && !prof; ++k) {
     const bool diag = k / 8 == k % 8;
     P->sub[k] = sub ? sub[k] : (int8_t)(scored ? (diag ? desc->match : desc->mismatch) : (diag ? 1 : 0));
     smax = k ? std::max(smax, (int)P->sub[k]) : (int)P->sub[k];
   }
-  if ((rc = check_ranges(desc, P->main.kp, scored ? P->sub : nullptr, sw_smax)) != MSA_OK) return rc;
+  if ((rc = check_ranges(desc, P->main.kp, scored && !prof ? P->sub : nullptr, sw_smax, prof_abs)) != MSA_OK)
+    return rc;
   P->mode = choose_mode(desc, kalg, tp, smax);
   set_layout_mode(*P, desc);
   const Extents ex = lay_out_pairs(*P, desc);

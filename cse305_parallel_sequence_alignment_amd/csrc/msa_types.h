@@ -28,6 +28,9 @@ enum msa_alg {
   MSA_ALG_OVL32 = 14,
   MSA_ALG_EXT = 15,    // MSA_NW_EXTEND
   MSA_ALG_EXT32 = 16,
+  MSA_ALG_SWP = 17,    // every XP: X32 under a position-specific profile, one 32-byte row of scores per row of the
+  MSA_ALG_NWP = 18,    // matrix (msa_plan_create_profile: MSA_SW_SCORED, MSA_NW_SCORED, MSA_NW_FIT)
+  MSA_ALG_FITP = 19,
 };
 
 // Per-cell outputs.
@@ -40,7 +43,8 @@ enum msa_out {
 
 // One pair of sequences inside a launch.  Codes are uint8 in [0,8) ([0,32): the 5-bit algorithms, msa_alg.h).
 typedef struct msa_pair_desc {
-  int64_t a_off;       // offset of row codes (A[0] = row 1) in the A code array
+  int64_t a_off;       // offset of row codes (A[0] = row 1) in the A code array (a profile plan: of row 1's 32 scores
+                       // in the plan's profile, in rows)
   int64_t b_off;       // offset of column codes (B[0] = column 1) in the B code array
   int32_t m, n;        // rows, columns
   int32_t stripe0;     // first global stripe index of this pair (result / meta arrays)

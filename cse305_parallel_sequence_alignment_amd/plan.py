@@ -50,7 +50,7 @@ class Plan:
     """One launch shape: ``n_pairs`` pairs of (m_k, n_k) codes at (a_off_k, b_off_k)."""
 
     def __init__(self, alg: int, cells: int, ms, ns, a_offs, b_offs, match=1, mismatch=0, gap_open=1,
-                 gap_extend=1, start_type=-1, band=-1, track_end=False, single=None, sub=None):
+                 gap_extend=1, start_type=-1, band=-1, track_end=False, single=None, sub=None, profile=None):
         """``sub`` (NW_SCORED, NW_FIT, NW_OVERLAP, NW_EXTEND and SW_SCORED only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code
         a against column code b (msa_plan_create_scored); None scores ``match`` on the diagonal and ``mismatch``
         elsewhere.  A 32 x 32 ``sub`` makes a plan over 5-bit codes (msa_plan_create_scored32: inputs in [0, 32), always the
@@ -68,7 +68,13 @@ class Plan:
         An SW_SCORED plan (SW_AFFINE's recurrence under the table: ``band`` -1, CELLS_DIR or CELLS_NONE) keeps the
         highest code, 7 or 31, as the kernels' out-of-matrix sentinel: inputs are codes 0..6 / 0..30 and ``sub``'s last
         row and column are ignored.  It always tracks its end cell and runs the stripe kernel; ``traceback``,
-        ``traceback_batch`` and ``deskew_dir`` serve it as they serve an SW_AFFINE plan."""
+        ``traceback_batch`` and ``deskew_dir`` serve it as they serve an SW_AFFINE plan.
+        ``profile`` (SW_SCORED, NW_SCORED, NW_FIT only; with ``sub`` a ValueError): a rows x 32 array-like of int8
+        scores, ``profile[r][c]`` = profile position r against column code c (msa_plan_create_profile).  The rows of
+        pair k are profile rows ``a_offs[k] .. a_offs[k] + ms[k]``, which many pairs may share; ``run`` takes
+        ``dA=None``.
+        Everything else -- codes (``format_info()['codes'] == 32``), the sentinel of a local plan (column 31 is
+        ignored), results and walks -- is a 32 x 32 ``sub`` plan's.  ``self.profile`` tells whether the plan is one."""
         L = LB.lib()
         self.alg, self.cells = alg, cells
         self.ms = [int(x) for x in ms]
@@ -83,7 +89,17 @@ class Plan:
                         single=int(bool(single)), n_pairs=npairs, m=self._arrs[0], n=self._arrs[1],
                         a_off=self._arrs[2], b_off=self._arrs[3])
         self._h = C.c_void_p()
-        if sub is None:
+        self.profile = profile is not None
+        if self.profile:
+            if sub is not None:
+                raise ValueError("give either sub or profile, not both")
+            prof = np.asarray(profile)
+            if prof.ndim != 2 or prof.shape[1] != 32 or prof.shape[0] < 1 or (prof != prof.astype(np.int8)).any():
+                raise ValueError("profile must be rows x 32 scores in [-128, 127]")
+            prof = np.ascontiguousarray(prof, dtype=np.int8)
+            LB.check(L.msa_plan_create_profile(C.byref(d), prof.ctypes.data_as(C.c_void_p), prof.shape[0],
+                                               C.byref(self._h)), "msa_plan_create_profile")
+        elif sub is None:
             LB.check(L.msa_plan_create(C.byref(d), C.byref(self._h)), "msa_plan_create")
         else:
             tab = np.asarray(sub)
@@ -123,7 +139,8 @@ class Plan:
 
         need_a = max(o + m for o, m in zip(self._arrs[2], self.ms))
         need_b = max(o + n for o, n in zip(self._arrs[3], self.ns))
-        for name, t, need in (("dA", dA, need_a), ("dB", dB, need_b)):
+        # (a profile plan reads no row codes: its dA is ignored and may be None)
+        for name, t, need in (("dA", dA, need_a), ("dB", dB, need_b))[(1 if self.profile else 0):]:
             if t is None or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
                 raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor of codes")
             if t.numel() < need:
@@ -140,8 +157,8 @@ class Plan:
 
     def run(self, dA, dB, out0=None, out1=None, out2=None, stream=None):
         self._check_buffers(dA, dB, (out0, out1, out2))
-        LB.check(LB.lib().msa_plan_run(self._h, _ptr(dA), _ptr(dB), _ptr(out0), _ptr(out1), _ptr(out2),
-                                       _stream_ptr(stream)), "msa_plan_run")
+        LB.check(LB.lib().msa_plan_run(self._h, None if self.profile else _ptr(dA), _ptr(dB), _ptr(out0), _ptr(out1),
+                                       _ptr(out2), _stream_ptr(stream)), "msa_plan_run")
 
     def results(self, stream=None):
         """Per-pair results; raises MsaError(TIMEOUT) if any run since creation / clear_error() had a kernel
@@ -179,12 +196,13 @@ class Plan:
     def format_info(self) -> dict:
         """The number formats the plan chose (msa_plan_format_info): values ("int32", "packed16" couples or
         "tagged4" Gotoh), end-cell tracking ("none", "select" or the packed "key"), whether the chunks of a
-        chunked banded plan write int16 cells, and the symbol codes the plan takes (8, or 32 for a 32 x 32 table)."""
+        chunked banded plan write int16 cells, the symbol codes the plan takes (8, or 32 for a 32 x 32 table or a
+        profile), and whether the plan scores from a profile."""
         v = (C.c_int32 * 4)()
         LB.check(LB.lib().msa_plan_format_info(self._h, v), "msa_plan_format_info")
         return dict(values={0: "int32", 1: "packed16", 2: "tagged4"}[v[0]],
                     tracking={0: "none", 1: "select", 2: "key"}[v[1]], int16_cells=int(v[2]),
-                    codes=32 if v[3] else 8)
+                    codes=32 if v[3] & 1 else 8, profile=bool(v[3] & 2))
 
     def clear_error(self, stream=None) -> None:
         LB.check(LB.lib().msa_plan_clear_error(self._h, _stream_ptr(stream)), "msa_plan_clear_error")

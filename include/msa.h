@@ -342,11 +342,32 @@ int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_pla
  * virtual column's, the inputs are codes 0..30 -- 31 symbols --, entries with either index 31 are ignored, smax is
  * taken over codes 0..30; msa_plan_traceback and msa_plan_traceback_batch walk it. */
 int msa_plan_create_scored32(const msa_plan_desc* desc, const int8_t* sub32, msa_plan** plan);
+/* MSA_SW_SCORED, MSA_NW_SCORED and MSA_NW_FIT under a position-specific score profile (a PSSM) in place of a table:
+ * f(i,j) = prof[32 r + code of B_j], r the profile position of row i -- the score no longer depends on a symbol of
+ * A, there is no A.  prof: host memory, prof_rows rows of 32 int8, row r column c = the score of profile position r
+ * against column code c; the plan makes its own device copy and owns it, as it owns a table's.  Pair p's rows 1..m[p]
+ * are profile rows desc->a_off[p] .. desc->a_off[p] + m[p] - 1; many pairs may name the same rows (a search: a_off
+ * all 0).  prof == NULL, prof_rows < 1, a negative a_off[p] or a_off[p] + m[p] > prof_rows: MSA_ERR_ARG.  Any other
+ * desc->alg: MSA_ERR_UNSUPPORTED, and so is any band but -1, for all three.  desc->match and desc->mismatch are
+ * ignored.  Cells (MSA_CELLS_DIR or MSA_CELLS_NONE), the gap rules, the value-range inequalities, a local plan's
+ * end-cell format rule and all their errors are msa_plan_create_scored32's for the same alg, with s = the largest
+ * |entry| of the whole profile and smax = max(0, the largest entry over columns 0..30).  A local plan keeps code 31 as
+ * the out-of-matrix sentinel: its inputs are codes 0..30 and column 31 of the caller's rows is ignored (the device
+ * copy carries the sentinel score there); global and fit plans take codes 0..31.
+ * msa_plan_run ignores dA (it may be NULL); dB is as for the 32-code plans.  Such a plan always launches the stripe
+ * kernel (msa_plan_launch_info mode 0), one pair or a batch: each lane loads its row's 32 bytes itself, and from there
+ * on the fill, the direction bytes and the results are a 32-code plan's -- for the profile whose row r is row
+ * code(A_r) of a 32 x 32 table, byte for byte that table plan's.  msa_plan_traceback (local), msa_plan_traceback_nw
+ * (global, fit) and msa_plan_traceback_batch walk it under their unchanged contracts.  msa_plan_format_info reports
+ * it in bit 1 of its fourth word.
+ * Not offered: overlap and extension profiles, a band, profiles over 3-bit codes, position-specific gap costs and
+ * profile-profile alignment. */
+int msa_plan_create_profile(const msa_plan_desc* desc, const int8_t* prof, int64_t prof_rows, msa_plan** plan);
 void msa_plan_destroy(msa_plan* plan);
 /* Elements (int32 for H/TAB planes, bytes for DIR) the per-cell output needs. */
 int msa_plan_cells_size(const msa_plan* plan, int64_t* elems);
-/* Launch on `stream`.  dA/dB: device code arrays.  cells0..2: device output
- * (H: cells0; DIR: cells0 as uint8; TAB: three planes), may be NULL for NONE. */
+/* Launch on `stream`.  dA/dB: device code arrays (dA is ignored by a profile plan and may be NULL for it).
+ * cells0..2: device output (H: cells0; DIR: cells0 as uint8; TAB: three planes), may be NULL for NONE. */
 int msa_plan_run(msa_plan* plan, const uint8_t* dA, const uint8_t* dB, void* cells0, void* cells1, void* cells2,
                  void* stream);
 /* Copy per-pair results to the host (synchronizes `stream`).  Returns
@@ -373,7 +394,8 @@ int msa_plan_launch_info(const msa_plan* plan, int32_t* out8);
  * int16 couples (two score-only SW-linear pairs per lane), 2 the x4 tagged values of the reference's Gotoh
  * (start type -1); end-cell tracking: 0 none, 1 compare-select on (value, position), 2 the first maximum's
  * step packed with the value into one int; 1 if the chunks of a chunked banded plan write int16 cells;
- * 1 for a plan over 5-bit codes (msa_plan_create_scored32), 0 for every other plan}. */
+ * bit 0: a plan over 5-bit codes (msa_plan_create_scored32, msa_plan_create_profile), bit 1: a profile plan
+ * (msa_plan_create_profile); 0 for every other plan}. */
 int msa_plan_format_info(const msa_plan* plan, int32_t* out4);
 /* The sticky error word (0 = no error; else the kernel site code), synchronizes. */
 int msa_plan_error(msa_plan* plan, int* code, void* stream);
@@ -752,6 +774,35 @@ int msa_sw_align_batch_scored32(const char* A, size_t a_len, const char* B, size
                                 const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
                                 int32_t gap_extend, int32_t* score, int64_t* end_ij, int64_t* beg_ij, char* cigars,
                                 size_t cigar_cap, int64_t* cigar_off);
+
+/* A position-specific score profile against sequences (build extension: msa_plan_create_profile's plans): local
+ * (MSA_SW_SCORED's recurrence, end cell and walk), global (MSA_NW_SCORED's, unbanded) or fit (MSA_NW_FIT's: all of
+ * the profile in a substring of B).  prof: m x n_sym int8, row-major, prof[n_sym r + c] = the score of profile
+ * position r against alphabet[c] -- what a caller's PSSM looks like; the entry pads it to the plans' 32 columns.
+ * alphabet: n_sym distinct bytes, the symbols of B, a symbol's code is its index; n_sym is at most 31 for
+ * MSA_PROFILE_LOCAL (the highest code is the kernels' sentinel) and at most 32 otherwise.  The batch aligns the ONE
+ * profile against n_pairs sequences B[b_off[p] .. b_off[p] + n[p]): every pair uses all m rows.
+ * Results, one shape for every mode: score (n_pairs); beg_ij and end_ij, two int64 {i, j} per pair (either may be
+ * NULL) -- global: {0, 0} and {m, n}; fit: {0, beg_j} and {m, end_j}, B[beg_j .. end_j) being the substring (beg_j =
+ * -1 without a walk); local: the start cell and the end cell as msa_sw_align reports them --; and the CIGAR, start ->
+ * end, I consuming a profile row and D a symbol of B.  Score-only calls (cigar NULL; local: and beg_ij NULL),
+ * MSA_ERR_CAPACITY (the batch: with the needed size in cigar_off[n_pairs]; cigar_off, n_pairs + 1, is required with
+ * cigars), chunks of pairs and a local call's empty result are msa_sw_align_batch_scored32's,
+ * msa_nw_align_batch_scored32's and msa_fit_align_batch32's; the profile's 32 bytes per row count against the device
+ * budget.
+ * Errors, in this order: a mode other than the three, n_sym out of range, a duplicate symbol, or a NULL prof or
+ * alphabet: MSA_ERR_ARG; the other argument errors (m, n[p] < 1, a range outside B, n_pairs < 1, a NULL array):
+ * MSA_ERR_ARG; the gap rule (local: gap_open, gap_extend >= 0; else gap_open >= gap_extend >= 0):
+ * MSA_ERR_UNSUPPORTED; a symbol of B outside the alphabet: MSA_ERR_ALPHABET; and only then the device.
+ * Building a PSSM from a multiple alignment -- counts, pseudocounts, log-odds -- is the caller's job. */
+enum { MSA_PROFILE_LOCAL = 0, MSA_PROFILE_GLOBAL = 1, MSA_PROFILE_FIT = 2 };
+int msa_profile_align(int mode, const int8_t* prof, size_t m, const char* B0, size_t n, const char* alphabet,
+                      size_t n_sym, int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_ij,
+                      int64_t* end_ij, char* cigar, size_t cigar_cap);
+int msa_profile_align_batch(int mode, const int8_t* prof, size_t m, const char* B, size_t b_len, int64_t n_pairs,
+                            const int64_t* b_off, const int64_t* n, const char* alphabet, size_t n_sym,
+                            int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* beg_ij, int64_t* end_ij,
+                            char* cigars, size_t cigar_cap, int64_t* cigar_off);
 
 #ifdef __cplusplus
 }
