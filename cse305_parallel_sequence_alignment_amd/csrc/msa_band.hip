@@ -320,9 +320,9 @@ __global__ __launch_bounds__((BK_W + 1) * 64) void band_kernel(KArgs a) {
       // chunked, chunk >= 1, int16 chunk cells (msa_plan_create): H relative to the guessed row, 2 B per
       // cell, widened by chunk_add_kernel
       const bool o16 = chunked && c >= 1 && a.outH16 != nullptr;
-      // (MSA_H16_PAIRED: a lane's cells of u-blocks 2h and 2h+1 side by side, one 16-B store per two
-      // u-blocks; chunk_add_kernel undoes the pairing)
-      int16_t* const orow16 = a.outH16 + (size_t)(k - C) * pd.pmax * MSA_K * 64 + (MSA_H16_PAIRED ? 8 : 4) * lane;
+      // (a lane's cells of u-blocks 2h and 2h+1 side by side, one 16-B store per two u-blocks;
+      // chunk_add_kernel undoes the pairing)
+      int16_t* const orow16 = a.outH16 + (size_t)(k - C) * pd.pmax * MSA_K * 64 + 8 * lane;
       // direction bytes: block q of the stripe is the phase's 1 KiB, 16 B per lane
       uint8_t* odir = nullptr;
       if constexpr (DIRK) odir = a.outDir + pd.out_off + (size_t)k * pd.pmax * MSA_K * 64 + 16 * lane;
@@ -499,15 +499,11 @@ __global__ __launch_bounds__((BK_W + 1) * 64) void band_kernel(KArgs a) {
             if constexpr (OUT == 2) {
               const fl_v2u hv = {__builtin_amdgcn_perm((unsigned)ho[4 * u + 1], (unsigned)ho[4 * u], 0x05040100u),
                                  __builtin_amdgcn_perm((unsigned)ho[4 * u + 3], (unsigned)ho[4 * u + 2], 0x05040100u)};
-              if constexpr (MSA_H16_PAIRED) {
-                if (u & 1) {
-                  const fl_v4u hp = {h16lo.x, h16lo.y, hv.x, hv.y};
-                  __builtin_nontemporal_store(hp, reinterpret_cast<fl_v4u*>(orow16 + (size_t)(2 * q + (u >> 1)) * 512));
-                } else {
-                  h16lo = hv;
-                }
+              if (u & 1) {
+                const fl_v4u hp = {h16lo.x, h16lo.y, hv.x, hv.y};
+                __builtin_nontemporal_store(hp, reinterpret_cast<fl_v4u*>(orow16 + (size_t)(2 * q + (u >> 1)) * 512));
               } else {
-                __builtin_nontemporal_store(hv, reinterpret_cast<fl_v2u*>(orow16 + (size_t)(4 * q + u) * 256));
+                h16lo = hv;
               }
             } else {
               const msa_v4i hv = {ho[4 * u], ho[4 * u + 1], ho[4 * u + 2], ho[4 * u + 3]};

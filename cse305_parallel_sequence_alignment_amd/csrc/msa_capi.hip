@@ -488,15 +488,13 @@ kfn_t pick_kernel(int alg, int out, int tp, bool sgl) {
 
 // single-pair SW linear (msa_flow.hip): pass 1 (chain), pass 2 (fill + H)
 kfn_t pick_flow(int alg, bool best, bool save, int tp, int R, bool nneg) {
-  // SW affine / the reference's Gotoh (direction bytes): pass 1 + in-launch pass 2, one row per lane;
+  // SW affine / the reference's Gotoh (direction bytes): pass 1 + in-launch pass 2, two rows per lane;
   // SW affine with scores >= 0: pass 1 applies the zero floor in its head phases only
   if (alg == MSA_ALG_SWA) {
-    if (!save) return nullptr;
-    if (R == 2) return nneg ? flow_kernel<false, false, true, true, 2, 1> : flow_kernel<true, false, true, true, 2, 1>;
-    return nneg ? flow_kernel<false, false, true, true, 1, 1> : flow_kernel<true, false, true, true, 1, 1>;
+    if (!save || R != 2) return nullptr;
+    return nneg ? flow_kernel<false, false, true, true, 2, 1> : flow_kernel<true, false, true, true, 2, 1>;
   }
-  if (alg == MSA_ALG_REF1)
-    return !save ? nullptr : (R == 2 ? flow_kernel<true, false, true, true, 2, 2> : flow_kernel<true, false, true, true, 1, 2>);
+  if (alg == MSA_ALG_REF1) return save && R == 2 ? flow_kernel<true, false, true, true, 2, 2> : nullptr;
   // score-only plans: pass 1 alone, one row per lane, best cell tracked in the chain;
   // H plans: pass 1 + in-launch pass 2, two rows per lane
   const bool fl = (alg == MSA_ALG_SWL);
@@ -510,11 +508,9 @@ kfn_t pick_flow(int alg, bool best, bool save, int tp, int R, bool nneg) {
 
 // the separate pass-2 launch of a long pair (flow_fill_kernel), same instantiation parameters
 kfn_t pick_fill(int alg, int tp, int R, bool nneg) {
-  if (alg == MSA_ALG_SWA)
-    return R == 2 ? (nneg ? flow_fill_kernel<false, false, 2, 1> : flow_fill_kernel<true, false, 2, 1>)
-                  : (nneg ? flow_fill_kernel<false, false, 1, 1> : flow_fill_kernel<true, false, 1, 1>);
-  if (alg == MSA_ALG_REF1) return R == 2 ? flow_fill_kernel<true, false, 2, 2> : flow_fill_kernel<true, false, 1, 2>;
   if (R != 2) return nullptr;
+  if (alg == MSA_ALG_SWA) return nneg ? flow_fill_kernel<false, false, 2, 1> : flow_fill_kernel<true, false, 2, 1>;
+  if (alg == MSA_ALG_REF1) return flow_fill_kernel<true, false, 2, 2>;
   if (alg == MSA_ALG_SWL) return tp ? flow_fill_kernel<true, true, 2, 0> : flow_fill_kernel<true, false, 2, 0>;
   return tp ? flow_fill_kernel<false, true, 2, 0> : flow_fill_kernel<false, false, 2, 0>;
 }

@@ -455,9 +455,7 @@ __device__ __forceinline__ FillArgs fill_args_of(kargs_c* k) {
 template <bool FLOOR, bool TRACKPOS, int R, int CALLER>
 // SW-linear pass-2 blocks take their arguments by value (C2 0.4646 -> 0.4604 ms against the kernarg pointer)
 __device__ __attribute__((noinline)) void fill_block(const FillArgs fa, int blk, int lane, lds_int* lds);
-template <int CALLER> __device__ __attribute__((noinline)) void fill_block_aff(kargs_c* ka, int blk, int lane, lds_int* lds);
 template <int CALLER> __device__ __attribute__((noinline)) void fill_block_aff2(kargs_c* ka, int blk, int lane, lds_int* lds);
-template <int CALLER> __device__ __attribute__((noinline)) void fill_block_got(kargs_c* ka, int blk, int lane, lds_int* lds);
 template <int CALLER> __device__ __attribute__((noinline)) void fill_block_got2(kargs_c* ka, int blk, int lane, lds_int* lds);
 
 template <bool FLOOR, bool BEST, bool SAVE, bool TRACKPOS, int R = 1, int FK = 0>
@@ -468,8 +466,8 @@ __global__ __launch_bounds__((FL_W + 2) * 64) __attribute__((amdgpu_waves_per_eu
   constexpr bool GS = !FLOOR;
   constexpr bool AFF = FK != 0;  // two values per link column (affine SW, Gotoh)
   constexpr bool GOT = FK == 2;  // the reference's Gotoh, tagged
-  static_assert(R == 1 || (R == 2 && !BEST), "two rows per lane: pass-2 plans only");
-  static_assert(!AFF || (SAVE && !BEST), "affine / Gotoh: two-pass");
+  static_assert(SAVE == (R == 2) && SAVE != BEST, "two rows per lane with a pass 2, one in score-only plans");
+  static_assert(!AFF || R == 2, "affine / Gotoh: two-pass");
   constexpr int NV = AFF ? 2 : 1;                  // values per column on a link (Z, F~)
   constexpr int NCP = AFF ? 4 : FL_NCOPY;          // LDS code copies (affine: 4-byte aligned reads)
   extern __shared__ __attribute__((aligned(16))) int smem[];
@@ -537,10 +535,8 @@ __global__ __launch_bounds__((FL_W + 2) * 64) __attribute__((amdgpu_waves_per_eu
         if (t >= a.nblk) break;
         kargs_c* ka = (kargs_c*)__builtin_amdgcn_kernarg_segment_ptr();  // (a is the only argument)
         lds_int* wl = L(smem + w * fl_p2ints(FL_PS));
-        if constexpr (GOT && R == 2) fill_block_got2<0>(ka, a.border[t], lane, wl);
-        else if constexpr (GOT) fill_block_got<0>(ka, a.border[t], lane, wl);
-        else if constexpr (AFF && R == 2) fill_block_aff2<0>(ka, a.border[t], lane, wl);
-        else if constexpr (AFF) fill_block_aff<0>(ka, a.border[t], lane, wl);
+        if constexpr (GOT) fill_block_got2<0>(ka, a.border[t], lane, wl);
+        else if constexpr (AFF) fill_block_aff2<0>(ka, a.border[t], lane, wl);
         else fill_block<FLOOR, TRACKPOS, R, 0>(fill_args_of(ka), a.border[t], lane, wl);
       }
 #ifdef MSA_STAMPS
@@ -788,9 +784,9 @@ __global__ __launch_bounds__((FL_W + 2) * 64) __attribute__((amdgpu_waves_per_eu
       const int k = k0 + w;
       const int cs = fl_cs(k);
       const int P = fl_P(k, m, n, R);
-      const int row_i = 64 * R * k + R * lane + 1;  // (R = 2, Gotoh: rows row_i, row_i + 1)
+      const int row_i = 64 * R * k + R * lane + 1;  // (the lane's rows: row_i, row_i + 1)
       const unsigned ac = (row_i <= m) ? (a.A[pd.a_off + row_i - 1] & 7u) : 0u;
-      const unsigned ac2 = (R == 2 && row_i + 1 <= m) ? (a.A[pd.a_off + row_i] & 7u) : 0u;
+      const unsigned ac2 = (row_i + 1 <= m) ? (a.A[pd.a_off + row_i] & 7u) : 0u;
       const bool has_out = (k < S - 1);
       const int Bin = (k == 0) ? P - 1 : min(P - 1, fl_bmax(k, m, n, R));
       const int dq_in = (w == 0) ? 0 : fl_dq(k);
@@ -805,8 +801,8 @@ __global__ __launch_bounds__((FL_W + 2) * 64) __attribute__((amdgpu_waves_per_eu
       unsigned plo, phi, plo2 = 0, phi2 = 0;
       if constexpr (GOT) fl_profile_got(g, ac, plo, phi);
       else fl_profile_aff(kp.match, kp.mismatch, g, oe, ac, plo, phi);
-      if constexpr (R == 2 && GOT) fl_profile_got(g, ac2, plo2, phi2);
-      if constexpr (R == 2 && !GOT) fl_profile_aff(kp.match, kp.mismatch, g, oe, ac2, plo2, phi2);
+      if constexpr (GOT) fl_profile_got(g, ac2, plo2, phi2);
+      else fl_profile_aff(kp.match, kp.mismatch, g, oe, ac2, plo2, phi2);
       // LDS code address of phase q: ring of copy x, byte (y_lane + 16 q) mod FL_CRING
       unsigned a_cring, y_code;
       {
@@ -815,29 +811,21 @@ __global__ __launch_bounds__((FL_W + 2) * 64) __attribute__((amdgpu_waves_per_eu
         a_cring = lds_addr(reinterpret_cast<int*>(codes + x * cstr));
         y_code = (unsigned)(c0 - x);
       }
-      // step 0: lane r at column cs - r (virtual, H = 0): its left cell's Z, the diagonal Z
-      // (Gotoh: Zl / E / Fo / U hold H~ / R~ / D~ / diagonal H~, the column-0 border)
-      const int flr0 = g * (64 * k + 1 + cs);  // e(i+j) at step 0, every lane
-      int Zl = g * (row_i + cs - lane - 1) - oe;
+      // step 0: lane r at column cs - r (virtual, H = 0, Z = e(i+j) - oe).  A lane's state is row 1's Z
+      // left, E~ and diagonal Z (Zl, E, U) and row 2's Z left, E~ and F~ (Zl2, E2, Fo2): row 2's diagonal
+      // is row 1's previous Z and its cell above row 1's new one -- no state of their own -- and the
+      // next lane's row 1 takes the cell above from row 2 (Zl2, Fo2) through the DPP.
+      // (the order of these statements shows in the instruction stream: DESIGN.md section 8)
+      int Zl =g * (row_i + cs - lane - 1) - oe;
       int U = Zl - g;
-      int E = MSA_NEG, Fo = MSA_NEG;
-      const int tmin = 1 - cs + lane;  // Gotoh: the lane's first step at column >= 1
-      if constexpr (GOT) {  // (E / Fo carry R~ + 4h / D~ + 4h in pass 1: see the step)
-        Zl = 1 - 4 * oe;
-        E = 1 - 4 * oe;
-        Fo = 1;
+      int E = MSA_NEG, E2 = MSA_NEG, Fo2 = MSA_NEG;
+      const int tmin = 1 - cs + lane;                 // Gotoh: the lane's first step at column >= 1
+      const int flb = g * (128 * k + 1 + cs + lane);  // affine: the floor e(i+j) of row 1 at step 0
+      int Zl2 = Zl + g;
+      if constexpr (GOT) {  // H~, R~ + 4h, D~ + 4h (see the step) and the diagonal H~: the column-0 border
+        Zl = Zl2 = E = E2 = 1 - 4 * oe;
+        Fo2 = 1;
         U = MSA_NEG;
-      }
-      // R = 2 (Gotoh): row 2's H~, R~ + 4h and D~ + 4h (Zl / E / U hold row 1's; row 2's diagonal is
-      // row 1's previous H~, its cell above row 1's new one -- no state of their own); the next lane's
-      // row 1 takes the cell above from row 2 (Zl2, Fo2) through the DPP.  Affine: row 2's Z left, E~,
-      // F~ (virtual cells left of column 1: H = 0, Z = e(i+j) - oe), the lane's floor e(i+j) row 1
-      int Zl2 = 1 - 4 * oe, E2 = 1 - 4 * oe, Fo2 = 1;
-      const int flb = g * (128 * k + 1 + cs + lane);  // affine R = 2: e(i+j) of row 1 at step 0
-      if constexpr (R == 2 && !GOT) {
-        Zl2 = Zl + g;
-        E2 = MSA_NEG;
-        Fo2 = MSA_NEG;
       }
       int pubv = 0, consv = 0;
       unsigned spins = 0;
@@ -923,39 +911,36 @@ __global__ __launch_bounds__((FL_W + 2) * 64) __attribute__((amdgpu_waves_per_eu
           ds_reread_b128x4(ra + 1024u, F);
           if constexpr (MASK) mask_in(q, Z, F);
         }
-        if ((q & ((1 << a.ps_shift) - 1)) == 0) {  // pass 2 restarts here: each lane's (Z left, E~, F~, diagonal Z)
-          if constexpr (R == 2) {  // rows 1 and 2: H~, R~, diagonal H~ / H~, R~, D~ (pass 2: unshifted)
-            // (affine: Z left, E~, diagonal Z / Z left, E~, F~)
-            constexpr int SH = GOT ? 1 : 0;
-            unsigned long long* sp = a.snap + ((size_t)k * a.nseg + (q >> a.ps_shift)) * 384 + lane;
-            gstore(sp, ((unsigned long long)ep << 32) | (unsigned)Zl);
-            gstore(sp + 64, ((unsigned long long)ep << 32) | (unsigned)(E - SH * 4 * oe));
-            gstore(sp + 128, ((unsigned long long)ep << 32) | (unsigned)U);
-            gstore(sp + 192, ((unsigned long long)ep << 32) | (unsigned)Zl2);
-            gstore(sp + 256, ((unsigned long long)ep << 32) | (unsigned)(E2 - SH * 4 * oe));
-            gstore(sp + 320, ((unsigned long long)ep << 32) | (unsigned)(Fo2 - SH * 4 * oe));
-          } else {
-            unsigned long long* sp = a.snap + ((size_t)k * a.nseg + (q >> a.ps_shift)) * 256 + lane;
-            gstore(sp, ((unsigned long long)ep << 32) | (unsigned)Zl);
-            gstore(sp + 64, ((unsigned long long)ep << 32) | (unsigned)(GOT ? E - 4 * oe : E));  // pass 2: R~, D~
-            gstore(sp + 128, ((unsigned long long)ep << 32) | (unsigned)(GOT ? Fo - 4 * oe : Fo));
-            gstore(sp + 192, ((unsigned long long)ep << 32) | (unsigned)U);
-          }
+        if ((q & ((1 << a.ps_shift) - 1)) == 0) {  // pass 2 restarts here, from each lane's state
+          // affine: Z left, E~, diagonal Z / Z left, E~, F~ of rows 1 / 2; Gotoh: H~, R~, diagonal H~ / H~,
+          // R~, D~ (pass 2: unshifted)
+          constexpr int SH = GOT ? 1 : 0;
+          unsigned long long* sp = a.snap + ((size_t)k * a.nseg + (q >> a.ps_shift)) * 384 + lane;
+          gstore(sp, ((unsigned long long)ep << 32) | (unsigned)Zl);
+          gstore(sp + 64, ((unsigned long long)ep << 32) | (unsigned)(E - SH * 4 * oe));
+          gstore(sp + 128, ((unsigned long long)ep << 32) | (unsigned)U);
+          gstore(sp + 192, ((unsigned long long)ep << 32) | (unsigned)Zl2);
+          gstore(sp + 256, ((unsigned long long)ep << 32) | (unsigned)(E2 - SH * 4 * oe));
+          gstore(sp + 320, ((unsigned long long)ep << 32) | (unsigned)(Fo2 - SH * 4 * oe));
         }
         int xz[16], xf[16];
         int pubn = 0;
-        const int flq = flr0 + 16 * g * q;
+        // Two references this lambda does not need.  Its closure had two more while a one-row step
+        // existed; at the smaller size the compiler turns mask_in's branches into selects (200-290
+        // instructions and 1-3 VGPRs more per kernel), code that has never been timed.
+        (void)chunk;
+        (void)grp;
         const unsigned cw[4] = {Cl.x, Cl.y, Ch.x, Ch.y};
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
-          const unsigned s4b = (R == 2) ? __builtin_amdgcn_perm(phi2, plo2, cw[u]) : 0u;
+          const unsigned s4b = __builtin_amdgcn_perm(phi2, plo2, cw[u]);
 #pragma unroll
           for (int kk = 0; kk < 4; ++kk) {
             const int kx = 4 * u + kk;
             if (kx == FL_PF) issue_reads(q + 1, Zn, Fn, Cln, Chn, pubn);
             const int sc = ((int)(s4 << (24 - 8 * kk))) >> 24;
-            if constexpr (GOT && R == 2) {
+            if constexpr (GOT) {
               // row 1: the cell above is the previous lane's row 2 (lane 0: the link)
               const int uH = dpp_shr1(Z[kx >> 2][kx & 3], Zl2);
               const int uD = dpp_shr1(F[kx >> 2][kx & 3], Fo2);
@@ -1014,36 +999,8 @@ __global__ __launch_bounds__((FL_W + 2) * 64) __attribute__((amdgpu_waves_per_eu
               Fo2 = dd2;
               xz[kx] = h2;
               xf[kx] = dd2;
-            } else if constexpr (GOT) {
-              // R~ and D~ are carried + 4h (E = R~ + 4h, Fo / F = D~ + 4h): then
-              //   R~ + 4h = max3(t1, t2 + 4h, t3),  D~ + 4h = max3(t1, t2, t3 + 4h)
-              // and t2 = t2' - 4h, t3 = t3' - 4h (4h keeps the tag bits): 11 VALU per step, not 12.
-              // SNAP and io-out's BR copy hand pass 2 the unshifted values; granules and rings keep
-              // this convention.
-              const int uH = dpp_shr1(Z[kx >> 2][kx & 3], Zl);
-              const int uD = dpp_shr1(F[kx >> 2][kx & 3], Fo);
-              const int t1 = (int)((unsigned)U | 3u) + sc;
-              const int t2p = (int)(((unsigned)E & ~3u) | 2u);
-              const int t3p = (int)(((unsigned)uD & ~3u) | 1u);
-              const int t2 = t2p - 4 * oe, t3 = t3p - 4 * oe;
-              int h = imax3(t1, t2, t3);
-              int rr = imax3(t1, t2p, t3);
-              int dd = imax3(t1, t2, t3p);
-              asm("" : "+v"(h));
-              if constexpr (HEAD) {
-                const bool before = 16 * q + kx < tmin;
-                h = before ? 1 - 4 * oe : h;
-                rr = before ? 1 - 4 * oe : rr;
-                dd = before ? 1 : dd;
-              }
-              U = uH;
-              Zl = h;
-              E = rr;
-              Fo = dd;
-              xz[kx] = h;
-              xf[kx] = dd;
-            } else if constexpr (R == 2) {
-              // affine, two rows: row 1 takes the cell above from the previous lane's row 2, row 2
+            } else {
+              // affine: row 1 takes the cell above from the previous lane's row 2, row 2
               // from row 1 (Z and F~ at the same column), its diagonal from row 1's previous Z
               const int upZ = dpp_shr1(Z[kx >> 2][kx & 3], Zl2);
               const int upF = dpp_shr1(F[kx >> 2][kx & 3], Fo2);
@@ -1068,23 +1025,6 @@ __global__ __launch_bounds__((FL_W + 2) * 64) __attribute__((amdgpu_waves_per_eu
               Zl2 = h2 - oe;
               xz[kx] = Zl2;
               xf[kx] = f2;
-            } else {
-              const int upZ = dpp_shr1(Z[kx >> 2][kx & 3], Zl);
-              const int upF = dpp_shr1(F[kx >> 2][kx & 3], Fo);
-              const int e = imax(E, Zl);
-              const int f = imax(upF, upZ);
-              // the floor e(i+j) (H = 0, a local start): with scores >= 0 (!FLOOR) the diagonal
-              // term of every real cell is already >= it (H~diag + s + 2e >= e(i+j)), so only the
-              // head phases, where lanes still hold virtual columns left of column 1, need it
-              const int d = (FLOOR || HEAD) ? imax(U + sc, flq + g * kx) : U + sc;
-              int h = imax3(d, e, f);
-              asm("" : "+v"(h));
-              U = upZ;
-              E = e;
-              Fo = f;
-              Zl = h - oe;
-              xz[kx] = Zl;
-              xf[kx] = f;
             }
           }
         }
@@ -1304,10 +1244,10 @@ __global__ __launch_bounds__((FL_W + 2) * 64) __attribute__((amdgpu_waves_per_eu
         }
         if constexpr (SAVE && (MSA_ABL & 2) == 0) {
           if ((q & ((1 << a.ps_shift) - 1)) == 0) {  // pass 2 restarts here: each lane's left and diagonal values
-            unsigned long long* sp = a.snap + ((size_t)k * a.nseg + (q >> a.ps_shift)) * (128 * R) + lane;
+            unsigned long long* sp = a.snap + ((size_t)k * a.nseg + (q >> a.ps_shift)) * 256 + lane;
             gstore(sp, ((unsigned long long)ep << 32) | (unsigned)X);
             gstore(sp + 64, ((unsigned long long)ep << 32) | (unsigned)U);
-            if constexpr (R == 2) gstore(sp + 128, ((unsigned long long)ep << 32) | (unsigned)X2);
+            gstore(sp + 128, ((unsigned long long)ep << 32) | (unsigned)X2);
           }
         }
         int hv[16];
@@ -1323,10 +1263,10 @@ __global__ __launch_bounds__((FL_W + 2) * 64) __attribute__((amdgpu_waves_per_eu
             const int kx = 4 * u + kk;
             if (kx == FL_PF) issue_reads(q + 1, INn, CWn, pubn);  // prefetch phase q+1 (6 DS ops)
             const int s = ((int)(s4 << (24 - 8 * kk))) >> 24;
-            if constexpr (R == 1) {
+            if constexpr (R == 1) {  // (score-only plans: BEST)
               const int h = fl_step<GS, FLOOR>(IN[kx >> 2][kx & 3], s, X, U, g);
               xo[kx] = X;
-              if constexpr (BEST) hv[kx] = GS ? h + negct + gk[kx] : h;
+              hv[kx] = GS ? h + negct + gk[kx] : h;
             } else if constexpr (GS) {
               fl_step2_gs(kk, IN[kx >> 2][kx & 3], s4, s4b, X, X2, U);
               xo[kx] = X2;
@@ -1473,13 +1413,14 @@ __device__ __forceinline__ fl_v4u p2_codes(lds_int* lds, int k, int lane) {
                 __builtin_amdgcn_alignbyte(d3, d2, sh), __builtin_amdgcn_alignbyte(d4, d3, sh)};
 }
 
-// What the five pass-2 block bodies share around their recurrences: the block's geometry (p2_geom), the
+// What the three pass-2 block bodies share around their recurrences: the block's geometry (p2_geom), the
 // wait for its inputs and their load (p2_wait_load), a phase's inputs out of the staged streams
 // (p2_unpack), the profile byte of a step (p2_sbyte), the block's first maximum (p2_block_best) and the
 // Gotoh phase dispatch (p2_got_phases).  All are inlined into the noinline bodies.
 //
-// Block blk = (stripe s, segment seg) of a plan with R rows per lane and PS phases per segment: phases
-// [q0, q1) of the stripe's P, first column cs, the lane's first row row_i and its one or two A codes,
+// Block blk = (stripe s, segment seg) of a plan with PS phases per segment (and two rows per lane, as in
+// every plan with a pass 2): phases [q0, q1) of the stripe's P, first column cs, the lane's first row
+// row_i and its two A codes,
 // nv bottom-row granules per BR stream from pass 1 (blocks [q0, qb) of the row above; none for stripe
 // 0), the lane's SNAP granules (SNAPW granules per block: 64 x the saved values) and the BR rows of
 // stripe s - 1 (value stream 0, and 1 for the two-stream kinds).  live: the block has phases.
@@ -1491,24 +1432,24 @@ struct P2Geom {
   const unsigned long long* br1;
   bool live;
 };
-template <int R, int PS, int SNAPW>
+template <int PS, int SNAPW>
 __device__ __forceinline__ P2Geom p2_geom(const FillArgs& a, int blk, int lane) {
   P2Geom G;
   const int m = a.m, n = a.n;
-  G.S = (m + 64 * R - 1) / (64 * R);
+  G.S = (m + 127) / 128;
   G.s = blk / a.nseg;
   G.seg = blk - G.s * a.nseg;
-  G.P = fl_P(G.s, m, n, R);
+  G.P = fl_P(G.s, m, n, 2);
   G.q0 = G.seg * PS;
   // (the rest is computed for a block without phases too -- address arithmetic, and A codes of rows <= m
   // only: a guard of its own here was a second divergent region in front of each body's, ~50 instructions)
   G.live = G.s < G.S && G.q0 < G.P;
   G.q1 = min(G.P, G.q0 + PS);
   G.cs = fl_cs(G.s);
-  G.row_i = 64 * R * G.s + R * lane + 1;
+  G.row_i = 128 * G.s + 2 * lane + 1;
   G.ac = (G.row_i <= m) ? (a.A[a.a_off + G.row_i - 1] & 7u) : 0u;
-  G.ac2 = (R == 2 && G.row_i + 1 <= m) ? (a.A[a.a_off + G.row_i] & 7u) : 0u;
-  const int Bin = (G.s == 0) ? G.P - 1 : min(G.P - 1, fl_bmax(G.s, m, n, R));
+  G.ac2 = (G.row_i + 1 <= m) ? (a.A[a.a_off + G.row_i] & 7u) : 0u;
+  const int Bin = (G.s == 0) ? G.P - 1 : min(G.P - 1, fl_bmax(G.s, m, n, 2));
   G.sp = a.snap + ((size_t)G.s * a.nseg + G.seg) * SNAPW + lane;
   G.br0 = a.br + (size_t)(G.s > 0 ? G.s - 1 : 0) * a.brw;
   G.br1 = a.br + (size_t)(G.S + (G.s > 0 ? G.s - 1 : 0)) * a.brw;
@@ -1646,30 +1587,32 @@ __device__ __forceinline__ void p2_got_phases(int q0, int q1, int tf, PHASE phas
 // Pass 2: block (stripe s, segment seg) of PS phases, one wave.  Its inputs
 // are {epoch, value} granules that pass 1 may still be writing: the wave waits
 // for the block's last bottom-row granule, then loads and checks them all.
-// R = 2: lane r holds rows 128s+2r+1 (X/U) and 128s+2r+2 (X2); cells go to the
-// R = 2 layout (per 4 steps: the wave's row-1 int4s, then its row-2 int4s).
+// Lane r holds rows 128s+2r+1 (X/U) and 128s+2r+2 (X2); cells go to the two-row
+// layout (per 4 steps: the wave's row-1 int4s, then its row-2 int4s).
+// (R: always 2; it stays in the signature, which names the function in the code object)
 template <bool FLOOR, bool TRACKPOS, int R, int CALLER>
 __device__ __attribute__((noinline)) void fill_block(const FillArgs a, int blk, int lane, lds_int* lds) {
+  static_assert(R == 2, "a pass 2 runs two rows per lane");
   constexpr int PS = fl_ps(CALLER);
   constexpr bool GS = !FLOOR;
   const int m = a.m, g = a.g;
-  const P2Geom G = p2_geom<R, PS, 128 * R>(a, blk, lane);
+  const P2Geom G = p2_geom<PS, 256>(a, blk, lane);
   const int s = G.s, q0 = G.q0, cs = G.cs, row_i = G.row_i;
   int bb = INT32_MIN, bi = 0, bj = 0;
   if (G.live) {
     unsigned plo, phi, plo2 = 0, phi2 = 0;
     fl_profile<GS, FLOOR>(a.match, a.mismatch, g, G.ac, plo, phi);
-    if constexpr (R == 2) fl_profile<GS, FLOOR>(a.match, a.mismatch, g, G.ac2, plo2, phi2);
-    int sn[R + 1] = {};  // SNAP: X, U (row 1's left and diagonal), R = 2: X2
+    fl_profile<GS, FLOOR>(a.match, a.mismatch, g, G.ac2, plo2, phi2);
+    int sn[3] = {};  // SNAP: X, U (row 1's left and diagonal), X2
     unsigned long long tload;
     // (not ready: nothing computed; the block reports no cell)
-    const int q1 = p2_wait_load<R + 1, 1, PS, false>(a, G, blk, lane, lds, sn, 0, tload) ? G.q1 : q0;
-    int X = sn[0], U = sn[1], X2 = sn[R];
+    const int q1 = p2_wait_load<3, 1, PS, false>(a, G, blk, lane, lds, sn, 0, tload) ? G.q1 : q0;
+    int X = sn[0], U = sn[1], X2 = sn[2];
     // row 0 (stripe 0): H = 0 left of and on the top border
     p2_stage<1, PS>(lds, s, G.nv, 16 * (q1 - q0), lane,
                 [&](int v, int) { return GS ? g * (cs + 16 * q0 + v) : -g; }, a.cod + a.cod_off, a.cod_copy, cs, q0);
-    // H = G - g(i+j); i+j = 64Rs + 1 + cs + t + (R-1) lane on row 1, +1 on row 2
-    const int negct0 = -g * (64 * R * s + 1 + cs + (R - 1) * lane);
+    // H = G - g(i+j); i+j = 128s + 1 + cs + t + lane on row 1, +1 on row 2
+    const int negct0 = -g * (128 * s + 1 + cs + lane);
     int gk[16];
 #pragma unroll
     for (int kx = 0; kx < 16; ++kx) {
@@ -1677,7 +1620,7 @@ __device__ __attribute__((noinline)) void fill_block(const FillArgs a, int blk, 
       asm("" : "+v"(gk[kx]));
     }
     int best = INT32_MIN, bt = -1, best2 = INT32_MIN, bt2 = -1;
-    msa_v4i* hp = reinterpret_cast<msa_v4i*>(a.outH + (size_t)a.out_off + (size_t)s * a.pmax * MSA_K * 64 * R) + lane;
+    msa_v4i* hp = reinterpret_cast<msa_v4i*>(a.outH + (size_t)a.out_off + (size_t)s * a.pmax * MSA_K * 128) + lane;
     for (int q = q0; q < q1; ++q) {
       int IN[16];
       p2_unpack<1, PS>(lds, q - q0, IN);
@@ -1688,54 +1631,47 @@ __device__ __attribute__((noinline)) void fill_block(const FillArgs a, int blk, 
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
-        const unsigned s4b = (R == 2) ? __builtin_amdgcn_perm(phi2, plo2, cw[u]) : 0u;
+        const unsigned s4b = __builtin_amdgcn_perm(phi2, plo2, cw[u]);
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
           const int kx = 4 * u + kk;
           const int sc = p2_sbyte(s4, kk);
-          if constexpr (R == 1) {
-            const int h = fl_step<GS, FLOOR>(IN[kx], sc, X, U, g);
-            hv[kx] = GS ? h + negct + gk[kx] : h;
-          } else {
-            const int sb = p2_sbyte(s4b, kk);
-            const int up = dpp_shr1(IN[kx], X2);
-            int h1 = imax3(U + sc, up, X);
-            if constexpr (FLOOR) h1 = imax(h1, 0);
-            asm("" : "+v"(h1));
-            U = up;
-            const int xprev = X;
-            X = GS ? h1 : h1 - g;
-            int h2 = imax3(xprev + sb, X, X2);
-            if constexpr (FLOOR) h2 = imax(h2, 0);
-            asm("" : "+v"(h2));
-            X2 = GS ? h2 : h2 - g;
-            hv[kx] = GS ? h1 + negct + gk[kx] : h1;
-            hv2[kx] = GS ? h2 + negct + gk[kx] - g : h2;
-          }
+          const int sb = p2_sbyte(s4b, kk);
+          const int up = dpp_shr1(IN[kx], X2);
+          int h1 = imax3(U + sc, up, X);
+          if constexpr (FLOOR) h1 = imax(h1, 0);
+          asm("" : "+v"(h1));
+          U = up;
+          const int xprev = X;
+          X = GS ? h1 : h1 - g;
+          int h2 = imax3(xprev + sb, X, X2);
+          if constexpr (FLOOR) h2 = imax(h2, 0);
+          asm("" : "+v"(h2));
+          X2 = GS ? h2 : h2 - g;
+          hv[kx] = GS ? h1 + negct + gk[kx] : h1;
+          hv2[kx] = GS ? h2 + negct + gk[kx] - g : h2;
           if constexpr (TRACKPOS) {
             if (hv[kx] > best) { best = hv[kx]; bt = 16 * q + kx; }
-            if (R == 2 && hv2[kx] > best2) { best2 = hv2[kx]; bt2 = 16 * q + kx; }
+            if (hv2[kx] > best2) { best2 = hv2[kx]; bt2 = 16 * q + kx; }
           }
         }
+        // (each store: one contiguous 1 KiB)
         __builtin_nontemporal_store(msa_v4i{hv[4 * u], hv[4 * u + 1], hv[4 * u + 2], hv[4 * u + 3]},
-                                    hp + (size_t)(4 * q + u) * 64 * R);
-        if constexpr (R == 2)  // (each store: one contiguous 1 KiB)
-          __builtin_nontemporal_store(msa_v4i{hv2[4 * u], hv2[4 * u + 1], hv2[4 * u + 2], hv2[4 * u + 3]},
-                                      hp + (size_t)(4 * q + u) * 128 + 64);
+                                    hp + (size_t)(4 * q + u) * 128);
+        __builtin_nontemporal_store(msa_v4i{hv2[4 * u], hv2[4 * u + 1], hv2[4 * u + 2], hv2[4 * u + 3]},
+                                    hp + (size_t)(4 * q + u) * 128 + 64);
       }
       if constexpr (!TRACKPOS) {
 #pragma unroll
         for (int kx = 0; kx < 16; kx += 2) best = imax3(best, hv[kx], hv[kx + 1]);
-        if constexpr (R == 2) {
 #pragma unroll
-          for (int kx = 0; kx < 16; kx += 2) best2 = imax3(best2, hv2[kx], hv2[kx + 1]);
-        }
+        for (int kx = 0; kx < 16; kx += 2) best2 = imax3(best2, hv2[kx], hv2[kx + 1]);
       }
     }
     bb = (row_i <= m) ? best : INT32_MIN;
     bi = row_i;
     bj = TRACKPOS ? cs + bt - lane : -1;
-    if (R == 2 && row_i + 1 <= m && best2 > bb) {  // ties keep the upper row
+    if (row_i + 1 <= m && best2 > bb) {  // ties keep the upper row
       bb = best2;
       bi = row_i + 1;
       bj = TRACKPOS ? cs + bt2 - lane : -1;
@@ -1745,92 +1681,20 @@ __device__ __attribute__((noinline)) void fill_block(const FillArgs a, int blk, 
   p2_block_best(a, blk, lane, bb, bi, bj);
 }
 
-// Pass 2, affine (config C5): block (stripe s, segment seg) recomputes its PS phases from
-// SNAP (Z left, E~, F~, diagonal Z per lane) and the stripe above's bottom row (Z and F~
-// granules), writes the direction bytes in the skewed stripe layout -- lane r's 16 bytes of a
-// phase are one 16-byte store, a wave's phase one contiguous 1 KiB -- and reduces its first
-// maximum H = H~ - e(i+j).  The bytes are stripe_kernel's MSA_ALG_SWA bytes (the walk
-// traceback_kernel<TB_SW> reads them unchanged).
-template <int CALLER>
-__device__ __attribute__((noinline)) void fill_block_aff(kargs_c* ka, int blk, int lane, lds_int* lds) {
-  constexpr int PS = fl_ps(CALLER);
-  const FillArgs a = fill_args_of(ka);
-  const int m = a.m, g = a.g, oe = a.oe;
-  const P2Geom G = p2_geom<1, PS, 256>(a, blk, lane);
-  const int s = G.s, q0 = G.q0, cs = G.cs, row_i = G.row_i;
-  int bb = INT32_MIN, bi = 0, bj = 0;
-  if (G.live) {
-    unsigned plo, phi;
-    fl_profile_aff(a.match, a.mismatch, g, oe, G.ac, plo, phi);
-    int sn[4] = {};  // SNAP: Z left, E~, F~, diagonal Z
-    unsigned long long tload;
-    const int q1 = p2_wait_load<4, 2, PS, true>(a, G, blk, lane, lds, sn, 0, tload) ? G.q1 : q0;
-    int Zl = sn[0], E = sn[1], Fo = sn[2], U = sn[3];
-    // row 0 (stripe 0): Z = g col - oe (H = 0), F~ = -inf
-    p2_stage<2, PS>(lds, s, G.nv, 16 * (q1 - q0), lane,
-                [&](int v, int k) { return k == 0 ? g * (cs + 16 * q0 + v) - oe : MSA_NEG; }, a.cod + a.cod_off,
-                a.cod_copy, cs, q0);
-    const int flr0 = g * (64 * s + 1 + cs);
-    int best = INT32_MIN, bt = -1;
-    fl_v4u* dp = reinterpret_cast<fl_v4u*>(a.outDir + (size_t)a.out_off + (size_t)s * a.pmax * 1024) + lane;
-    for (int q = q0; q < q1; ++q) {
-      int INZ[16], INF[16];
-      p2_unpack<2, PS>(lds, q - q0, INZ, INF);
-      const fl_v4u c4 = p2_codes<PS>(lds, q - q0, lane);
-      const unsigned cw[4] = {c4.x, c4.y, c4.z, c4.w};
-      const int flq = flr0 + 16 * g * q;
-      unsigned dw[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
-        unsigned word = 0;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-          const int kx = 4 * u + kk;
-          const int sc = p2_sbyte(s4, kk);
-          const int flr = flq + g * kx;
-          const int upZ = dpp_shr1(INZ[kx], Zl);
-          const int upF = dpp_shr1(INF[kx], Fo);
-          const int e = imax(E, Zl);
-          const int f = imax(upF, upZ);
-          const int draw = U + sc;
-          int h = imax3(imax(draw, flr), e, f);
-          asm("" : "+v"(h));
-          // stripe_kernel's SWA byte: H's source (0 local start, 1 diagonal, 2 E, 3 F), bit 2
-          // E opened from H(i, j-1), bit 3 F opened from H(i-1, j)
-          const unsigned hs = (h == flr) ? 0u : (h == draw ? 1u : (h == e ? 2u : 3u));
-          const unsigned dir = hs | ((e == Zl) ? 4u : 0u) | ((f == upZ) ? 8u : 0u);
-          word |= dir << (8 * kk);
-          const int hv = h - flr;
-          if (hv > best) { best = hv; bt = 16 * q + kx; }
-          U = upZ;
-          E = e;
-          Fo = f;
-          Zl = h - oe;
-        }
-        dw[u] = word;
-      }
-      __builtin_nontemporal_store(fl_v4u{dw[0], dw[1], dw[2], dw[3]}, dp + (size_t)q * 64);
-    }
-    bb = (row_i <= m) ? best : INT32_MIN;
-    bi = row_i;
-    bj = cs + bt - lane;
-    p2_stat_done(a, blk, lane, tload);
-  }
-  p2_block_best(a, blk, lane, bb, bi, bj);
-}
-
-// Pass 2, affine, two rows per lane (R = 2: 128-row stripes, lane r holds rows 128s+2r+1 and
-// 128s+2r+2 at column cs + t - r): as fill_block_aff, both rows per step -- row 1 takes the cell
-// above (Z, F~) from the previous lane's row 2 (lane 0: the stripe above's bottom row), row 2 from
-// row 1 at the same column and its diagonal from row 1's previous Z.  A phase's bytes go out as
-// one 2 KiB block (row-1 segments, then row-2 segments: traceback_kernel<TB_SW, 2>'s layout).
+// Pass 2, affine (config C5): block (stripe s, segment seg) recomputes its PS phases from SNAP
+// (row 1's Z left, E~ and diagonal Z, row 2's Z left, E~ and F~ per lane) and the stripe above's
+// bottom row (Z and F~ granules) and reduces its first maximum H = H~ - e(i+j).  Lane r holds rows
+// 128s+2r+1 and 128s+2r+2 at column cs + t - r: row 1 takes the cell above (Z, F~) from the previous
+// lane's row 2 (lane 0: the stripe above's bottom row), row 2 from row 1 at the same column and its
+// diagonal from row 1's previous Z.  The direction bytes are stripe_kernel's MSA_ALG_SWA bytes in the
+// skewed stripe layout: lane r's 16 bytes of a row and phase are one 16-byte store, and a phase goes
+// out as one 2 KiB block (row-1 segments, then row-2 segments: traceback_kernel<TB_SW, 2>'s layout).
 template <int CALLER>
 __device__ __attribute__((noinline)) void fill_block_aff2(kargs_c* ka, int blk, int lane, lds_int* lds) {
   constexpr int PS = fl_ps(CALLER);
   const FillArgs a = fill_args_of(ka);
   const int m = a.m, g = a.g, oe = a.oe;
-  const P2Geom G = p2_geom<2, PS, 384>(a, blk, lane);
+  const P2Geom G = p2_geom<PS, 384>(a, blk, lane);
   const int s = G.s, q0 = G.q0, cs = G.cs, row_i = G.row_i;
   int bb = INT32_MIN, bi = 0, bj = 0;
   if (G.live) {
@@ -1874,7 +1738,9 @@ __device__ __attribute__((noinline)) void fill_block_aff2(kargs_c* ka, int blk, 
           const int d1 = U + sc;
           int h1 = imax3(imax(d1, flr), e1, f1);
           asm("" : "+v"(h1));
-          const unsigned hs1 = (h1 == flr) ? 0u : (h1 == d1 ? 1u : (h1 == e1 ? 2u : 3u));
+          // stripe_kernel's SWA byte: H's source (0 local start, 1 diagonal, 2 E, 3 F), bit 2
+          // E opened from H(i, j-1), bit 3 F opened from H(i-1, j)
+          const unsigned hs1 =(h1 == flr) ? 0u : (h1 == d1 ? 1u : (h1 == e1 ? 2u : 3u));
           word1 |= (hs1 | ((e1 == Zl) ? 4u : 0u) | ((f1 == upZ) ? 8u : 0u)) << (8 * kk);
           if (h1 - flr > best) { best = h1 - flr; bt = 16 * q + kx; }
           const int zprev = Zl;
@@ -1915,108 +1781,22 @@ __device__ __attribute__((noinline)) void fill_block_aff2(kargs_c* ka, int blk, 
   p2_block_best(a, blk, lane, bb, bi, bj);
 }
 
-// Pass 2, Gotoh (the reference's main_alignment_function path): block (stripe s, segment
-// seg) recomputes its PS phases from SNAP (H~, R~, D~, diagonal H~ per lane) and the
-// stripe above's bottom row (H~ and D~ granules) and writes the tag bytes (T1's, T2's, T3's
-// predecessor: the diagonal H~'s, the left R~'s and the upper D~'s tag) in the skewed stripe
-// layout.  The block holding cell (m, n) stores its three tables, unshifted, as the last
-// stripe's final state (reduce_pairs_kernel turns it into the pair result, the walk reads
-// find_alignment's end rule from it).
-template <int CALLER>
-__device__ __attribute__((noinline)) void fill_block_got(kargs_c* ka, int blk, int lane, lds_int* lds) {
-  constexpr int PS = fl_ps(CALLER);
-  const FillArgs a = fill_args_of(ka);
-  const int m = a.m, n = a.n, S = (m + 63) / 64, g = a.g, h4 = 4 * a.oe;
-  const P2Geom G = p2_geom<1, PS, 256>(a, blk, lane);
-  const int s = G.s, q0 = G.q0, cs = G.cs, row_i = G.row_i;
-  if (G.live) {
-    unsigned plo, phi;
-    fl_profile_got(g, G.ac, plo, phi);
-    int sn[4] = {};  // SNAP: H~, R~, D~, diagonal H~
-    unsigned long long tload;
-    const int q1 = p2_wait_load<4, 2, PS, true>(a, G, blk, lane, lds, sn, 0, tload) ? G.q1 : q0;
-    int Hs = sn[0], Rs = sn[1], Ds = sn[2], U = sn[3];
-    // row 0 (stripe 0), tagged and shifted: H~ 3 at column 0, 2 - 4h right of it; D~ 3 - 4h, 2 - 8h
-    p2_stage<2, PS>(lds, s, G.nv, 16 * (q1 - q0), lane,
-                [&](int v, int k) {
-                  const int col = cs + 16 * q0 + v;
-                  return col < 0 ? MSA_NEG : (k == 0 ? (col == 0 ? 3 : 2 - h4) : (col == 0 ? 3 - h4 : 2 - 2 * h4));
-                },
-                a.cod + a.cod_off, a.cod_copy, cs, q0);
-    const int tmin = 1 - cs + lane;
-    // the final cell (m, n): the lane of row m at step n - cs + lane of the last stripe
-    const int tf = (row_i == m) ? n - cs + lane : -1;
-    fl_v4u* dp = reinterpret_cast<fl_v4u*>(a.outDir + (size_t)a.out_off + (size_t)s * a.pmax * 1024) + lane;
-    auto phase = [&](const int q, auto HEAD_, auto CAP_) __attribute__((always_inline)) {
-      constexpr bool HEAD = decltype(HEAD_)::value;  // lanes left of column 1 hold the border
-      constexpr bool CAP = decltype(CAP_)::value;    // the phase holds cell (m, n)
-      int INZ[16], INF[16];
-      p2_unpack<2, PS>(lds, q - q0, INZ, INF);
-      const fl_v4u c4 = p2_codes<PS>(lds, q - q0, lane);
-      const unsigned cw[4] = {c4.x, c4.y, c4.z, c4.w};
-      unsigned dw[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const unsigned s4 = __builtin_amdgcn_perm(phi, plo, cw[u]);
-        unsigned word = 0;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-          const int kx = 4 * u + kk;
-          const int sc = p2_sbyte(s4, kk);
-          const int uH = dpp_shr1(INZ[kx], Hs);
-          const int uD = dpp_shr1(INF[kx], Ds);
-          const int t1 = (int)((unsigned)U | 3u) + sc;
-          const int t2 = (int)(((unsigned)Rs & ~3u) | 2u);
-          const int t3 = (int)(((unsigned)uD & ~3u) | 1u);
-          const unsigned dir = ((unsigned)U & 3u) | (((unsigned)Rs & 3u) << 2) | (((unsigned)uD & 3u) << 4);
-          word |= dir << (8 * kk);
-          const int t1h = t1 - h4;
-          int hh = imax3(t1, t2, t3);
-          int rr = imax3(t1h, t2, t3 - h4);
-          int dd = imax3(t1h, t2 - h4, t3);
-          asm("" : "+v"(hh));
-          if constexpr (HEAD) {
-            const bool before = 16 * q + kx < tmin;
-            hh = before ? 1 - h4 : hh;
-            rr = before ? 1 - 2 * h4 : rr;
-            dd = before ? 1 - h4 : dd;
-          }
-          if constexpr (CAP) {
-            if (16 * q + kx == tf) {
-              const int gmn = g * (m + n);  // unshift
-              msa_stripe_meta* md = a.meta + a.stripe0 + S - 1;
-              md->fin[0] = (t1 >> 2) - gmn;
-              md->fin[1] = (t2 >> 2) - gmn;
-              md->fin[2] = (t3 >> 2) - gmn;
-              md->has_fin = 1;
-            }
-          }
-          U = uH;
-          Hs = hh;
-          Rs = rr;
-          Ds = dd;
-        }
-        dw[u] = word;
-      }
-      __builtin_nontemporal_store(fl_v4u{dw[0], dw[1], dw[2], dw[3]}, dp + (size_t)q * 64);
-    };
-    p2_got_phases(q0, q1, tf, phase);
-    p2_stat_done(a, blk, lane, tload);
-  }
-  if (lane == 0) a.blk[blk] = make_int4(0, 0, 0, 0);
-}
-
-// Pass 2, Gotoh, two rows per lane (R = 2: 128-row stripes, lane r holds rows 128s+2r+1 and
-// 128s+2r+2 at column cs + t - r): as fill_block_got, both rows per step -- row 1 takes the cell above
-// from the previous lane's row 2 (lane 0: the stripe above's bottom row), row 2 from row 1 at the same
-// column, its diagonal from row 1's previous cell.  A phase's bytes go out as one 2 KiB block: the
-// wave's row-1 16-byte segments, then its row-2 segments (traceback_kernel's R = 2 layout).
+// Pass 2, Gotoh (the reference's main_alignment_function path): block (stripe s, segment seg)
+// recomputes its PS phases from SNAP (row 1's H~, R~ and diagonal H~, row 2's H~, R~ and D~ per lane)
+// and the stripe above's bottom row (H~ and D~ granules) and writes the tag bytes (T1's, T2's, T3's
+// predecessor: the diagonal H~'s, the left R~'s and the upper D~'s tag) in the skewed stripe layout.
+// Lane r holds rows 128s+2r+1 and 128s+2r+2 at column cs + t - r: row 1 takes the cell above from the
+// previous lane's row 2 (lane 0: the stripe above's bottom row), row 2 from row 1 at the same column,
+// its diagonal from row 1's previous cell.  A phase's bytes go out as one 2 KiB block: the wave's
+// row-1 16-byte segments, then its row-2 segments (traceback_kernel's two-row layout).  The block
+// holding cell (m, n) stores its three tables, unshifted, as the last stripe's final state
+// (reduce_pairs_kernel turns it into the pair result, the walk reads find_alignment's end rule from it).
 template <int CALLER>
 __device__ __attribute__((noinline)) void fill_block_got2(kargs_c* ka, int blk, int lane, lds_int* lds) {
   constexpr int PS = fl_ps(CALLER);
   const FillArgs a = fill_args_of(ka);
   const int m = a.m, n = a.n, g = a.g, h4 = 4 * a.oe;
-  const P2Geom G = p2_geom<2, PS, 384>(a, blk, lane);
+  const P2Geom G = p2_geom<PS, 384>(a, blk, lane);
   const int s = G.s, q0 = G.q0, cs = G.cs, row_i = G.row_i;
   if (G.live) {
     unsigned plo, phi, plo2, phi2;
@@ -2148,6 +1928,7 @@ template <bool FLOOR, bool TRACKPOS, int R, int FK>
 #define FL_FILL_WPE 4  // waves per SIMD the pass-2 launch is sized for
 #endif
 __global__ __launch_bounds__(FL_FILLW * 64) __attribute__((amdgpu_waves_per_eu(FL_FILL_WPE, 8))) void flow_fill_kernel(KArgs a) {
+  static_assert(R == 2, "a pass 2 runs two rows per lane");
   extern __shared__ __attribute__((aligned(16))) int smem[];
   const int lane = threadIdx.x & 63;
   const int w = uni(threadIdx.x >> 6);
@@ -2158,10 +1939,8 @@ __global__ __launch_bounds__(FL_FILLW * 64) __attribute__((amdgpu_waves_per_eu(F
     if (lane == 0) t = atomicAdd(a.ticket + MSA_TK_BLOCK, 1);
     t = __builtin_amdgcn_readlane(t, 0);
     if (t >= a.nblk) break;
-    if constexpr (FK == 2 && R == 2) fill_block_got2<1>(ka, a.border[t], lane, wl);
-    else if constexpr (FK == 2) fill_block_got<1>(ka, a.border[t], lane, wl);
-    else if constexpr (FK == 1 && R == 2) fill_block_aff2<1>(ka, a.border[t], lane, wl);
-    else if constexpr (FK == 1) fill_block_aff<1>(ka, a.border[t], lane, wl);
+    if constexpr (FK == 2) fill_block_got2<1>(ka, a.border[t], lane, wl);
+    else if constexpr (FK == 1) fill_block_aff2<1>(ka, a.border[t], lane, wl);
     else fill_block<FLOOR, TRACKPOS, R, 1>(fill_args_of(ka), a.border[t], lane, wl);
   }
 }

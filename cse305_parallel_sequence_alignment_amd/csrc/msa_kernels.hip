@@ -187,9 +187,6 @@ struct KArgs {
   // p's matrix scores from profile row pairs[p].a_off + r - 1.  A and sub are unused (A may be null)
   const uint4* prof;
 };
-#ifndef MSA_H16_PAIRED
-#define MSA_H16_PAIRED 1  // int16 chunk cells: two u-blocks of a lane per 16 B (msa_band.hip)
-#endif
 
 template <int ALG>
 __device__ __forceinline__ void border_top(const msa_kparams& kp, int c, int (&v)[3], int r0 = 0) {
@@ -584,7 +581,6 @@ __device__ __forceinline__ unsigned score4_wide(const unsigned (&p)[8], unsigned
   return __builtin_amdgcn_perm(__builtin_amdgcn_perm(q3, q2, sa), __builtin_amdgcn_perm(q1, q0, sa), sb);
 }
 
-enum Src { SRC_BORDER = 0, SRC_RING = 1, SRC_ROW = 2, SRC_GLOBAL = 3 };
 enum Snk { SNK_NONE = 0, SNK_RING = 1, SNK_ROW = 2, SNK_GLOBAL = 3 };
 
 // Loader wave (wave W): in single mode it pulls the row above the
@@ -1785,43 +1781,29 @@ __global__ __launch_bounds__(256) void chunk_add_kernel(int32_t* H, const int16_
     // every load and every store instruction covers whole 128-B lines (16-B loads feeding two 16-B stores
     // 32 B apart wrote every other 16 B of a line per instruction: 190 vs 145 us for C3's in-place int32
     // add); plain loads, the int16 cells were just written and are partly in the MALL.
-    // MSA_H16_PAIRED: int16 16-B group G = (b, lane) holds the lane's 4 cells of u-blocks 2b and 2b + 1
-    // (int32 16-B groups (2b, lane) and (2b + 1, lane), 64 groups per u-block); else 8-B group x = the
-    // int32 16-B group x.
+    // The int16 16-B group G = (b, lane) holds the lane's 4 cells of u-blocks 2b and 2b + 1 (int32 16-B
+    // groups (2b, lane) and (2b + 1, lane), 64 groups per u-block).
     typedef int v2i_t __attribute__((ext_vector_type(2)));
     auto widen = [&](int lo, int hi) __attribute__((always_inline)) {
       return msa_v4i{(lo << 16 >> 16) + e, (lo >> 16) + e, (hi << 16 >> 16) + e, (hi >> 16) + e};
     };
-    if constexpr (MSA_H16_PAIRED) {
-      // one 8-B half of a pair group per thread (8-B loads, as below: 16-B loads feeding two stores 1 KB
-      // apart took 146 vs 134 us): half h of group (b, lane) -> int32 group (2b + h, lane); a wave's
-      // store covers 32 lanes' 16 B of two u-blocks, whole lines
-      const v2i_t* q = reinterpret_cast<const v2i_t*>(H16 + (size_t)(ks0 - chunk_c) * per);
-      for (size_t x0 = (size_t)blockIdx.x * 1024 + threadIdx.x; x0 < nv; x0 += step) {  // 4 loads in flight
-        v2i_t v[4];
+    // one 8-B half of a pair group per thread (8-B loads: 16-B loads feeding two stores 1 KB apart took
+    // 146 vs 134 us): half h of group (b, lane) -> int32 group (2b + h, lane); a wave's store covers 32
+    // lanes' 16 B of two u-blocks, whole lines
+    const v2i_t* q = reinterpret_cast<const v2i_t*>(H16 + (size_t)(ks0 - chunk_c) * per);
+    for (size_t x0 = (size_t)blockIdx.x * 1024 + threadIdx.x; x0 < nv; x0 += step) {  // 4 loads in flight
+      v2i_t v[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (x0 + 256 * u < nv) v[u] = q[x0 + 256 * u];
+      for (int u = 0; u < 4; ++u)
+        if (x0 + 256 * u < nv) v[u] = q[x0 + 256 * u];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const size_t x = x0 + 256 * u;
-          if (x < nv) {
-            const size_t G = x >> 1;
-            const size_t o = 2 * G - (G & 63) + 64 * (x & 1);  // (2b + h) * 64 + lane
-            __builtin_nontemporal_store(widen(v[u].x, v[u].y), p + o);
-          }
+      for (int u = 0; u < 4; ++u) {
+        const size_t x = x0 + 256 * u;
+        if (x < nv) {
+          const size_t G = x >> 1;
+          const size_t o = 2 * G - (G & 63) + 64 * (x & 1);  // (2b + h) * 64 + lane
+          __builtin_nontemporal_store(widen(v[u].x, v[u].y), p + o);
         }
-      }
-    } else {
-      const v2i_t* q = reinterpret_cast<const v2i_t*>(H16 + (size_t)(ks0 - chunk_c) * per);
-      for (size_t x0 = (size_t)blockIdx.x * 1024 + threadIdx.x; x0 < nv; x0 += step) {  // 4 loads in flight
-        v2i_t v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (x0 + 256 * u < nv) v[u] = q[x0 + 256 * u];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (x0 + 256 * u < nv) __builtin_nontemporal_store(widen(v[u].x, v[u].y), p + x0 + 256 * u);
       }
     }
     return;

@@ -493,12 +493,9 @@ void set_layout_mode(msa_plan& P, const msa_plan_desc* desc) {
   const char* fr = std::getenv("MSA_FUSED_REDUCE");
   const int64_t cells1 = (desc->m[0] + 1) * (desc->n[0] + 1);
   P.fused_reduce = P.flow2 && kalg != MSA_ALG_REF1 && cells1 < (int64_t(1) << 32) && !(fr && fr[0] == '0');
-  // rows per lane of the flow kernel (two-pass plans): 2 halves the inter-wave hand-offs per row
-  // (SW linear with H; the reference's Gotoh and SW affine with direction bytes; MSA_FLOW_GOT_R=1 /
-  // MSA_FLOW_AFF_R=1 keep one row for those two; read once per process)
-  static const int got_r = env_int("MSA_FLOW_GOT_R", 2) == 1 ? 1 : 2;
-  static const int aff_r = env_int("MSA_FLOW_AFF_R", 2) == 1 ? 1 : 2;
-  P.R = kalg == MSA_ALG_REF1 ? got_r : kalg == MSA_ALG_SWA ? aff_r : (desc->cells == MSA_OUT_H ? 2 : 1);
+  // rows per lane of the flow kernel: 2 in every two-pass plan (SW linear with H; the reference's Gotoh and
+  // SW affine with direction bytes), which halves the inter-wave hand-offs per row; 1 in score-only plans
+  P.R = P.flow2 ? 2 : 1;
 }
 
 // ---- step 4: where every pair's stripes, cells and column codes go ----------------------------------

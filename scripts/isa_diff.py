@@ -1,5 +1,5 @@
 """Do two builds of libmsa.so hold the same gfx950 code?  Compares, function by function, the disassembled
-(mnemonic, operands) streams as they are, and kernel by kernel the code-object metadata rows (registers,
+(mnemonic, operands) streams (normalise: all but where the function sits), and kernel by kernel the code-object metadata rows (registers,
 scratch, spills, LDS, arguments).  Exit status 1 if anything differs.
 
     python scripts/isa_diff.py old/libmsa.so new/libmsa.so
@@ -12,8 +12,22 @@ from kmeta import kernels  # noqa: E402
 from waitloops import disassemble, functions  # noqa: E402
 
 
+def normalise(insts):
+    """A function's (mnemonic, operands) stream without what only says where it sits in the file: the s_nop padding
+    behind its last s_endpgm / s_setpc_b64 / s_branch, and the pc-relative literals of the s_add_u32, s_addc_u32
+    behind an s_getpc_b64 (the address of a called function)."""
+    out = [(mn, ops) for _, mn, ops in insts]
+    ends = [i for i, (mn, _) in enumerate(out) if mn in ("s_endpgm", "s_setpc_b64", "s_branch")]
+    if ends and all(mn == "s_nop" for mn, _ in out[ends[-1] + 1:]):
+        del out[ends[-1] + 1:]
+    for i in range(len(out) - 2):
+        if [mn for mn, _ in out[i:i + 3]] == ["s_getpc_b64", "s_add_u32", "s_addc_u32"]:
+            out[i + 1:i + 3] = [(mn, ops.rsplit(",", 1)[0] + ", <pcrel> ") for mn, ops in out[i + 1:i + 3]]
+    return out
+
+
 def streams(so: Path):
-    return {name: [(mn, ops) for _, mn, ops in insts] for name, insts in functions(disassemble(so)).items()}
+    return {name: normalise(insts) for name, insts in functions(disassemble(so)).items()}
 
 
 def rows(so: Path):

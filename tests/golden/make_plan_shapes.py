@@ -25,8 +25,7 @@ sys.path.insert(0, str(HERE.parent.parent))
 OUT = HERE / "plan_shapes.json"
 
 # diagnostic variables libmsa reads once per process: a recorded shape only holds with none of them set
-ONCE_PER_PROCESS = ("MSA_FLOW_GOT_R", "MSA_FLOW_AFF_R", "MSA_FLOW_LDS_MIN", "MSA_BAND_WARM", "MSA_BAND_CHUNK",
-                    "MSA_BAND_H16")
+ONCE_PER_PROCESS = ("MSA_FLOW_LDS_MIN", "MSA_BAND_WARM", "MSA_BAND_CHUNK", "MSA_BAND_H16")
 
 SW_LINEAR, SW_AFFINE, NW_BANDED, REF_GOTOH, PARTIAL = 0, 1, 2, 3, 4
 NONE, H, DIR, TAB = 0, 1, 2, 3

@@ -762,8 +762,8 @@ def test_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring):
     check_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring)
 
 
-def check_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring, rows=2, pair=None, to_dev=None):
-    """test_sw_affine_flow_dir_bytes' comparison for a flow plan of `rows` rows per lane; returns that plan.
+def check_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring, pair=None, to_dev=None):
+    """test_sw_affine_flow_dir_bytes' comparison; returns the flow plan.
     pair / to_dev: another input (A, B) of m rows and how to bring it to the device as codes (default: the
     test's own ACGT input)."""
     import torch
@@ -793,7 +793,7 @@ def check_sw_affine_flow_dir_bytes(dev, LB, m, n, scoring, rows=2, pair=None, to
         out.append((pl.deskew_dir(D.cpu().numpy(), 0, pl.stripe_meta()), r["score"], tuple(r["end"]), info["mode"],
                     pl.geom[0].rows_per_lane, pl))
     (d1, s1, e1, mode1, r1, flow_plan), (d0, s0, e0, _, _, _) = out
-    assert mode1 == "flow" and r1 == rows  # (default: the flow kernel's two-rows-per-lane layout)
+    assert mode1 == "flow" and r1 == 2  # (the flow kernel's two-rows-per-lane layout)
     assert (s1, e1) == (s0, e0)
     assert np.array_equal(d1[1:, 1:], d0[1:, 1:])
     return flow_plan

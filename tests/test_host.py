@@ -468,7 +468,7 @@ def test_wait_loops_are_wave_uniform():
     with_loops = {k: v for k, v in res.items() if v["loops"]}
     for prefix in ("_ZN3msa11flow_kernel", "_ZN3msa11band_kernel", "_ZN3msa13stripe_kernel",
                    "_ZN3msa12cflow_kernel",
-                   "_ZN3msa10fill_block", "_ZN3msa14fill_block_aff", "_ZN3msa14fill_block_got"):
+                   "_ZN3msa10fill_block", "_ZN3msa15fill_block_aff2", "_ZN3msa15fill_block_got2"):
         assert any(k.startswith(prefix) for k in with_loops), f"no wait loop found in {prefix}*"
     bad = {k: v["bad"] for k, v in with_loops.items() if v["bad"]}
     assert not bad, f"exec-mask controlled wait loops: {bad}"
@@ -524,6 +524,37 @@ def test_asm_hazard_detector():
     assert [b[0] for b in H.hazards(cx)] == ["dpp_exec"]
 
 
+def test_isa_diff_ignores_only_where_a_function_sits():
+    """scripts/isa_diff.py's comparison on hand-written code.  Two things depend on a function's place in the
+    code object and not on its code, and compare equal: the pc-relative literal of the s_add_u32 / s_addc_u32
+    behind an s_getpc_b64 (a call) and the s_nop padding behind the last instruction.  A literal anywhere
+    else and an s_nop inside the body are differences."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("isa_diff", ROOT / "scripts" / "isa_diff.py")
+    D = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(D)
+
+    def fn(lit="0xffc3f1d0", hi="-1", other="0x12345", mid=(), pad=0, end=("s_setpc_b64", "s[30:31] ")):
+        body = [("s_getpc_b64", "s[0:1] "), ("s_add_u32", f"s0, s0, {lit} "), ("s_addc_u32", f"s1, s1, {hi} "),
+                ("s_add_u32", f"s2, s2, {other} "), *mid, ("s_swappc_b64", "s[30:31], s[0:1] "),
+                ("v_mov_b32_e32", "v0, s36 "), end] + [("s_nop", "0 ")] * pad
+        return D.normalise([(0x100 + 4 * k, mn, o) for k, (mn, o) in enumerate(body)])
+
+    assert fn() == fn(lit="0xffc5f1d4") == fn(lit="0x1f1d4", hi="0")
+    assert fn() == fn(pad=4)
+    for end in (("s_endpgm", " "), ("s_branch", "65530 <f+0x8>")):
+        assert fn(end=end) == fn(end=end, pad=3) != fn()
+    assert len(fn(pad=4)) == 7 and fn()[1] == ("s_add_u32", "s0, s0, <pcrel> ")
+    assert fn() != fn(other="0x12346")                                    # a literal, but not a call's
+    assert fn() != fn(mid=(("s_nop", "0 "),))                             # padding, but inside the body
+    assert fn(pad=2) != fn(mid=(("s_nop", "0 "),), pad=1)
+    assert fn(mid=(("s_nop", "0 "),)) != fn(mid=(("s_nop", "1 "),))
+    # an s_add_u32 with no s_getpc_b64 in front of it keeps its literal
+    plain = [(0x100, "s_add_u32", "s0, s0, 0x10 "), (0x104, "s_addc_u32", "s1, s1, 0 "), (0x108, "s_endpgm", " ")]
+    assert D.normalise(plain) == [(mn, o) for _, mn, o in plain]
+
+
 def test_asm_hazards_have_their_wait_states():
     """Every kernel and device function in libmsa.so's gfx950 code object gives each software-managed
     hazard its wait states on every control-flow path: VALU-write -> DPP-read (2), VALU EXEC write -> DPP
@@ -536,7 +567,7 @@ def test_asm_hazards_have_their_wait_states():
         pytest.skip("libmsa.so not built")
     res = H.scan(so)
     for prefix in ("_ZN3msa11flow_kernel", "_ZN3msa11band_kernel", "_ZN3msa13stripe_kernel",
-                   "_ZN3msa12cflow_kernel", "_ZN3msa14fill_block_aff", "_ZN3msa14fill_block_got"):
+                   "_ZN3msa12cflow_kernel", "_ZN3msa15fill_block_aff2", "_ZN3msa15fill_block_got2"):
         assert any(k.startswith(prefix) and v[0].get("dpp_vgpr") for k, v in res.items()), f"no DPP in {prefix}*"
     assert any(v[0].get("m0_lds") for k, v in res.items() if "traceback_kernel" in k), "no LDS-DMA in the walk"
     bad = {k: v[1][:3] for k, v in res.items() if v[1]}
