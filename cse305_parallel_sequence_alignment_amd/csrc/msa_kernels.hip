@@ -1822,9 +1822,11 @@ __global__ __launch_bounds__(256) void chunk_add_kernel(int32_t* H, const int16_
   }
 }
 
-__global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* pairs, const msa_stripe_meta* meta,
+__global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* pairs, msa_stripe_meta* meta,
                                                          int n_pairs, int rule, PairResult* out) {
   // rule: the algorithm's msa_result (msa_alg.h)
+  // has_fin is this run's alone: the stripe of row m sets it, this kernel -- the last of every run that reads it --
+  // reports it as the pair's status and clears it for the plan's next run (no launch of its own)
   // one wave per pair: lanes stride over the pair's stripes (a serial loop of
   // dependent meta loads took ~27 us for a 157-stripe pair)
   const int p = blockIdx.x;
@@ -1915,7 +1917,10 @@ __global__ __launch_bounds__(64) void reduce_pairs_kernel(const msa_pair_desc* p
       r.end_j = empty ? 0 : bj;
     }
   }
-  if (lane == 0) out[p] = r;
+  if (lane == 0) {
+    out[p] = r;  // (r.status holds the loaded has_fin: the store below cannot pass that load)
+    if (rule != RES_BEST) meta[pd.stripe0 + S - 1].has_fin = 0;
+  }
 }
 
 // ---------------------------------------------------------------------------

@@ -291,7 +291,8 @@ typedef struct msa_plan_desc {
 
 typedef struct msa_pair_result {
   int32_t score;
-  int32_t status;
+  int32_t status;        /* 0, or -1: this run's row-m stripe left no final state (every run of a plan, not only
+                            its first: the flag is cleared once it has been reported) */
   int64_t end_i, end_j;  /* SW: end cell; Gotoh: (m, n); MSA_NW_FIT: (m, first column of row m's maximum);
                             MSA_NW_OVERLAP: the end cell on row m or column n, or (m, 0) with score 0;
                             MSA_NW_EXTEND: the first maximum over the interior, or (0, 0) with score 0 */
