@@ -17,8 +17,12 @@
 // it reads the result of the one before it or not (mbench/mb_chain.hip,
 // DESIGN.md section 8), so an s_nop in front of a DPP costs like a v_max3.  The
 // two-row G-space step is therefore one hand-ordered block (fl_step2_gs: add,
-// add, DPP, v_max3, v_max3 -- the adds are the DPP's wait states), and nothing
-// else sits on the chain:
+// add, DPP, v_max3, v_max3 -- the adds are the DPP's wait states).  For the same
+// reason a stripe's steady phases run as unrolled groups of 16 whose ring slot is
+// a compile-time constant (run_gphase, plans with a pass 2): the generic SW-linear
+// phase issues ~155 instructions from one hand-off to the next, 88 of them the 16
+// steps and their 8 v_perm, a group phase ~129 -- the per-phase table is in
+// DESIGN.md section 5.  Nothing else sits on the chain:
 //   * waves 0..W-1 compute (one per SIMD), wave W io-in, wave W+1 io-out;
 //   * no s_barrier: a producer's lane 63 writes each 16-column block of its
 //     bottom row to an LDS ring and then bumps its phase counter; the consumer
@@ -192,6 +196,16 @@ __device__ __forceinline__ void ds_reread_b128x4(unsigned a, fl_v4i (&in)[4]) {
       : "v"(a)
       : "memory");
 }
+// the groups' slow path: a block re-read into 16 single registers (two statements: 30 operands at most)
+__device__ __forceinline__ void ds_reread_b32x8(unsigned a, int* e) {
+  asm volatile(
+      "ds_read_b32 %0, %8\n\tds_read_b32 %1, %8 offset:4\n\tds_read_b32 %2, %8 offset:8\n\t"
+      "ds_read_b32 %3, %8 offset:12\n\tds_read_b32 %4, %8 offset:16\n\tds_read_b32 %5, %8 offset:20\n\t"
+      "ds_read_b32 %6, %8 offset:24\n\tds_read_b32 %7, %8 offset:28\n\ts_waitcnt lgkmcnt(0)"
+      : "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]), "+v"(e[4]), "+v"(e[5]), "+v"(e[6]), "+v"(e[7])
+      : "v"(a)
+      : "memory");
+}
 template <int N = 0>
 __device__ __forceinline__ void lgkm_wait(int& v) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "i"(N) : "memory"); }
 // A stripe's end: every phase already waited for its prefetched inputs, so only the hand-off writes
@@ -230,8 +244,50 @@ __device__ __forceinline__ void ds_handoff_tid(unsigned long long m63, unsigned 
         [pv] "v"(pv)
       : "memory");
 }
-
-
+// The same hand-off for the steady-state groups of the SW-linear chain wave.  A compute wave's control flow is
+// wave-uniform from the kernel's entry (its branches are scalar), so its exec mask is all ones: it is
+// restored with the constant and not saved first -- one SALU less per phase.
+// The phase counter is a VGPR the statement itself advances (pv + 1 is written): not rebuilt from q per phase.
+// The add stands where ds_handoff_tid has its s_nop 0, behind the exec write: lane 63's counter is the one written.
+__device__ __forceinline__ void ds_handoff_tid_full(unsigned long long m63, unsigned m0v, const int (&x)[16],
+                                                    unsigned pa, int& pv) {
+  asm volatile(
+      "s_mov_b64 exec, %[m]\n\tv_add_u32 %[pv], 1, %[pv]\n\t"
+      "ds_write_addtid_b32 %[x0] offset:0\n\tds_write_addtid_b32 %[x1] offset:4\n\t"
+      "ds_write_addtid_b32 %[x2] offset:8\n\tds_write_addtid_b32 %[x3] offset:12\n\t"
+      "ds_write_addtid_b32 %[x4] offset:16\n\tds_write_addtid_b32 %[x5] offset:20\n\t"
+      "ds_write_addtid_b32 %[x6] offset:24\n\tds_write_addtid_b32 %[x7] offset:28\n\t"
+      "ds_write_addtid_b32 %[x8] offset:32\n\tds_write_addtid_b32 %[x9] offset:36\n\t"
+      "ds_write_addtid_b32 %[x10] offset:40\n\tds_write_addtid_b32 %[x11] offset:44\n\t"
+      "ds_write_addtid_b32 %[x12] offset:48\n\tds_write_addtid_b32 %[x13] offset:52\n\t"
+      "ds_write_addtid_b32 %[x14] offset:56\n\tds_write_addtid_b32 %[x15] offset:60\n\t"
+      "ds_write_b32 %[pa], %[pv]\n\t"
+      "s_mov_b64 exec, -1\n\ts_nop 4"
+      : [pv] "+v"(pv)
+      : [m] "s"(m63), "{m0}"(m0v), [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]), [x4] "v"(x[4]),
+        [x5] "v"(x[5]), [x6] "v"(x[6]), [x7] "v"(x[7]), [x8] "v"(x[8]), [x9] "v"(x[9]), [x10] "v"(x[10]),
+        [x11] "v"(x[11]), [x12] "v"(x[12]), [x13] "v"(x[13]), [x14] "v"(x[14]), [x15] "v"(x[15]), [pa] "v"(pa)
+      : "memory");
+}
+// A group phase's one wait, behind the hand-off: the prefetched inputs and the counter read (older than
+// they) have landed, and the counter comes back wave-uniform -- one statement (apart, the compiler pads one
+// s_nop between a wait that names the VGPR and the v_readfirstlane that reads it)
+template <int N>
+__device__ __forceinline__ int lgkm_wait_v_uni(fl_v4i (&in)[4], fl_v4u& cw, int v) {
+  int s;
+  asm volatile("s_waitcnt lgkmcnt(%7)\n\tv_readfirstlane_b32 %5, %6"
+               : "+v"(in[0]), "+v"(in[1]), "+v"(in[2]), "+v"(in[3]), "+v"(cw), "=s"(s)
+               : "v"(v), "i"(N)
+               : "memory");
+  return s;
+}
+// 16 code bytes at a + 8 O0 and a + 8 O1 (a group phase's code read: one address register per group)
+template <int O0, int O1>
+__device__ __forceinline__ fl_v4u ds_read2_b64_at(unsigned a) {
+  fl_v4u v;
+  asm volatile("ds_read2_b64 %0, %1 offset0:%2 offset1:%3" : "=v"(v) : "v"(a), "i"(O0), "i"(O1) : "memory");
+  return v;
+}
 
 
 // Affine hand-off: lane 63 alone writes its 16 Z and 16 F~ of the phase as 8 b128 writes
@@ -356,6 +412,36 @@ __device__ __forceinline__ void fl_step2_gs(int kk, int in, unsigned sw, unsigne
   U = in;
   X = h1;
   X2 = h2;
+}
+// The four steps of one profile word as one block (the steady-state groups).  Between two asm statements of
+// which the second reads a register the first wrote, the compiler pads with an s_nop 0 unless another
+// instruction stands there (it assumes the first may have written part of a register); the generic phase
+// has its bookkeeping between its steps, a group phase has none left, and eight paddings per phase came
+// back.  Inside one statement nothing is padded.  Row 1 runs in place (X), row 2's values are the hand-off.
+//   in: U, X, X2 as above, in[0..3] the ring values;  out: X, X2, U, h2[k] = row 2 of step k
+#define FL_S2X4(SEL, U_, X2_, IN_, H2_)                                                                     \
+  "v_add_u32_sdwa %[a], " U_ ", sext(%[sw]) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD "            \
+  "src1_sel:BYTE_" #SEL "\n\t"                                                                              \
+  "v_add_u32_sdwa %[b], %[x], sext(%[swb]) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD "             \
+  "src1_sel:BYTE_" #SEL "\n\t"                                                                              \
+  "v_mov_b32_dpp " IN_ ", " X2_ " wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"                                \
+  "v_max3_i32 %[x], %[a], " IN_ ", %[x]\n\t"                                                                \
+  "v_max3_i32 " H2_ ", %[b], %[x], " X2_
+__device__ __forceinline__ void fl_step2x4_gs(int& i0, int& i1, int& i2, int& i3, unsigned sw, unsigned swb, int& X,
+                                              int& X2, int& U, int (&h2)[4]) {
+  int a, b;
+  // (volatile: the statement keeps its place among the DS statements and their waits, which are volatile --
+  // free to move, the last block of a phase was scheduled behind the wait for the counter read issued just
+  // in front of it, and the wave sat out the LDS latency in every phase)
+  asm volatile(FL_S2X4(0, "%[u]", "%[x2]", "%[i0]", "%[h0]") "\n\t"
+      FL_S2X4(1, "%[i0]", "%[h0]", "%[i1]", "%[h1]") "\n\t"
+      FL_S2X4(2, "%[i1]", "%[h1]", "%[i2]", "%[h2]") "\n\t"
+      FL_S2X4(3, "%[i2]", "%[h2]", "%[i3]", "%[h3]")
+      : [a] "=&v"(a), [b] "=&v"(b), [x] "+v"(X), [i0] "+v"(i0), [i1] "+v"(i1), [i2] "+v"(i2), [i3] "+v"(i3),
+        [h0] "=&v"(h2[0]), [h1] "=&v"(h2[1]), [h2] "=&v"(h2[2]), [h3] "=&v"(h2[3])
+      : [u] "v"(U), [x2] "v"(X2), [sw] "v"(sw), [swb] "v"(swb));
+  U = i3;
+  X2 = h2[3];
 }
 
 // FLOOR: scores may be negative (zero floor, X-space); otherwise G-space.  Affine SW: the
@@ -1315,10 +1401,185 @@ __global__ __launch_bounds__((FL_W + 2) * 64) __attribute__((amdgpu_waves_per_eu
       using F_ = std::false_type;
       // phases q < qa prefetch a block q+1 <= Bin: no masking code
       const int qa = max(0, min(P, Bin));
+
+      // ---- steady-state groups: 16 phases q0 .. q0 + 15, q0 % 16 == 0, the phase's index J in the group (=
+      // its slot in the 16-block rings) a compile-time constant.  A stripe runs a group only where every
+      // phase of it is a plain one: q0 >= 16 (every phase hands a block off: q - dq >= 0), q0 + 16 <= qa (no
+      // masked prefetch) and whole-row LDS code copies (linear addresses).  The last stripe runs them too: it
+      // ends the chain, and at the generic phase's length it would set the pace that its producers' groups
+      // had just raised.  Its blocks go to its own out ring, which nothing reads (the next wave has no
+      // stripe and io-out no link there), with dq taken as 4 and the consumer check switched off -- the same
+      // code as every other stripe's, instead of run_phase's 64-byte sink, which a group's constant slot
+      // offsets would overrun.
+      // What run_phase derives from q per phase is then a constant or carried:
+      //   * ring reads: immediate offsets ((J + 1) & 15) * 64 + 16 u from the pinned ring base;
+      //   * code read: immediate offsets 2 (J + 1), 2 (J + 1) + 1 (8-byte units) from g_ca = the address of
+      //     phase q0's codes, advanced by 256 once per group;
+      //   * write slot (q - dq) & 15 = (J - dq) & 15: dq is 3 or 4, so M0 = g_m0 + 64 ((J - 4) & 15) for
+      //     every J but 3, where the slot is 0 (dq 3) or 15 (dq 4): g_m0j3.  One s_add or s_mov per phase;
+      //   * hand-off: always (no dummy sink), exec restored with the constant (ds_handoff_tid_full);
+      //   * consumers: checked every fourth phase (J % 4 == 1: not the phases that store SNAP) for the furthest
+      //     of the next four blocks, q + 3 - dq: the out ring looks three blocks shorter (13 of 16; a consumer
+      //     runs ~dq phases behind).  J = 13 covers the next group's J = 0; phase 16, the first group's, writes
+      //     block 16 - dq < 15 and needs no check;
+      //   * SNAP: a segment can start only at J = 0, or at J = 8 when segments are 8 phases (ps_shift 3);
+      //     the stores go through a carried pointer;
+      //   * the producer check stays per phase, against q0 + dq_in + J + 1, with run_phase's slow path.
+      //   * the four steps of a profile word are one asm statement (fl_step2x4_gs) on 16 single ring-value
+      //     registers, and the phase's one wait with the counter's readfirstlane another (lgkm_wait_v_uni).
+      // Everything else (first 16 phases, tail, masked phases, ring codes) runs run_phase.
+      unsigned g_ca = 0, g_m0 = 0, g_m0j3 = 0;
+      const int g_dq = has_out ? dq : 4;  // (the last stripe: any of the two)
+      unsigned v_ring_in = a_ring_in, v_prog_in = a_prog_in, v_prog_me = a_prog_me;
+      int g_pv = 0;
+      char* g_snap = nullptr;  // the stripe's SNAP area (wave-uniform) and the lane's byte offset of the next segment
+      unsigned g_snapoff = 0;  // (< 16 n: a segment is 2 KiB and at least 128 columns)
+      unsigned g_ephi = ep;
+      const int ps_shift = a.ps_shift;
+      const unsigned g_snapstep = ps_shift == 3 ? 2u * 256u * 8u : 256u * 8u;  // a group's segments (8-phase: two)
+      auto run_gphase = [&](auto J_, const int q0, fl_v4i (&IN)[4], fl_v4u& CW, fl_v4i (&INn)[4], fl_v4u& CWn)
+          __attribute__((always_inline)) {
+        constexpr int J = decltype(J_)::value;
+        constexpr int JN = (J + 1) & (FL_RINGB - 1);
+        static_assert(FL_PF % 4 == 0, "the prefetch stands between two four-step blocks");
+        const int q = q0 + J;
+        // the block as 16 single registers: the steps write them in place, and the slow path's re-read joins
+        // the fast path on them (joined on the b128 tuples, three of a tuple's four values were copied out
+        // in front of every four-step block)
+        int in[16];
+#pragma unroll
+        for (int t = 0; t < 16; ++t) in[t] = IN[t >> 2][t & 3];
+        if (__builtin_expect((MSA_ABL & 48) == 0 && pubv < q0 + dq_in + (J + 1), 0)) {
+#ifdef MSA_STAMPS
+          ++nslow;
+#endif
+          wait_flag(a_prog_in, pubv, q + 1 + dq_in);
+          const unsigned ra = a_ring_in + (unsigned)((q & (FL_RINGB - 1)) * 64);
+          ds_reread_b32x8(ra, in);
+          ds_reread_b32x8(ra + 32u, in + 8);
+        }
+        if constexpr (SAVE && (MSA_ABL & 2) == 0 && (J == 0 || J == 8)) {
+          // (J = 8: the segment behind J = 0's, 2 KiB on, in the stores' immediate offsets; J = 0 advances)
+          if (J == 0 ? (q0 & ((1 << ps_shift) - 1)) == 0 : ps_shift == 3) {
+            unsigned long long* sp = reinterpret_cast<unsigned long long*>(g_snap + g_snapoff) + (J == 8 ? -256 : 0);
+            gstore(sp, ((unsigned long long)g_ephi << 32) | (unsigned)X);
+            gstore(sp + 64, ((unsigned long long)g_ephi << 32) | (unsigned)U);
+            gstore(sp + 128, ((unsigned long long)g_ephi << 32) | (unsigned)X2);
+            if (J == 0) g_snapoff += g_snapstep;
+          }
+        }
+        int hv[16];
+        int xo[16];
+        int pubn = 0;
+        const int negct = negct0 - 16 * g * q;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (4 * u == FL_PF) {  // prefetch phase q+1 (6 DS ops), in front of the block's two v_perm
+            pubn = ds_read_b32(v_prog_in);
+            INn[0] = ds_read_b128<JN * 64>(v_ring_in);
+            INn[1] = ds_read_b128<JN * 64 + 16>(v_ring_in);
+            INn[2] = ds_read_b128<JN * 64 + 32>(v_ring_in);
+            INn[3] = ds_read_b128<JN * 64 + 48>(v_ring_in);
+            CWn = ds_read2_b64_at<2 * (J + 1), 2 * (J + 1) + 1>(g_ca);
+          }
+          const unsigned s4 = __builtin_amdgcn_perm(phi, plo, CW[u]);
+          const unsigned s4b = (R == 2) ? __builtin_amdgcn_perm(phi2, plo2, CW[u]) : 0u;
+          if constexpr (R == 2 && GS) {
+            int h2[4];
+            fl_step2x4_gs(in[4 * u], in[4 * u + 1], in[4 * u + 2], in[4 * u + 3], s4, s4b, X, X2, U, h2);
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) xo[4 * u + kk] = h2[kk];
+            continue;
+          }
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) {
+            const int kx = 4 * u + kk;
+            const int s = ((int)(s4 << (24 - 8 * kk))) >> 24;
+            if constexpr (R == 1) {
+              const int h = fl_step<GS, FLOOR>(in[kx], s, X, U, g);
+              xo[kx] = X;
+              hv[kx] = GS ? h + negct + gk[kx] : h;
+            } else if constexpr (GS) {
+              fl_step2_gs(kk, in[kx], s4, s4b, X, X2, U);
+              xo[kx] = X2;
+            } else {
+              const int sb = ((int)(s4b << (24 - 8 * kk))) >> 24;
+              const int up = dpp_shr1(in[kx], X2);
+              int h1 = imax3(U + s, up, X);
+              if constexpr (FLOOR) h1 = imax(h1, 0);
+              asm("" : "+v"(h1));
+              U = up;
+              const int xprev = X;
+              X = GS ? h1 : h1 - g;
+              int h2 = imax3(xprev + sb, X, X2);
+              if constexpr (FLOOR) h2 = imax(h2, 0);
+              asm("" : "+v"(h2));
+              X2 = GS ? h2 : h2 - g;
+              xo[kx] = X2;
+            }
+          }
+        }
+        if constexpr (BEST) {
+#pragma unroll
+          for (int kx = 0; kx < 16; kx += 2) best = imax3(best, hv[kx], hv[kx + 1]);
+        }
+        if constexpr ((J & 3) == 1) {
+          const int cneed = q0 - g_dq + (J + 3 - (FL_RINGB - 1));
+          if (__builtin_expect((MSA_ABL & 80) == 0 && consv < cneed, 0)) refresh_cons(cneed);
+        }
+        ds_handoff_tid_full(m63, J == 3 ? g_m0j3 : g_m0 + 64u * (unsigned)((J - 4) & (FL_RINGB - 1)), xo, v_prog_me,
+                            g_pv);
+        pubv = lgkm_wait_v_uni<5>(INn, CWn, pubn);  // phase q+1's inputs and the counter (the writes may fly)
+      };
+      auto run_group = [&](const int q0) __attribute__((always_inline)) {
+#define FL_GPH(J) std::integral_constant<int, J> {}
+        run_gphase(FL_GPH(0), q0, INa, CWa, INb, CWb);
+        run_gphase(FL_GPH(1), q0, INb, CWb, INa, CWa);
+        run_gphase(FL_GPH(2), q0, INa, CWa, INb, CWb);
+        run_gphase(FL_GPH(3), q0, INb, CWb, INa, CWa);
+        run_gphase(FL_GPH(4), q0, INa, CWa, INb, CWb);
+        run_gphase(FL_GPH(5), q0, INb, CWb, INa, CWa);
+        run_gphase(FL_GPH(6), q0, INa, CWa, INb, CWb);
+        run_gphase(FL_GPH(7), q0, INb, CWb, INa, CWa);
+        run_gphase(FL_GPH(8), q0, INa, CWa, INb, CWb);
+        run_gphase(FL_GPH(9), q0, INb, CWb, INa, CWa);
+        run_gphase(FL_GPH(10), q0, INa, CWa, INb, CWb);
+        run_gphase(FL_GPH(11), q0, INb, CWb, INa, CWa);
+        run_gphase(FL_GPH(12), q0, INa, CWa, INb, CWb);
+        run_gphase(FL_GPH(13), q0, INb, CWb, INa, CWa);
+        run_gphase(FL_GPH(14), q0, INa, CWa, INb, CWb);
+        run_gphase(FL_GPH(15), q0, INb, CWb, INa, CWa);
+#undef FL_GPH
+        g_ca += 16u * FL_RINGB;
+      };
+      static_assert(FL_RINGB == 16, "a group is one turn of the rings");
+      // SAVE only: the score-only kernels (R = 1, BEST) went from 121 / 122 VGPRs to 256 with 97 / 81 spilled
+      // with the group code (16 more phase bodies, each with its 16 best-cell candidates), so they keep
+      // run_phase alone
+      const bool grp = SAVE && cwhole && ps_shift >= 3 && (g_dq == 3 || g_dq == 4);
+      const int qg = grp ? (qa & ~(FL_RINGB - 1)) : 0;  // groups cover phases [16, qg)
+
       int q = 0;
-      for (; q + 1 < qa; q += 2) {
-        run_phase(q, INa, CWa, INb, CWb, F_{});
-        run_phase(q + 1, INb, CWb, INa, CWa, F_{});
+      for (int qstop = (qg >= 2 * FL_RINGB) ? FL_RINGB : qa;;) {
+        for (; q + 1 < qstop; q += 2) {
+          run_phase(q, INa, CWa, INb, CWb, F_{});
+          run_phase(q + 1, INb, CWb, INa, CWa, F_{});
+        }
+        if (qstop == qa) break;
+        if constexpr (SAVE) {
+        // (q == 16 here: an even phase, its inputs in INa as at every group's start)
+        g_ca = a_cring + y_code + 16u * (unsigned)q;
+        g_m0 = a_ring_out - 252u + 64u * (unsigned)(4 - g_dq);
+        g_m0j3 = a_ring_out - 252u + (g_dq == 3 ? 0u : 64u * (FL_RINGB - 1));
+        g_pv = q;
+        // the first segment that starts at a phase >= q
+        g_snap = reinterpret_cast<char*>(a.snap + (size_t)k * a.nseg * 256);
+        g_snapoff = (unsigned)(((q + (1 << ps_shift) - 1) >> ps_shift) * 256 + lane) * 8u;
+        asm volatile("" : "+v"(v_ring_in), "+v"(v_prog_in), "+v"(v_prog_me), "+v"(g_ephi));
+        if (!has_out) consv = 1 << 30;  // (no consumer; run_phase never looks at it in the last stripe)
+        for (; q < qg; q += FL_RINGB) run_group(q);
+        }
+        qstop = qa;
       }
       if (q < qa) {
         run_phase(q, INa, CWa, INb, CWb, F_{});
