@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from flow_dir_reference import gotoh_tags as _gotoh_tags  # (the tag byte of every cell from the oracle's tables)
 
 pytestmark = pytest.mark.gpu
 
@@ -932,19 +933,6 @@ def check_gotoh_flow_dir_bytes(dev, LB, gh, m, n, pair=None, to_dev=None):
     assert (s1, f1) == (s0, f0)
     assert np.array_equal(d1[1:, 1:] & 63, d0[1:, 1:] & 63)
     return flow_plan
-
-
-def _gotoh_tags(T1, T2, T3, g, h):
-    """The REF1 tag byte of every cell from the reference's double tables: bits 0-1 / 2-3 / 4-5 = 4 - the table
-    find_alignment's T1 / T2 / T3 branch picks (the first of T1, T2, T3 whose candidate is the maximum,
-    subproblem_alignment.cpp:150-171)."""
-    def first(c):
-        return 4 - np.argmax(np.stack(c), axis=0).astype(np.uint8) - 1
-
-    t1 = first([T1[:-1, :-1], T2[:-1, :-1], T3[:-1, :-1]])
-    t2 = first([T1[1:, :-1] - g - h, T2[1:, :-1] - g, T3[1:, :-1] - g - h])
-    t3 = first([T1[:-1, 1:] - g - h, T2[:-1, 1:] - g - h, T3[:-1, 1:] - g])
-    return t1 | (t2 << 2) | (t3 << 4)
 
 
 @pytest.mark.parametrize("m,n", [(130, 45000), (300, 61000), (1000, 20100), (64, 9000)])

@@ -222,9 +222,10 @@ def test_null_sub_equals_affine_plan(oracle, dev, LB):
             assert alg == LB.SW_AFFINE or mode == "stripe"
             out.append((mode, tb["ops"], pl.deskew_dir(D.cpu().numpy(), 0, pl.stripe_meta())[1:, 1:] & 15))
     assert sum(mode == "stripe" for mode, _, _ in out) >= 3  # both scored plans and the affine batch plan
+    assert [mode for mode, _, _ in out].count("flow") == 1  # the single-pair affine plan
     for mode, ops, byte in out[1:]:
         assert ops == out[0][1]
-        assert mode != "stripe" or (byte == out[0][2]).all()  # the same kernel family: the same bytes
+        assert (byte == out[0][2]).all()  # all four planes, the flow kernel's too (test_gpu_flow_dir.py): the contract's
 
 
 # ---- 9. host entries and api -----------------------------------------------------------------------------------
