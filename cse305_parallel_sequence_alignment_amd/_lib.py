@@ -28,6 +28,8 @@ SW_LINEAR, SW_AFFINE, NW_BANDED, REF_GOTOH, PARTIAL, NW_ALIGN, NW_SCORED, NW_FIT
 SW_SCORED = 8
 NW_OVERLAP = 9
 NW_EXTEND = 10
+NW_EXTEND_BAND = 11
+SCORE_NONE = -(1 << 31)  # MSA_SCORE_NONE: no such score (a clipped banded extension's global score)
 CELLS_NONE, CELLS_H, CELLS_DIR, CELLS_TAB = 0, 1, 2, 3
 # msa_profile_align's modes
 PROFILE_LOCAL, PROFILE_GLOBAL, PROFILE_FIT = 0, 1, 2
@@ -153,6 +155,14 @@ def lib() -> C.CDLL:
     L.msa_extend_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, P, P, P, P, sz, P]
     L.msa_extend_align32.argtypes = L.msa_extend_align.argtypes
     L.msa_extend_align_batch32.argtypes = L.msa_extend_align_batch.argtypes
+    # ... inside a band: `band` after gap_extend; the clip rule on its own
+    L.msa_extend_align_banded.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, i64, C.POINTER(i32), P, C.POINTER(i32), P,
+                                          sz]
+    L.msa_extend_align_batch_banded.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, i64, P, P, P, P, sz,
+                                                P]
+    L.msa_extend_align_banded32.argtypes = L.msa_extend_align_banded.argtypes
+    L.msa_extend_align_batch_banded32.argtypes = L.msa_extend_align_batch_banded.argtypes
+    L.msa_extend_band_clip.argtypes = [i64, i64, i64, C.POINTER(i64), C.POINTER(i64)]
     # local alignment under a matrix: msa_sw_align's / msa_sw_align_batch's, (alphabet, n_sym, sub) for (match, mismatch)
     L.msa_sw_align_scored.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64),
                                       C.POINTER(i64), C.POINTER(i64), P, sz]
@@ -195,5 +205,7 @@ EXPORTED = [
     "msa_sw_align_scored", "msa_sw_align_batch_scored", "msa_sw_align_scored32", "msa_sw_align_batch_scored32",
     "msa_overlap_align", "msa_overlap_align_batch", "msa_overlap_align32", "msa_overlap_align_batch32",
     "msa_extend_align", "msa_extend_align_batch", "msa_extend_align32", "msa_extend_align_batch32",
+    "msa_extend_align_banded", "msa_extend_align_batch_banded", "msa_extend_align_banded32",
+    "msa_extend_align_batch_banded32", "msa_extend_band_clip",
     "msa_plan_create_profile", "msa_profile_align", "msa_profile_align_batch",
 ]

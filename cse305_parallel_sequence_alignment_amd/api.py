@@ -632,14 +632,16 @@ def overlap_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=
 
 
 def _extend_dict(score, end, gscore, traceback, cigar):
-    r = dict(score=int(score), a_end=int(end[0]), b_end=int(end[1]), global_score=int(gscore))
+    # (MSA_SCORE_NONE: a banded extension clipped the pair, so its fill never reached (m, n))
+    r = dict(score=int(score), a_end=int(end[0]), b_end=int(end[1]),
+             global_score=None if int(gscore) == LB.SCORE_NONE else int(gscore))
     if traceback:
         r["cigar"] = cigar
     return r
 
 
 def extend_align(A, B, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
-                 matrix=None, max_symbols=8):
+                 matrix=None, max_symbols=8, band=-1):
     """Extension alignment (build extension, msa_extend_align): the alignment starts at the first symbols of both
     sequences and may stop anywhere -> dict(score, a_end, b_end, global_score[, cigar]): the best-scoring pair of
     prefixes, ``A[:a_end]`` against ``B[:b_end]``.
@@ -650,29 +652,39 @@ def extend_align(A, B, gap_open=3, gap_extend=1, traceback=True, match=None, mis
     extension, score 0, ``a_end == b_end == 0`` and an empty CIGAR.  The CIGAR (start -> end, I consumes A, D consumes
     B) consumes exactly ``a_end`` and ``b_end``.  ``global_score`` is the end-to-end score of all of A against all of
     B -- nw_align's -- from the same fill: compare it with ``score`` to choose between clipping and aligning to the
-    end.  ``traceback=False`` gives the scores and the end cell only.  Scoring and ``max_symbols`` as for fit_align."""
+    end.  ``traceback=False`` gives the scores and the end cell only.  Scoring and ``max_symbols`` as for fit_align.
+
+    ``band`` >= 0 (msa_extend_align_banded): only cells with ``|i - j| <= band`` exist, so the work is bounded by the
+    lengths and the band -- about ``(2 band + 1) min(m, n)`` cells instead of ``m n`` -- and the extension is the best
+    one with at most ``band`` net indels at every point.  Rows past ``len(B) + band`` and columns past ``len(A) +
+    band`` hold no such cell: the call clips the longer sequence there, and ``global_score`` is then ``None`` (there
+    is no end-to-end alignment inside the band); otherwise it is nw_align's under the same band.  A negative band
+    other than the default -1 is an MsaError (ARG)."""
     A, B = _buf(A), _buf(B)
     alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
-    name = _entry("msa_extend_align", max_symbols)
+    name = _entry("msa_extend_align" if band == -1 else "msa_extend_align_banded", max_symbols)
+    bands = () if band == -1 else (int(band),)
     sc, gs = C.c_int32(), C.c_int32()
     end = np.zeros(2, dtype=np.int64)
     cap = 4 * (len(A) + len(B)) + 16
     cig = C.create_string_buffer(cap) if traceback else None
     LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open,
-                                     gap_extend, C.byref(sc), _i64p(end), C.byref(gs), cig,
+                                     gap_extend, *bands, C.byref(sc), _i64p(end), C.byref(gs), cig,
                                      cap if traceback else 0), name)
     return _extend_dict(sc.value, end, gs.value, traceback, cig.value.decode() if traceback else None)
 
 
 def extend_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
-                       matrix=None, max_symbols=8):
+                       matrix=None, max_symbols=8, band=-1):
     """A batch of extension alignments (msa_extend_align_batch) -> a list of extend_align()'s dicts.
 
     ``Bs``: a list as long as ``As``, or one bytes object every A is aligned against (uploaded once), exactly like
     nw_align_batch's; scoring as for extend_align, over one alphabet for the whole call (``match`` / ``mismatch``:
     the distinct symbols of all As, then all Bs, in first-seen order).  ``max_symbols=32``
-    (msa_extend_align_batch32): up to 32 symbols in the whole call."""
-    name = _entry("msa_extend_align_batch", max_symbols)
+    (msa_extend_align_batch32): up to 32 symbols in the whole call.  ``band`` >= 0 (msa_extend_align_batch_banded): one
+    band for every pair, each clipped to it on its own, as extend_align does."""
+    name = _entry("msa_extend_align_batch" if band == -1 else "msa_extend_align_batch_banded", max_symbols)
+    bands = () if band == -1 else (int(band),)
     if len(As) == 0:
         return []
     A, B, a_off, m, b_off, n = _batch_in(As, Bs)
@@ -685,7 +697,7 @@ def extend_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=N
     cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
     cig = C.create_string_buffer(cap) if traceback else None
     LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
-                                     alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend,
+                                     alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend, *bands,
                                      sc.ctypes.data_as(C.c_void_p), _i64p(end), gs.ctypes.data_as(C.c_void_p), cig, cap,
                                      _i64p(coff) if traceback else None), name)
     return [_extend_dict(sc[p], end[p], gs[p], traceback,

@@ -62,6 +62,13 @@ struct msa_alg_info {
   constexpr bool row_m() const { return result == RES_ROW_M || result == RES_ROW_M_COL; }
 };
 
+// An id that IS another id with a band: that row with |i - j| <= band accepted, and a 32-code twin of its own.
+constexpr msa_alg_info msa_alg_with_band(msa_alg_info t, int twin32) {
+  t.band = true;
+  t.twin32 = twin32;
+  return t;
+}
+
 // clang-format off
 constexpr msa_alg_info msa_alg_info_of(int alg) {
   constexpr msa_border RAMP = BORDER_RAMP, FREE = BORDER_FREE;
@@ -88,6 +95,10 @@ constexpr msa_alg_info msa_alg_info_of(int alg) {
     case MSA_ALG_NWP:   return {2, CELL_GOTOH,     RAMP, RAMP, RES_FINAL,     true,  true,  true,  false, TB_NW,      MSA_ALG_NONE};
     case MSA_ALG_FITP:  return {2, CELL_GOTOH,     FREE, RAMP, RES_ROW_M,     true,  true,  true,  false, TB_FIT,     MSA_ALG_NONE};
   }
+  // the derived ids: a banded extension (MSA_NW_EXTEND_BAND) is the extension row, with a band -- the banded global
+  // kernel's cell, borders, edge fix-ups and bytes under the extension's tracker, result rule and walker
+  if (alg == MSA_ALG_EXTB) return msa_alg_with_band(msa_alg_info_of(MSA_ALG_EXT), MSA_ALG_EXTB32);
+  if (alg == MSA_ALG_EXTB32) return msa_alg_with_band(msa_alg_info_of(MSA_ALG_EXT32), MSA_ALG_NONE);
   return {0, CELL_PART, RAMP, RAMP, RES_FINAL, false, false, false, false, TB_NONE, MSA_ALG_NONE};  // no such id
 }
 // clang-format on
@@ -110,7 +121,7 @@ constexpr int nc_of_cell(msa_cell c) {
 // every id: nc agrees with the cell; its twin, if any, is itself but for the code width (and has no twin of its own);
 // a profile row is a row of a plan-owned table over 5-bit codes
 constexpr bool rows_ok() {
-  for (int alg = 0; alg <= MSA_ALG_FITP; ++alg) {
+  for (int alg = 0; alg <= MSA_ALG_EXTB32; ++alg) {
     const msa_alg_info t = msa_alg_info_of(alg);
     if (t.nc != nc_of_cell(t.cell) || (t.wide && !t.table) || (t.profile && !t.wide)) return false;
     if (t.twin32 != MSA_ALG_NONE && (t.wide || diff(alg, t.twin32) != (WIDE | TWIN))) return false;
@@ -126,6 +137,13 @@ static_assert(msa_alg_info_of(MSA_ALG_NWA).twin32 == MSA_ALG_NWA32 && msa_alg_in
 static_assert(diff(MSA_ALG_OVL, MSA_ALG_FIT) == (LEFT | RESULT | TWIN), "OVL = FIT but for the left border and the result");
 // extension is the unbanded global kernel with another result (its walk starts there: TB_FIT, not TB_NW)
 static_assert(diff(MSA_ALG_EXT, MSA_ALG_NWA) == (RESULT | BAND | WALKER | TWIN), "EXT = unbanded NWA but for the result");
+// a banded extension is the extension with a band, and so the banded global kernel with the extension's result
+static_assert(diff(MSA_ALG_EXTB, MSA_ALG_EXT) == (BAND | TWIN) && diff(MSA_ALG_EXTB32, MSA_ALG_EXT32) == BAND,
+              "EXTB = EXT with a band");
+static_assert(diff(MSA_ALG_EXTB, MSA_ALG_NWA) == (RESULT | WALKER | TWIN) &&
+                  diff(MSA_ALG_EXTB32, MSA_ALG_NWA32) == (RESULT | WALKER),
+              "EXTB = banded NWA but for the result");
+static_assert(msa_alg_info_of(MSA_ALG_EXTB).twin32 == MSA_ALG_EXTB32, "EXTB32 is EXTB's twin");
 // scored local is SW affine under the plan's table
 static_assert(diff(MSA_ALG_SWS, MSA_ALG_SWA) == (TABLE | TWIN), "SWS = SWA under a table");
 // a profile id is a 32-code id whose 32 scores belong to the row of the matrix (the global one takes no band: its

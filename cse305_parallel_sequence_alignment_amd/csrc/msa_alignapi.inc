@@ -7,6 +7,7 @@
 //     msa_fit_align, msa_fit_align_batch, *32           all of A in a substring of B
 //     msa_overlap_align, msa_overlap_align_batch, *32   a suffix of one sequence against a prefix of the other
 //     msa_extend_align, msa_extend_align_batch, *32     the best pair of prefixes (anchored start, free end)
+//     msa_extend_align_banded, ..._batch_banded, *32    ... inside a band, each pair clipped to it
 //     msa_profile_align, msa_profile_align_batch        a position-specific profile: local, global, fit
 // The host encodes the inputs, runs plans (the flow / band kernels behind msa_plan_run) and the device walks
 // (traceback_kernel, msa_plan_traceback_batch), and turns a walk's O(m + n) ops into a CIGAR.
@@ -55,6 +56,8 @@ struct AlignSpec {
   bool wide = false;        // more than 8 symbols: 5-bit codes, tab is 32 x 32
   bool stop_is_beg = false; // the walk's stop cell (i, j) is the alignment's 0-based start, reported through
                             // AlignOut::beg where a walk ran (-1, -1 where none did); never a reason to walk
+  bool clip_to_band = false;  // a band >= 0 is required, and a pair with |m - n| > band is shortened to its in-band
+                              // prefixes (extend_band_clip) where a global kind answers MSA_ERR_ARG
   const int8_t* prof = nullptr;  // the rows are positions of this profile, a_len rows of 32 scores, not symbols of A
                                  // (msa_plan_create_profile; A is unused, tab too)
 };
@@ -123,6 +126,16 @@ AlignSpec spec_extend(const char* alphabet, size_t n_sym, const int8_t* sub, siz
   s.border = BORDER_GLOBAL;
   return s;
 }
+// ... inside a band: the banded global alignment's cells, footprint and border gap (a walk never leaves the band, so
+// the gap it stops at is inside it); the band's rule for the sizes is the clip
+AlignSpec spec_extend_band(const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym = 8) {
+  AlignSpec s = spec_extend(alphabet, n_sym, sub, max_sym);
+  s.alg_walk = s.alg_score = MSA_NW_EXTEND_BAND;
+  s.banded = true;
+  s.footprint = FOOT_BAND;
+  s.clip_to_band = true;
+  return s;
+}
 
 // A profile's positions against the caller's alphabet -- a symbol's code is its index --, local (the highest code is
 // the sentinel's: 31 symbols), global or fit (32).  prof32: the caller's m x n_sym scores padded to 32 columns (the
@@ -181,7 +194,8 @@ struct AlignOut {
   char* cigars;      // the CIGARs back to back, each with its NUL; cigar_off[np + 1]
   size_t cigar_cap;
   int64_t* cigar_off;
-  int32_t* fin_h = nullptr;  // extension: H(m, n) of every pair, the global alignment's score (fin[0] of its result)
+  int32_t* fin_h = nullptr;  // extension: H(m, n) of every pair, the global alignment's score (fin[0] of its result);
+                             // MSA_SCORE_NONE for a pair a banded extension clipped
 };
 struct GapBand {
   int32_t gap_open, gap_extend;
@@ -303,16 +317,17 @@ int align_range(const AlignSpec& spec, int single, const GapBand& gb, bool want_
 const int64_t kPairLimit = int64_t(1) << 26;  // rows / columns of a pair (msa_sw_align has no limit of its own)
 
 // Every alignment entry: check the arguments (MSA_ERR_ARG; size_lim bounds m and n), the gap rule
-// (MSA_ERR_UNSUPPORTED), the band against the lengths (MSA_ERR_ARG), encode with one symbol map for the call, A
-// then B (MSA_ERR_ALPHABET), and only then ask for the device; then align_range chunk by chunk -- consecutive pairs
+// (MSA_ERR_UNSUPPORTED), the band against the lengths (MSA_ERR_ARG; a banded extension clips instead), encode with
+// one symbol map for the call, A then B (MSA_ERR_ALPHABET), and only then ask for the device; then align_range chunk by chunk -- consecutive pairs
 // whose summed single-pair footprints fit a quarter of the device budget, at most 2^20 of them -- and hand out the
 // CIGARs.
-int align_pairs(AlignSpec spec, int single, const AlignIn& in, int64_t size_lim, int32_t gap_open,
+int align_pairs(AlignSpec spec, int single, const AlignIn& in0, int64_t size_lim, int32_t gap_open,
                 int32_t gap_extend, int64_t band_in, const AlignOut& out) {
   if (spec.status != MSA_OK) return spec.status;
-  if ((!in.A && !spec.prof) || !in.B || !in.a_off || !in.m || !in.b_off || !in.n || in.np < 1 ||
-      (out.cigars && !out.cigar_off) || band_in < -1)
+  if ((!in0.A && !spec.prof) || !in0.B || !in0.a_off || !in0.m || !in0.b_off || !in0.n || in0.np < 1 ||
+      (out.cigars && !out.cigar_off) || band_in < (spec.clip_to_band ? 0 : -1))
     return MSA_ERR_ARG;
+  AlignIn in = in0;  // (a banded extension: with the clipped sizes, below)
   int64_t span_max = 0;
   for (int64_t p = 0; p < in.np; ++p) {
     const int64_t m = in.m[p], n = in.n[p], ao = in.a_off[p], bo = in.b_off[p];
@@ -326,11 +341,22 @@ int align_pairs(AlignSpec spec, int single, const AlignIn& in, int64_t size_lim,
                               : (gap_extend < 0 || gap_open < gap_extend))
     return MSA_ERR_UNSUPPORTED;
   if (!spec.banded) band_in = -1;
-  if (band_in >= 0)
+  std::vector<int64_t> cm, cn;  // a banded extension's sizes: every pair's in-band prefixes (offsets stay)
+  if (spec.clip_to_band) {
+    cm.assign(in.m, in.m + in.np);
+    cn.assign(in.n, in.n + in.np);
+    for (int64_t p = 0; p < in.np; ++p) extend_band_clip(in.m[p], in.n[p], band_in, cm[(size_t)p], cn[(size_t)p]);
+    in.m = cm.data();
+    in.n = cn.data();
+  } else if (band_in >= 0) {
     for (int64_t p = 0; p < in.np; ++p)
       if (std::llabs(in.m[p] - in.n[p]) > band_in) return MSA_ERR_ARG;
-  // (a band that holds every cell of every pair is no band)
-  const GapBand gb{gap_open, gap_extend, (band_in < 0 || band_in >= span_max) ? -1 : (int)band_in};
+  }
+  // (a band that holds every cell of every pair is no band -- but for a banded extension, whose plan kind needs one:
+  // there it is the band of the longest sequence, which holds every cell just as well)
+  const GapBand gb{gap_open, gap_extend,
+                   spec.clip_to_band ? (int)std::min(band_in, span_max)
+                                     : ((band_in < 0 || band_in >= span_max) ? -1 : (int)band_in)};
   std::vector<uint8_t> ca(spec.prof ? 0 : in.a_len), cb(in.b_len);
   int rc = spec.prof ? MSA_OK : spec.symbols.encode(in.A, in.a_len, ca.data());
   if (rc == MSA_OK) rc = spec.symbols.encode(in.B, in.b_len, cb.data());
@@ -354,6 +380,9 @@ int align_pairs(AlignSpec spec, int single, const AlignIn& in, int64_t size_lim,
     if ((rc = align_range(spec, single, gb, want_tb, ca.data(), cb.data(), in, p0, p1, bytes, out, all)) != MSA_OK)
       return rc;
   }
+  // (a clipped pair has no H(m, n): its fill ended at (m', n'))
+  for (int64_t p = 0; spec.clip_to_band && out.fin_h && p < in.np; ++p)
+    if (in.m[p] != in0.m[p] || in.n[p] != in0.n[p]) out.fin_h[p] = MSA_SCORE_NONE;
   if (out.cigars) {
     out.cigar_off[in.np] = (int64_t)all.size();
     if (all.size() > out.cigar_cap) return MSA_ERR_CAPACITY;
@@ -544,24 +573,30 @@ int msa_overlap_align_batch32(const char* A, size_t a_len, const char* B, size_t
 }
 
 // ---- extension alignment (MSA_NW_EXTEND): the overlap entries with {a_end, b_end} and H(m, n) for their two cells;
-// 8 symbols, or 32 for the *32 entries
+// 8 symbols, or 32 for the *32 entries.  banded (MSA_NW_EXTEND_BAND, the *_banded entries): inside `band`, clipped
 static int extend_align(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
                         const int8_t* sub, size_t max_sym, int32_t gap_open, int32_t gap_extend, int32_t* score,
-                        int64_t* end_ij, int32_t* global_score, char* cigar, size_t cigar_cap) {
+                        int64_t* end_ij, int32_t* global_score, char* cigar, size_t cigar_cap, bool banded = false,
+                        int64_t band = -1) {
   const OnePairIn one(A0, m, B0, n);
   int64_t coff[2];
   const AlignOut out{score, PairOut(end_ij), PairOut(), PairOut(), cigar, cigar_cap, coff, global_score};
-  return align_pairs(spec_extend(alphabet, n_sym, sub, max_sym), 1, one.in, kPairLimit, gap_open, gap_extend, -1, out);
+  const AlignSpec spec = banded ? spec_extend_band(alphabet, n_sym, sub, max_sym)
+                                : spec_extend(alphabet, n_sym, sub, max_sym);
+  return align_pairs(spec, 1, one.in, kPairLimit, gap_open, gap_extend, band, out);
 }
 static int extend_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
                               const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
                               const char* alphabet, size_t n_sym, const int8_t* sub, size_t max_sym,
                               int32_t gap_open, int32_t gap_extend, int32_t* score, int64_t* end_ij,
-                              int32_t* global_score, char* cigars, size_t cigar_cap, int64_t* cigar_off) {
+                              int32_t* global_score, char* cigars, size_t cigar_cap, int64_t* cigar_off,
+                              bool banded = false, int64_t band = -1) {
   if (!end_ij) return MSA_ERR_ARG;
   const AlignIn in{A, B, a_len, b_len, n_pairs, a_off, m, b_off, n};
   const AlignOut out{score, PairOut(end_ij), PairOut(), PairOut(), cigars, cigar_cap, cigar_off, global_score};
-  return align_pairs(spec_extend(alphabet, n_sym, sub, max_sym), 0, in, kPairLimit, gap_open, gap_extend, -1, out);
+  const AlignSpec spec = banded ? spec_extend_band(alphabet, n_sym, sub, max_sym)
+                                : spec_extend(alphabet, n_sym, sub, max_sym);
+  return align_pairs(spec, 0, in, kPairLimit, gap_open, gap_extend, band, out);
 }
 
 int msa_extend_align(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
@@ -594,6 +629,46 @@ int msa_extend_align_batch32(const char* A, size_t a_len, const char* B, size_t 
                              char* cigars, size_t cigar_cap, int64_t* cigar_off) {
   return extend_align_batch(A, a_len, B, b_len, n_pairs, a_off, m, b_off, n, alphabet, n_sym, sub, 32, gap_open,
                             gap_extend, score, end_ij, global_score, cigars, cigar_cap, cigar_off);
+}
+
+int msa_extend_band_clip(int64_t m, int64_t n, int64_t band, int64_t* m_eff, int64_t* n_eff) {
+  int64_t me, ne;
+  if (!extend_band_clip(m, n, band, me, ne)) return MSA_ERR_ARG;
+  if (m_eff) *m_eff = me;
+  if (n_eff) *n_eff = ne;
+  return MSA_OK;
+}
+
+int msa_extend_align_banded(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                            const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band, int32_t* score,
+                            int64_t* end_ij, int32_t* global_score, char* cigar, size_t cigar_cap) {
+  return extend_align(A0, m, B0, n, alphabet, n_sym, sub, 8, gap_open, gap_extend, score, end_ij, global_score, cigar,
+                      cigar_cap, true, band);
+}
+
+int msa_extend_align_banded32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                              const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band, int32_t* score,
+                              int64_t* end_ij, int32_t* global_score, char* cigar, size_t cigar_cap) {
+  return extend_align(A0, m, B0, n, alphabet, n_sym, sub, 32, gap_open, gap_extend, score, end_ij, global_score, cigar,
+                      cigar_cap, true, band);
+}
+
+int msa_extend_align_batch_banded(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                                  const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                                  const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                                  int32_t gap_extend, int64_t band, int32_t* score, int64_t* end_ij,
+                                  int32_t* global_score, char* cigars, size_t cigar_cap, int64_t* cigar_off) {
+  return extend_align_batch(A, a_len, B, b_len, n_pairs, a_off, m, b_off, n, alphabet, n_sym, sub, 8, gap_open,
+                            gap_extend, score, end_ij, global_score, cigars, cigar_cap, cigar_off, true, band);
+}
+
+int msa_extend_align_batch_banded32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                                    const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                                    const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                                    int32_t gap_extend, int64_t band, int32_t* score, int64_t* end_ij,
+                                    int32_t* global_score, char* cigars, size_t cigar_cap, int64_t* cigar_off) {
+  return extend_align_batch(A, a_len, B, b_len, n_pairs, a_off, m, b_off, n, alphabet, n_sym, sub, 32, gap_open,
+                            gap_extend, score, end_ij, global_score, cigars, cigar_cap, cigar_off, true, band);
 }
 
 // ---- local alignment under a substitution matrix (MSA_SW_SCORED): msa_sw_align / msa_sw_align_batch with the

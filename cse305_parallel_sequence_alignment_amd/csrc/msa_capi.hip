@@ -472,6 +472,10 @@ kfn_t pick_kernel(int alg, int out, int tp, bool sgl) {
     // must be non-negative)
     case MSA_ALG_EXT: return tp == 1 ? kf_nd<MSA_ALG_EXT, 1>(out, sgl) : nullptr;
     case MSA_ALG_EXT32: return tp == 1 ? kf_nd<MSA_ALG_EXT32, 1>(out, sgl) : nullptr;
+    // ... inside a band (MSA_NW_EXTEND_BAND): the banded global kernels' edge phases with that tracker in them --
+    // instantiations of their own again, the MSA_ALG_EXT and MSA_ALG_NWA kernels' code is unchanged
+    case MSA_ALG_EXTB: return tp == 1 ? kf_nd<MSA_ALG_EXTB, 1>(out, sgl) : nullptr;
+    case MSA_ALG_EXTB32: return tp == 1 ? kf_nd<MSA_ALG_EXTB32, 1>(out, sgl) : nullptr;
     // an MSA_SW_SCORED plan always tracks its end cell: compare-select (1) or the packed key (2) only
     case MSA_ALG_SWS: return tp == 2 ? kf_nd<MSA_ALG_SWS, 2>(out, sgl) : tp == 1 ? kf_nd<MSA_ALG_SWS, 1>(out, sgl) : nullptr;
     case MSA_ALG_SWS32:

@@ -72,6 +72,17 @@ inline int64_t complete_border(std::string& ops, int64_t i, int64_t j, Border ru
   return j;
 }
 
+// A banded extension's clip rule (msa.h at msa_extend_align_banded): rows past n + band and columns past m + band hold
+// no cell with |i - j| <= band, so the problem is the pair of prefixes (m', n') = (min(m, n + band), min(n, m + band)),
+// which always has |m' - n'| <= band.  false for m, n < 1 or band < 0
+inline bool extend_band_clip(int64_t m, int64_t n, int64_t band, int64_t& m_eff, int64_t& n_eff) {
+  if (m < 1 || n < 1 || band < 0) return false;
+  // (n + band may pass INT64_MAX for a huge band: compare the differences instead)
+  m_eff = (m - n > band) ? n + band : m;
+  n_eff = (n - m > band) ? m + band : n;
+  return true;
+}
+
 // The description of a plan for one pair spread over many workgroups, with the arrays it points to (so: neither
 // copied nor moved).  No band, codes at offset 0; the caller sets the scores.
 struct SinglePairDesc {

@@ -207,7 +207,7 @@ __device__ __forceinline__ void border_top(const msa_kparams& kp, int c, int (&v
     v[0] = c >= 0 ? 0 : MSA_NEG;  // H
     v[1] = MSA_NEG;               // F
     v[2] = MSA_NEG;
-  } else if constexpr (TR.cell == CELL_GOTOH) {  // (no band accepted: kp.band = -1, r0 = 0)
+  } else if constexpr (TR.cell == CELL_GOTOH) {  // (an id without a band: kp.band = -1; r0 > 0: chunked NWA alone)
     if (r0 > 0) {
       const int d = c > r0 ? c - r0 : r0 - c;
       v[0] = (d <= kp.band) ? -kp.h - kp.gap_ext * d : MSA_NEG;
@@ -267,7 +267,7 @@ __device__ __forceinline__ void border_left(const msa_kparams& kp, int i, int (&
     v[0] = 0;        // H
     v[1] = MSA_NEG;  // E
     v[2] = MSA_NEG;  // F
-  } else if constexpr (TR.cell == CELL_GOTOH) {  // (no band accepted: kp.band = -1)
+  } else if constexpr (TR.cell == CELL_GOTOH) {  // (an id without a band: kp.band = -1)
     const bool inb = (kp.band < 0) || (i <= kp.band);
     v[0] = inb ? -kp.h - kp.gap_ext * i : MSA_NEG;  // H
     v[1] = MSA_NEG;                                 // T2 (E)
@@ -1337,6 +1337,22 @@ __global__ __launch_bounds__((W + 1 + (SGL ? 1 : 0)) * 64) void stripe_kernel(KA
               // and is outside [tmin, tmax] like a step past column n; mask_lo / mask_hi put every row <= m inside
               // its range in an unmasked phase; a lane whose row is > m has tmax = -1 in the masked phases and
               // counts what it likes in the unmasked ones: stripe finalize drops it.)
+              // (EXTB, the same tracker inside a band -- what keeps an out-of-band value from ever counting:
+              //  (a) a v_writelane phase (MMODE >= 2) is MASKED, so inr tests t against L.tmin / L.tmax, which are
+              //      jlo_of / jhi_of under kp.band: the band's own limits of the lane's row;
+              //  (b) the tracker reads L.S[0] here, after the lane write and after band_fix, and both fix-up steps
+              //      (t = tmin - 1, t = tmax + 1) lie outside [tmin, tmax] like every other out-of-band step.  Those
+              //      steps hold the bare recurrence's values, which may exceed every in-band H (a better alignment
+              //      just outside the band): inr alone drops them, never their value;
+              //  (c) in an unmasked body phase every row <= m is inside its band: stripe_geom takes the band, its
+              //      mask_lo is the largest tmin (jlo_of and the lane both grow with the row) and mask_hi the smallest
+              //      tmax less 1; a regular stripe has no row past m;
+              //  (d) a row with jlo > 1 holds -inf at t = tmin - 1, not the border (stripe init), and is out of range
+              //      there anyway;
+              //  (e) fin[] and has_fin come from the lane of row m as in every global plan: a plan's (m, n) satisfies
+              //      |m - n| <= band (check_ranges), so (m, n) is an in-band cell and row m's tmax is its column n.
+              //  Every row i <= m has an in-band cell (jlo = max(1, i - band) <= n) and its first one has an in-band
+              //  diagonal or border neighbour, so every row's best is a finite H and lane 0's always counts.)
               const bool inr = !MASKED || (t >= L.tmin && t <= L.tmax);
               const bool better = inr && L.S[0] > L.best;
               L.best = better ? L.S[0] : L.best;

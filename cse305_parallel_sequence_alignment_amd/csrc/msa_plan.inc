@@ -161,11 +161,13 @@ msa_walk walker_of(const msa_plan* P) {
   return (P->d.cells != MSA_CELLS_DIR || (w == TB_SW && !P->d.track_end)) ? TB_NONE : w;
 }
 // the algorithms that score as MSA_NW_SCORED does (table or match / mismatch) under free ends, on the stripe kernel alone
-bool free_ends(int alg) { return alg == MSA_NW_FIT || alg == MSA_NW_OVERLAP || alg == MSA_NW_EXTEND; }
+bool free_ends(int alg) {
+  return alg == MSA_NW_FIT || alg == MSA_NW_OVERLAP || alg == MSA_NW_EXTEND || alg == MSA_NW_EXTEND_BAND;
+}
 
 // ---- step 1: kernel algorithm and end-cell tracking mode --------------------------------------------
 // wide32: a 32 x 32 table over 5-bit codes (msa_plan_create_scored32: MSA_NW_SCORED, MSA_NW_FIT, MSA_NW_OVERLAP,
-// MSA_NW_EXTEND only)
+// MSA_NW_EXTEND, MSA_NW_EXTEND_BAND only)
 // sw_smax: max(0, the largest table entry over real codes) of an MSA_SW_SCORED plan (unused by every other plan)
 // profile: the 32-code id's profile twin (msa_plan_create_profile: MSA_SW_SCORED, MSA_NW_SCORED, MSA_NW_FIT only)
 int choose_algorithm(const msa_plan_desc* desc, bool wide32, bool profile, int sw_smax, int& kalg, int& tp) {
@@ -214,6 +216,13 @@ int choose_algorithm(const msa_plan_desc* desc, bool wide32, bool profile, int s
     case MSA_NW_FIT: kalg = MSA_ALG_FIT; break;
     case MSA_NW_OVERLAP: kalg = MSA_ALG_OVL; break;
     case MSA_NW_EXTEND: kalg = MSA_ALG_EXT; break;
+    // ... but for the extension inside a band, a plan kind of its own with a rule of its own for the sizes (msa.h at
+    // msa_extend_align_banded: the caller clips, so |m - n| <= band holds here as for a global plan).  It needs a
+    // band; MSA_NW_EXTEND keeps rejecting one
+    case MSA_NW_EXTEND_BAND:
+      kalg = MSA_ALG_EXTB;
+      if (desc->band < 0) return MSA_ERR_UNSUPPORTED;
+      break;
     case MSA_REF_GOTOH: {
       // start type -1 (main_alignment_function's single subproblem) with direction bytes or no
       // cells: the tagged-max form (every interior value is finite; values carried x4)
@@ -327,7 +336,10 @@ int check_ranges(const msa_plan_desc* desc, const msa_kparams& kp, const int8_t*
       // last-column maxima are copies of cells again: the same inequality holds.
       // MSA_NW_EXTEND (MSA_ALG_EXT) is the unbanded MSA_ALG_NWA itself in the stripe kernel, unshifted: same sources,
       // steps and -inf, and the tracked maximum is a copy of a cell: the same inequality holds.
-      // The 32-code kernels (MSA_ALG_NWA32, MSA_ALG_FIT32, MSA_ALG_OVL32, MSA_ALG_EXT32: stripe_kernel, unshifted, raw S) differ in where a step's
+      // MSA_NW_EXTEND_BAND (MSA_ALG_EXTB) is the BANDED MSA_ALG_NWA in the stripe kernel, unshifted: the banded global
+      // plan's sources (the borders up to the band, -inf past it), steps and drifting out-of-band lanes between the
+      // edge fix-ups -- all counted above --, and the tracked maximum is a copy of an in-band cell: the same inequality.
+      // The 32-code kernels (MSA_ALG_NWA32, MSA_ALG_FIT32, MSA_ALG_OVL32, MSA_ALG_EXT32, MSA_ALG_EXTB32: stripe_kernel, unshifted, raw S) differ in where a step's
       // S comes from, not in what a step is: the same inequality with s over the 1,024 scores.
       // The profile kernels (MSA_ALG_NWP, MSA_ALG_FITP) are those kernels again with a row's 32 bytes taken from the
       // profile: the same inequality with s over the whole profile (a row past m scores 0: within s).
@@ -438,6 +450,8 @@ PlanMode choose_mode(const msa_plan_desc* desc, int kalg, int tp, int smax) {
     // A banded pair has only ~(2*band+64)/(64*lag) stripes in flight at once: band_kernel's chains of
     // 4-stripe items, as long as its code rows fit LDS; chunked from 4 chunks up, when cells are written
     // (direction bytes: MSA_NW_ALIGN, chunked like H -- a chunk's bytes do not depend on its constant)
+    // (MSA_ALG_NWA alone: a banded extension, MSA_ALG_EXTB, has a band too and stays on the exact stripe launch below,
+    // as every free-end plan does -- band_kernel and the chunks keep no best cell)
     if (kalg == MSA_ALG_NWA && band >= 0) {
       const int S = stripes_of(desc->m[0]);
       // MSA_NW_SCORED: band_kernel works on values shifted by g (i + j), so its profile bytes are S + 2g + h; a
@@ -951,8 +965,8 @@ static int plan_create(const msa_plan_desc* desc, const int8_t* sub, bool wide32
   P->nc = msa_alg_info_of(kalg).nc;
   if (msa_alg_info_of(kalg).band && P->main.kp.h < 0) return MSA_ERR_UNSUPPORTED;
   // the substitution scores of the banded recurrence: MSA_NW_SCORED's table, or its match / mismatch; 1 / 0 for
-  // MSA_NW_BANDED and MSA_NW_ALIGN, whatever their description says; MSA_NW_FIT, MSA_NW_OVERLAP and MSA_NW_EXTEND
-  // score as MSA_NW_SCORED does
+  // MSA_NW_BANDED and MSA_NW_ALIGN, whatever their description says; MSA_NW_FIT, MSA_NW_OVERLAP, MSA_NW_EXTEND and
+  // MSA_NW_EXTEND_BAND score as MSA_NW_SCORED does
   const bool scored = desc->alg == MSA_NW_SCORED || free_ends(desc->alg);
   int smax = 0;
   if (scored && !sub && !prof &&

@@ -31,6 +31,8 @@ enum msa_alg {
   MSA_ALG_SWP = 17,    // every XP: X32 under a position-specific profile, one 32-byte row of scores per row of the
   MSA_ALG_NWP = 18,    // matrix (msa_plan_create_profile: MSA_SW_SCORED, MSA_NW_SCORED, MSA_NW_FIT)
   MSA_ALG_FITP = 19,
+  MSA_ALG_EXTB = 20,   // MSA_NW_EXTEND_BAND: MSA_ALG_EXT, with a band (a derived row of msa_alg.h)
+  MSA_ALG_EXTB32 = 21,
 };
 
 // Per-cell outputs.

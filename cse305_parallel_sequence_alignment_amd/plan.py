@@ -51,7 +51,7 @@ class Plan:
 
     def __init__(self, alg: int, cells: int, ms, ns, a_offs, b_offs, match=1, mismatch=0, gap_open=1,
                  gap_extend=1, start_type=-1, band=-1, track_end=False, single=None, sub=None, profile=None):
-        """``sub`` (NW_SCORED, NW_FIT, NW_OVERLAP, NW_EXTEND and SW_SCORED only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code
+        """``sub`` (NW_SCORED, NW_FIT, NW_OVERLAP, NW_EXTEND, NW_EXTEND_BAND and SW_SCORED only): an 8 x 8 array-like of int8 scores, ``sub[a][b]`` = row code
         a against column code b (msa_plan_create_scored); None scores ``match`` on the diagonal and ``mismatch``
         elsewhere.  A 32 x 32 ``sub`` makes a plan over 5-bit codes (msa_plan_create_scored32: inputs in [0, 32), always the
         stripe kernel); any other shape is a ValueError.
@@ -65,6 +65,9 @@ class Plan:
         reports the score and its end cell ``end = (a_end, b_end)``, the first maximum over the interior -- ``(0, 0)``
         with score 0 for the empty extension --, and in ``fin[0]`` the global score H(m, n); the same two walks start
         at the end cell and append the global border gap.
+        An NW_EXTEND_BAND plan is an NW_EXTEND plan inside ``band`` >= 0 (required): a banded NW_SCORED plan's cells
+        and bytes, the first maximum over the in-band interior, ``fin[0]`` = H(m, n).  Like every banded plan it takes
+        sizes with ``|m - n| <= band``: clip longer pairs with ``extend_band_clip`` first.
         An SW_SCORED plan (SW_AFFINE's recurrence under the table: ``band`` -1, CELLS_DIR or CELLS_NONE) keeps the
         highest code, 7 or 31, as the kernels' out-of-matrix sentinel: inputs are codes 0..6 / 0..30 and ``sub``'s last
         row and column are ignored.  It always tracks its end cell and runs the stripe kernel; ``traceback``,
@@ -328,8 +331,8 @@ class Plan:
         """The ops a global walk that stopped on the matrix border at (i, j) still lacks: i x 'I' or j x 'D'.  An
         NW_FIT plan's alignment starts at reference column j for free: only the 'I' gap (the query overhangs the
         reference's start) is appended, and ``stop[1]`` is where the aligned substring begins.  An NW_OVERLAP plan's
-        alignment starts at the stop cell itself: nothing is appended.  An NW_EXTEND plan's starts at (0, 0): the global
-        gap."""
+        alignment starts at the stop cell itself: nothing is appended.  An NW_EXTEND or NW_EXTEND_BAND plan's starts at
+        (0, 0): the global gap (inside the band, since the walk never leaves it)."""
         if self.alg == LB.NW_OVERLAP:
             return b""
         if i > 0:
@@ -392,7 +395,7 @@ class Plan:
             LB.check(int(inf[k, 3]), "msa_plan_traceback_batch")
             o = oh[off[k]:off[k] + int(inf[k, 0])].tobytes()
             stats = dict(switches=int(inf[k, 4]), staged=int(inf[k, 5]), ticks=int(inf[k, 6]))
-            if self.alg in (LB.NW_ALIGN, LB.NW_SCORED, LB.NW_FIT, LB.NW_OVERLAP, LB.NW_EXTEND):
+            if self.alg in (LB.NW_ALIGN, LB.NW_SCORED, LB.NW_FIT, LB.NW_OVERLAP, LB.NW_EXTEND, LB.NW_EXTEND_BAND):
                 i, j = int(inf[k, 1]) - 1, int(inf[k, 2]) - 1
                 o += self._border_gap(i, j)
                 out.append(dict(ops=o, stop=(i, j), cigar=cigar_of(o), stats=stats))
@@ -464,6 +467,14 @@ def cigar_of(ops_end_to_start: bytes) -> str:
             k -= 1
         out.append(f"{run}{chr(op)}")
     return "".join(out)
+
+
+def extend_band_clip(m: int, n: int, band: int) -> tuple:
+    """(m', n') of a banded extension (msa_extend_band_clip): rows past n + band and columns past m + band hold no
+    in-band cell, so A[:m'] against B[:n'] is the whole problem, and ``|m' - n'| <= band``."""
+    me, ne = C.c_int64(), C.c_int64()
+    LB.check(LB.lib().msa_extend_band_clip(m, n, band, C.byref(me), C.byref(ne)), "msa_extend_band_clip")
+    return me.value, ne.value
 
 
 def jlo_of(i: int, band: int) -> int:

@@ -53,6 +53,11 @@
  *                        extension alignment (anchored start, free end: what a seed-and-extend pipeline runs on
  *                        each flank of a seed): the best-scoring pair of prefixes, with the end-to-end score
  *                        beside it (build extension: MSA_NW_EXTEND plans)
+ *   msa_extend_align_banded, msa_extend_align_batch_banded, msa_extend_align_banded32,
+ *   msa_extend_align_batch_banded32, msa_extend_band_clip
+ *                        the same inside a band |i - j| <= band, the work bounded by m, n and the band alone (build
+ *                        extension: MSA_NW_EXTEND_BAND plans -- the banded global kernel's cells and edge phases
+ *                        under the extension's end-cell tracker; the clip rule that stands for |m - n| <= band)
  *   msa_plan_create_scored32, msa_nw_align_scored32, msa_nw_align_batch_scored32, msa_fit_align32,
  *   msa_fit_align_batch32
  *                        MSA_NW_SCORED and MSA_NW_FIT over alphabets of up to 32 symbols (proteins, IUPAC DNA):
@@ -265,9 +270,13 @@ typedef enum msa_alg_e {
   MSA_NW_OVERLAP = 9, /* overlap ("dovetail", "ends-free") alignment: MSA_NW_FIT's cells under zero borders on the top
                          AND the left, ending anywhere on the last row or the last column; the contract is at
                          msa_overlap_align below.  band = -1, MSA_CELLS_DIR or MSA_CELLS_NONE */
-  MSA_NW_EXTEND = 10  /* extension alignment: an unbanded MSA_NW_SCORED plan's cells, borders and bytes, ending at the
+  MSA_NW_EXTEND = 10, /* extension alignment: an unbanded MSA_NW_SCORED plan's cells, borders and bytes, ending at the
                          first maximum over all interior cells (the best pair of prefixes) or nowhere; the contract is
                          at msa_extend_align below.  band = -1, MSA_CELLS_DIR or MSA_CELLS_NONE */
+  MSA_NW_EXTEND_BAND = 11 /* extension alignment inside a band: a BANDED MSA_NW_SCORED plan's cells, borders and bytes,
+                         ending at the first maximum over the in-band interior cells or nowhere; the contract is at
+                         msa_extend_align_banded below.  band >= 0 and |m - n| <= band (msa_extend_band_clip),
+                         MSA_CELLS_DIR or MSA_CELLS_NONE */
 } msa_alg_e;
 
 typedef enum msa_out_e { MSA_CELLS_NONE = 0, MSA_CELLS_H = 1, MSA_CELLS_DIR = 2, MSA_CELLS_TAB = 3 } msa_out_e;
@@ -295,7 +304,8 @@ typedef struct msa_pair_result {
                             its first: the flag is cleared once it has been reported) */
   int64_t end_i, end_j;  /* SW: end cell; Gotoh: (m, n); MSA_NW_FIT: (m, first column of row m's maximum);
                             MSA_NW_OVERLAP: the end cell on row m or column n, or (m, 0) with score 0;
-                            MSA_NW_EXTEND: the first maximum over the interior, or (0, 0) with score 0 */
+                            MSA_NW_EXTEND: the first maximum over the interior, or (0, 0) with score 0;
+                            MSA_NW_EXTEND_BAND: ... over the in-band interior */
   int32_t fin[3];        /* Gotoh: state at (m, n) (T1,T2,T3 / H,E,F); MSA_NW_FIT: the same cell's (H,E,F), which
                             is not part of that algorithm's result; MSA_NW_EXTEND: the same, and part of the
                             result -- fin[0] = H(m, n) is the end-to-end (global) score */
@@ -318,6 +328,8 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** plan);
  * with any band but -1 and with cells other than MSA_CELLS_DIR / MSA_CELLS_NONE.  MSA_NW_OVERLAP: exactly
  * MSA_NW_FIT's rules and errors (its zero left border is within the bound too).  MSA_NW_EXTEND: the same rules
  * and errors again (its cells and borders are the unbanded MSA_NW_SCORED plan's: the same inequality).
+ * MSA_NW_EXTEND_BAND: MSA_NW_SCORED's rules with a band REQUIRED -- band < 0 is MSA_ERR_UNSUPPORTED, |m - n| > band is
+ * MSA_ERR_ARG (clip with msa_extend_band_clip first) -- under the same inequality; a profile is MSA_ERR_UNSUPPORTED.
  * MSA_SW_SCORED takes a table too (NULL: desc->match on the diagonal, desc->mismatch elsewhere, in [-128, 127]; the
  * results are then an MSA_SW_AFFINE plan's).  The kernels keep their out-of-matrix sentinel: code 7 is the virtual
  * column's, the inputs are codes 0..6 -- 7 symbols --, table entries with either index 7 are ignored, and the launch's
@@ -332,9 +344,9 @@ int msa_plan_create(const msa_plan_desc* desc, msa_plan** plan);
  * msa_plan_traceback_nw and msa_plan_traceback_gotoh reject it with MSA_ERR_UNSUPPORTED.  A non-NULL sub with
  * MSA_SW_AFFINE stays MSA_ERR_UNSUPPORTED, and MSA_SW_AFFINE plans choose their kernels as before. */
 int msa_plan_create_scored(const msa_plan_desc* desc, const int8_t* sub, msa_plan** plan);
-/* MSA_NW_SCORED, MSA_NW_FIT, MSA_NW_OVERLAP and MSA_NW_EXTEND over 5-bit codes: sub32 = 1,024 scores, row-major
+/* MSA_NW_SCORED, MSA_NW_FIT, MSA_NW_OVERLAP, MSA_NW_EXTEND and MSA_NW_EXTEND_BAND over 5-bit codes: sub32 = 1,024 scores, row-major
  * sub32[32*a + b] = the score of A's code a against B's code b.  The inputs of msa_plan_run are codes in [0, 32).  desc->alg must be one of
- * those four (anything else but MSA_SW_SCORED, below: MSA_ERR_UNSUPPORTED); sub32 == NULL is MSA_ERR_ARG.  Cells, band and gap rules, the
+ * those five (anything else but MSA_SW_SCORED, below: MSA_ERR_UNSUPPORTED); sub32 == NULL is MSA_ERR_ARG.  Cells, band and gap rules, the
  * value-range inequality (s = the largest |score| of the 1,024) and their errors are msa_plan_create_scored's.
  * Such a plan always launches the stripe kernel (msa_plan_launch_info mode 0): one pair, a batch, any band (a banded
  * single pair runs the exact masked stripe launch).  msa_plan_format_info reports it in its fourth word;
@@ -721,6 +733,55 @@ int msa_extend_align_batch32(const char* A, size_t a_len, const char* B, size_t 
                              const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
                              int32_t gap_extend, int32_t* score, int64_t* end_ij, int32_t* global_score,
                              char* cigars, size_t cigar_cap, int64_t* cigar_off);
+
+/* Banded extension alignment (build extension: MSA_NW_EXTEND_BAND plans; the band of ksw2's "extz", BWA-MEM's and
+ * BLAST's gapped extensions): the extension contract of msa_extend_align above with these changes, for a band w >= 0.
+ *   Cells: a cell with |i - j| > w is -inf in all three states.  Row 0 and column 0 are the banded global borders:
+ *     H(0, j) = -h - g j for 1 <= j <= w, H(i, 0) = F(i, 0) = -h - g i for 1 <= i <= w, -inf beyond.  E, F, H, the
+ *     direction byte and every tie rule are exactly a banded MSA_NW_SCORED plan's: the in-band interior bytes of the
+ *     two plans on one input are equal.
+ *   Result: best = max of H(i, j) over the interior cells with |i - j| <= w; the end cell is the first maximum in
+ *     row-major order; best <= 0 is the empty extension (score 0, end cell (0, 0), no walk, empty CIGAR).  The walk is
+ *     msa_extend_align's, from the end cell, completed by the global border gap; it never leaves the band, so a stop
+ *     at (i, 0) has i <= w and one at (0, j) has j <= w.
+ *   The clip rule (what stands for the global plans' |m - n| <= band): a row i > n + w and a column j > m + w hold no
+ *     in-band cell, so with m' = min(m, n + w) and n' = min(n, m + w) the problem IS A[0, m') against B[0, n'), and
+ *     that pair always has |m' - n'| <= w.  msa_extend_band_clip computes (m', n'); the host entries below clip, a
+ *     plan takes clipped sizes and answers |m - n| > band with MSA_ERR_ARG as every banded plan does.
+ *   global_score: H(m, n) exists only when nothing was clipped, (m', n') = (m, n); it is then what
+ *     msa_nw_align_scored returns under the same band.  Otherwise the entries report MSA_SCORE_NONE.  A plan's
+ *     fin[0] is H(m', n'), as for any banded global plan.
+ *   One band per call.  band = -1 is not this plan kind's: MSA_NW_EXTEND is untouched and keeps rejecting any band.
+ *   Out of scope, each MSA_ERR_UNSUPPORTED at plan creation: band < 0, cells other than MSA_CELLS_DIR /
+ *   MSA_CELLS_NONE, a profile (msa_plan_create_profile), gap_extend < 0 or gap_open < gap_extend.  No Z-drop; no band,
+ *   flow, chunked or split launch: every such plan runs the stripe kernel's exact launch (msa_plan_launch_info mode
+ *   0), as every free-end plan does, with end-cell tracking 1.  The value-range inequality of msa_plan_create_scored
+ *   holds unchanged (a banded global plan's sources and steps; the tracked maximum is a copy of an in-band cell).
+ * The entries are their unbanded twins with `band` after gap_extend, in everything else and in the twins' order of
+ * checks: band < 0 is MSA_ERR_ARG, decided with the other arguments; then the gap rule, the alphabet, the device.  Each
+ * pair is clipped to (m', n') -- its offsets stay, a prefix is kept -- and a clipped pair's global_score is
+ * MSA_SCORE_NONE.  Admission reserves the band's bytes (~(2 band + 64) per row), not the matrix's. */
+#define MSA_SCORE_NONE INT32_MIN
+/* (m', n') of the clip rule above into *m_eff, *n_eff (either may be NULL).  m, n < 1 or band < 0: MSA_ERR_ARG.  Pure
+ * host arithmetic: it needs no device. */
+int msa_extend_band_clip(int64_t m, int64_t n, int64_t band, int64_t* m_eff, int64_t* n_eff);
+int msa_extend_align_banded(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                            const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band, int32_t* score,
+                            int64_t* end_ij, int32_t* global_score, char* cigar, size_t cigar_cap);
+int msa_extend_align_batch_banded(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                                  const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                                  const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                                  int32_t gap_extend, int64_t band, int32_t* score, int64_t* end_ij,
+                                  int32_t* global_score, char* cigars, size_t cigar_cap, int64_t* cigar_off);
+/* ... for alphabets of up to 32 symbols (9..32 symbols: MSA_ALG_EXTB32 plans) */
+int msa_extend_align_banded32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                              const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band, int32_t* score,
+                              int64_t* end_ij, int32_t* global_score, char* cigar, size_t cigar_cap);
+int msa_extend_align_batch_banded32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                                    const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                                    const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                                    int32_t gap_extend, int64_t band, int32_t* score, int64_t* end_ij,
+                                    int32_t* global_score, char* cigars, size_t cigar_cap, int64_t* cigar_off);
 
 /* The four matrix-scored entries above for alphabets of up to 32 symbols (proteins with B Z X *, IUPAC DNA): the
  * signatures of their 8-symbol twins, 1 <= n_sym <= 32, sub = n_sym x n_sym.  With n_sym <= 8 a call builds exactly
