@@ -5,12 +5,19 @@ The library is built in-tree by ``__graft_entry__.build()`` /
 fallback: if the library is missing, importing the compute API raises, and
 on a machine without a gfx950 GPU every call returns MSA_ERR_NODEV, which
 this module turns into ``MsaError``.
+
+The alignment entries (msa_sw_align ... msa_profile_align_batch) are not listed
+by hand: ``KINDS`` declares each alignment kind once -- how its entries are
+named, the order of their arguments, its outputs and its result dict -- and
+both ``lib()``'s argtypes and api.py's calls come from that declaration.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 from pathlib import Path
+from typing import Callable, Optional, Tuple
 
 PKG = Path(__file__).resolve().parent
 # MSA_LIB_PATH: a diagnostic build (e.g. -DMSA_STAMPS) loaded instead of the in-tree library
@@ -63,6 +70,96 @@ class PlanDesc(C.Structure):
 class PairResult(C.Structure):
     _fields_ = [("score", C.c_int32), ("status", C.c_int32), ("end_i", C.c_int64), ("end_j", C.c_int64),
                 ("fin", C.c_int32 * 3), ("pad", C.c_int32)]
+
+
+# The alignment entries (msa_*_align*).  An argument is a named slot; these are the integers, every other slot is a
+# pointer.  A Kind puts the slots of each of its entries in C order, once: lib() takes the argtypes from that order and
+# api.py the call.
+_INT_SLOTS = {"mode": C.c_int, "a_len": C.c_size_t, "b_len": C.c_size_t, "rows": C.c_size_t, "n_sym": C.c_size_t,
+              "cap": C.c_size_t, "k": C.c_int64, "band": C.c_int64, "match": C.c_int32, "mismatch": C.c_int32,
+              "gap_open": C.c_int32, "gap_extend": C.c_int32}
+
+
+@dataclass(frozen=True)
+class Kind:
+    """One alignment kind of include/msa.h: the names of its entries, their arguments and its result."""
+    name: str                                    # msa_<name>_align
+    result: Callable                             # (traceback, one pair's outputs in C order) -> its dict, cigar aside
+    pairs: Tuple[str, ...] = ()                  # the int64 {i, j} outputs that follow the score
+    split: bool = False                          # a single-pair entry takes each as two pointers, to i and to j
+    score2: bool = False                         # a second int32 score follows them (extension's global score)
+    withheld: Tuple[str, ...] = ()               # the outputs that are NULL when traceback=False
+    head: Tuple[str, ...] = ("A", "a_len")       # what stands on the A side
+    matrix: Tuple[str, ...] = ("alphabet", "n_sym", "sub")
+    # the scoring slots of the entries without `_scored`, which run when match / mismatch (sw) or nothing (nw) is
+    # given and max_symbols is 8; None: there are none, every call has an alphabet and a matrix (+1 / 0 by default)
+    plain: Optional[Tuple[str, ...]] = None
+    sentinel: bool = False                       # the highest code is kept free: one symbol fewer than max_symbols
+    band: Optional[str] = None                   # None: no band; "": in every entry; else the suffix of those with one
+
+    def outputs(self):
+        return ("score",) + self.pairs + (("global_score",) if self.score2 else ())
+
+    def entry(self, batch, scored=True, banded=False, wide=False):
+        """(C name, argument slots in C order) of one entry."""
+        name = (f"msa_{self.name}_align" + "_batch" * batch + "_scored" * (scored and self.plain is not None)
+                + (self.band if banded else "") + "32" * wide)
+        slots = self.head + ("B", "b_len")
+        if batch:
+            slots += ("k",) + (("a_off", "m") if self.head[0] == "A" else ()) + ("b_off", "n")
+        slots += self.matrix if scored else self.plain
+        slots += ("gap_open", "gap_extend") + (("band",) if banded or self.band == "" else ())
+        for o in self.outputs():
+            slots += (o + "_i", o + "_j") if o in self.pairs and self.split and not batch else (o,)
+        return name, slots + ("cigar", "cap") + (("cigar_off",) if batch else ())
+
+    def entries(self):
+        """Every entry the header declares for this kind."""
+        for batch in (False, True):
+            for scored in (True,) if self.plain is None else (False, True):
+                for banded in (False, True) if self.band else (False,):
+                    for wide in (False, True) if scored and "sub" in self.matrix else (False,):
+                        yield self.entry(batch, scored, banded, wide)
+
+
+def _ij(c):
+    return int(c[0]), int(c[1])
+
+
+def _sw_result(tb, score, end, beg):
+    return dict(score=int(score), end=_ij(end), **(dict(beg=_ij(beg)) if tb else {}))
+
+
+def _fit_result(tb, score, beg_end):
+    return dict(score=int(score), beg=int(beg_end[0]) if tb else None, end=int(beg_end[1]))
+
+
+def _overlap_result(tb, score, beg, end):
+    return dict(score=int(score), a_beg=int(beg[0]) if tb else None, a_end=int(end[0]),
+                b_beg=int(beg[1]) if tb else None, b_end=int(end[1]))
+
+
+def _extend_result(tb, score, end, gscore):
+    # (MSA_SCORE_NONE: a banded extension clipped the pair, so its fill never reached (m, n))
+    return dict(score=int(score), a_end=int(end[0]), b_end=int(end[1]),
+                global_score=None if int(gscore) == SCORE_NONE else int(gscore))
+
+
+def _profile_result(tb, score, beg, end):
+    return dict(score=int(score), beg=_ij(beg) if tb else None, end=_ij(end))
+
+
+KINDS = {kind.name: kind for kind in (
+    Kind("sw", _sw_result, pairs=("end", "beg"), split=True, withheld=("beg",), plain=("match", "mismatch"),
+         sentinel=True),
+    Kind("nw", lambda tb, score: dict(score=int(score)), plain=(), band=""),
+    Kind("fit", _fit_result, pairs=("beg_end",), split=True),
+    Kind("overlap", _overlap_result, pairs=("beg", "end")),
+    Kind("extend", _extend_result, pairs=("end",), score2=True, band="_banded"),
+    # (mode, prof, rows) for A; the profile is its own scoring, so there is no matrix and no 32-symbol twin
+    Kind("profile", _profile_result, pairs=("beg", "end"), withheld=("beg",), head=("mode", "prof", "rows"),
+         matrix=("alphabet", "n_sym")),
+)}
 
 
 _lib = None
@@ -129,49 +226,11 @@ def lib() -> C.CDLL:
     L.msa_plan_last_kernel_ms.argtypes = [P, C.POINTER(C.c_float)]
     L.msa_plan_set_timing.argtypes = [P, i32]
     L.msa_encode_pair.argtypes = [P, sz, P, sz, P, P]
-    L.msa_sw_align.argtypes = [P, sz, P, sz, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64),
-                               C.POINTER(i64), C.POINTER(i64), P, sz]
-    L.msa_nw_align.argtypes = [P, sz, P, sz, i32, i32, i64, C.POINTER(i32), P, sz]
-    L.msa_sw_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, i32, i32, i32, i32, P, P, P, P, sz, P]
-    L.msa_nw_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, i32, i32, i64, P, P, sz, P]
-    L.msa_nw_align_scored.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, i64, C.POINTER(i32), P, sz]
-    L.msa_nw_align_batch_scored.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, i64, P, P, sz, P]
-    L.msa_fit_align.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), P,
-                                sz]
-    L.msa_fit_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, P, P, P, sz, P]
-    # the *32 entries: their 8-symbol twins' signatures
-    L.msa_nw_align_scored32.argtypes = L.msa_nw_align_scored.argtypes
-    L.msa_nw_align_batch_scored32.argtypes = L.msa_nw_align_batch_scored.argtypes
-    L.msa_fit_align32.argtypes = L.msa_fit_align.argtypes
-    L.msa_fit_align_batch32.argtypes = L.msa_fit_align_batch.argtypes
-    # overlap alignment: fit's arguments, with {a_beg, b_beg} and {a_end, b_end} for beg_j and end_j (the batch: two
-    # arrays of 2 n_pairs for fit's one)
-    L.msa_overlap_align.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, C.POINTER(i32), P, P, P, sz]
-    L.msa_overlap_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, P, P, P, P, sz, P]
-    L.msa_overlap_align32.argtypes = L.msa_overlap_align.argtypes
-    L.msa_overlap_align_batch32.argtypes = L.msa_overlap_align_batch.argtypes
-    # extension alignment: overlap's arguments with {a_end, b_end} and the global score H(m, n) for its two cells
-    L.msa_extend_align.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, C.POINTER(i32), P, C.POINTER(i32), P, sz]
-    L.msa_extend_align_batch.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, P, P, P, P, sz, P]
-    L.msa_extend_align32.argtypes = L.msa_extend_align.argtypes
-    L.msa_extend_align_batch32.argtypes = L.msa_extend_align_batch.argtypes
-    # ... inside a band: `band` after gap_extend; the clip rule on its own
-    L.msa_extend_align_banded.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, i64, C.POINTER(i32), P, C.POINTER(i32), P,
-                                          sz]
-    L.msa_extend_align_batch_banded.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, i64, P, P, P, P, sz,
-                                                P]
-    L.msa_extend_align_banded32.argtypes = L.msa_extend_align_banded.argtypes
-    L.msa_extend_align_batch_banded32.argtypes = L.msa_extend_align_batch_banded.argtypes
     L.msa_extend_band_clip.argtypes = [i64, i64, i64, C.POINTER(i64), C.POINTER(i64)]
-    # local alignment under a matrix: msa_sw_align's / msa_sw_align_batch's, (alphabet, n_sym, sub) for (match, mismatch)
-    L.msa_sw_align_scored.argtypes = [P, sz, P, sz, P, sz, P, i32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64),
-                                      C.POINTER(i64), C.POINTER(i64), P, sz]
-    L.msa_sw_align_batch_scored.argtypes = [P, sz, P, sz, i64, P, P, P, P, P, sz, P, i32, i32, P, P, P, P, sz, P]
-    L.msa_sw_align_scored32.argtypes = L.msa_sw_align_scored.argtypes
-    L.msa_sw_align_batch_scored32.argtypes = L.msa_sw_align_batch_scored.argtypes
-    # profile alignment: (mode, prof, m) for A; two cells {i, j} per pair
-    L.msa_profile_align.argtypes = [C.c_int, P, sz, P, sz, P, sz, i32, i32, C.POINTER(i32), P, P, P, sz]
-    L.msa_profile_align_batch.argtypes = [C.c_int, P, sz, P, sz, i64, P, P, P, sz, i32, i32, P, P, P, P, sz, P]
+    # the alignment entries: every entry of every kind, from the kind's own argument order
+    for kind in KINDS.values():
+        for name, slots in kind.entries():
+            getattr(L, name).argtypes = [_INT_SLOTS.get(s, P) for s in slots]
     _lib = L.lib
     return _lib
 

@@ -264,75 +264,17 @@ def partial_tables(A, B, m, n, g, h, start_type, end_type):
     return T, R
 
 
-def _sw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols):
-    """The scoring of sw_align / sw_align_batch: None for today's match / mismatch call (``max_symbols`` 8 and neither
-    ``alphabet`` nor ``matrix``), else _nw_scoring's (alphabet bytes, int8 matrix) under its rules and ValueErrors.
-    The local kernels keep their highest code as the out-of-matrix sentinel, so ``max_symbols=32`` with ``match`` /
-    ``mismatch`` takes at most 31 distinct symbols in ``seqs`` (more: MsaError with the ALPHABET status)."""
-    if max_symbols not in (8, 32):
-        raise ValueError("max_symbols must be 8 or 32")
-    if alphabet is None and matrix is None:
-        if max_symbols == 8:
-            return None
-        if len(set(b"".join(seqs))) > 31:
-            raise LB.MsaError(-2, "sw_align")
-        match = 1 if match is None else match
-    return _nw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols)
+# The alignment calls of the build extension.  LB.KINDS declares each kind once; _align (or _profile_align) and
+# _call marshal every one of them, a single pair being a batch of one handed to the single-pair entry.
 
 
-def sw_align(A, B, match=None, mismatch=None, gap_open=1, gap_extend=1, traceback=True, alphabet=None, matrix=None,
-             max_symbols=8):
-    """Smith-Waterman local alignment (build extension) -> dict(score, end, beg, cigar).
-
-    ``match`` / ``mismatch`` (None: 1 / 0) over the symbols of A and B, at most 7 (msa_sw_align).  Or ``alphabet``
-    (up to 7 distinct bytes) with ``matrix``, len(alphabet) x len(alphabet) scores in [-128, 127], ``matrix[a][b]`` =
-    alphabet[a] in A against alphabet[b] in B (msa_sw_align_scored); giving ``match`` or ``mismatch`` with it is a
-    ValueError, as for nw_align.  ``max_symbols=32`` (msa_sw_align_scored32; any value but 8 or 32 is a ValueError):
-    ``alphabet`` may hold up to 31 bytes -- proteins, IUPAC DNA --, and ``match`` / ``mismatch`` score the symbols of
-    A and B themselves, at most 31.  The matrix-scored calls run the stripe kernel whatever the pair's size."""
-    A, B = _buf(A), _buf(B)
-    scoring = _sw_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
-    sc = C.c_int32()
-    ei, ej, bi, bj = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-    cap = 4 * (len(A) + len(B)) + 16
-    cig = C.create_string_buffer(cap) if traceback else None
-    outs = (C.byref(sc), C.byref(ei), C.byref(ej), C.byref(bi) if traceback else None,
-            C.byref(bj) if traceback else None, cig, cap if traceback else 0)
-    if scoring is None:
-        LB.check(LB.lib().msa_sw_align(A, len(A), B, len(B), 1 if match is None else match,
-                                       0 if mismatch is None else mismatch, gap_open, gap_extend, *outs),
-                 "msa_sw_align")
-    else:
-        alpha, S = scoring
-        name = "msa_sw_align_scored" if max_symbols == 8 else "msa_sw_align_scored32"
-        LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p),
-                                         gap_open, gap_extend, *outs), name)
-    r = dict(score=sc.value, end=(ei.value, ej.value))
-    if traceback:
-        r["beg"] = (bi.value, bj.value)
-        r["cigar"] = cig.value.decode()
-    return r
-
-
-def _entry(name: str, max_symbols: int) -> str:
-    """The library entry of a matrix-scored call: ``name`` itself, or its twin for up to 32 symbols."""
-    if max_symbols not in (8, 32):
-        raise ValueError("max_symbols must be 8 or 32")
-    return name if max_symbols == 8 else name + "32"
-
-
-def _nw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols=8):
-    """The scoring of nw_align / nw_align_batch: None when none of the four arguments is given (+1 / 0), else
-    (alphabet bytes, n_sym x n_sym int8 matrix, row = A's symbol).  ``match`` / ``mismatch`` (the other defaults to
-    1 / 0): the alphabet is the distinct symbols of ``seqs`` in first-seen order (more than ``max_symbols``, 8 or 32:
-    MsaError with the ALPHABET status).  ``matrix`` needs ``alphabet`` and excludes ``match`` / ``mismatch``
-    (ValueError).  With ``max_symbols=32`` and none of the four given, +1 / 0 over the symbols of ``seqs`` (the
-    32-symbol entries always take an alphabet and a matrix)."""
-    _entry("msa_nw_align_scored", max_symbols)  # (the ValueError of any other max_symbols)
-    if match is None and mismatch is None and alphabet is None and matrix is None:
-        if max_symbols == 8:
-            return None
-        match, mismatch = 1, 0
+def _scoring(kind, seqs, match, mismatch, alphabet, matrix, max_symbols):
+    """The scoring of one call (``max_symbols`` 8 or 32): None for the kind's plain entry, else (alphabet bytes,
+    n_sym x n_sym int8 matrix, row = A's symbol).  ``matrix`` needs ``alphabet`` and excludes ``match`` / ``mismatch``
+    (ValueError).  Without one, ``match`` / ``mismatch`` (None: 1 / 0) score the distinct symbols of ``seqs`` in
+    first-seen order, at most ``max_symbols`` -- one fewer for a kind whose kernels keep the highest code as the
+    out-of-matrix sentinel -- else MsaError with the ALPHABET status.  The plain entries take 8 symbols only: sw's
+    whenever there is no matrix (it has ``match`` / ``mismatch`` itself), nw's when nothing is given (+1 / 0)."""
     if matrix is not None:
         if match is not None or mismatch is not None:
             raise ValueError("give either matrix (with alphabet) or match / mismatch, not both")
@@ -348,9 +290,12 @@ def _nw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols=8):
         return alphabet, np.ascontiguousarray(S, dtype=np.int8)
     if alphabet is not None:
         raise ValueError("alphabet comes with matrix")
+    if kind.plain is not None and max_symbols == 8 and ("match" in kind.plain
+                                                          or (match is None and mismatch is None)):
+        return None
     seen = dict.fromkeys(b"".join(seqs))  # first-seen order
-    if len(seen) > max_symbols:
-        raise LB.MsaError(-2, "nw_align")
+    if len(seen) > max_symbols - kind.sentinel:
+        raise LB.MsaError(-2, "sw_align" if kind.sentinel else "nw_align")
     ma, mi = (1 if match is None else int(match)), (0 if mismatch is None else int(mismatch))
     if not (-128 <= ma <= 127 and -128 <= mi <= 127):
         raise LB.MsaError(-5, "nw_align")
@@ -358,6 +303,104 @@ def _nw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols=8):
     S = np.full((k, k), mi, dtype=np.int8)
     np.fill_diagonal(S, ma)
     return bytes(seen), S
+
+
+def _concat(seqs):
+    """(the sequences end to end, their offsets in that buffer, their lengths), the last two as int64 arrays."""
+    seqs = [_buf(s) for s in seqs]
+    n = np.array([len(s) for s in seqs], dtype=np.int64)
+    return b"".join(seqs), np.concatenate(([0], np.cumsum(n)[:-1])).astype(np.int64), n
+
+
+def _batch_in(As, Bs):
+    """(A buffer, B buffer, a_off, m, b_off, n as int64 arrays) of a batch; ``Bs`` one bytes object = shared by
+    every pair (sent once)."""
+    A, a_off, m = _concat(As)
+    if isinstance(Bs, (bytes, bytearray, str, memoryview)):
+        B = _buf(Bs)
+        n = np.full(len(m), len(B), dtype=np.int64)
+        b_off = np.zeros(len(m), dtype=np.int64)
+    else:
+        B, b_off, n = _concat(Bs)
+        if len(n) != len(m):
+            raise ValueError("Bs must be as long as As, or one bytes object shared by every pair")
+    return A, B, a_off, m, b_off, n
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _ref(a, i):
+    """A pointer to element ``i`` of the C-contiguous array ``a`` (None: NULL), as ctypes.byref gives one."""
+    if a is None:
+        return None
+    return C.byref(np.ctypeslib.as_ctypes_type(a.dtype).from_buffer(a.reshape(-1), i * a.itemsize))
+
+
+def _call(kind, single, vals, m, n, traceback, scored=True, wide=False, banded=False):
+    """One call of ``kind``'s single-pair or batch entry over the len(m) pairs whose input slots ``vals`` holds (pair p
+    is m[p] x n[p]) -> the list of their result dicts.  The outputs are arrays with one row per pair, which either
+    flavour of entry fills; the argument order is the entry's slot order."""
+    k = len(m)
+    name, slots = kind.entry(not single, scored, banded, wide)
+    outs = {o: np.zeros((k, 2), dtype=np.int64) if o in kind.pairs else np.zeros(k, dtype=np.int32)
+            for o in kind.outputs()}
+    coff = np.zeros(k + 1, dtype=np.int64)
+    cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
+    cig = C.create_string_buffer(cap) if traceback else None
+    vals = dict(vals, k=k, cigar=cig, cap=cap, cigar_off=_ptr(coff) if traceback else None)
+    for o, a in outs.items():
+        if o in kind.withheld and not traceback:
+            a = None
+        # (a single pair's {i, j}: one pointer, or one to each)
+        vals[o] = vals[o + "_i"] = _ref(a, 0)
+        vals[o + "_j"] = _ref(a, 1) if o in kind.pairs else None
+    LB.check(getattr(LB.lib(), name)(*(vals[s] for s in slots)), name)
+    res = []
+    for p in range(k):
+        r = kind.result(traceback, *(a[p] for a in outs.values()))
+        if traceback:
+            r["cigar"] = cig.value.decode() if single else cig.raw[coff[p]:coff[p + 1] - 1].decode()
+        res.append(r)
+    return res
+
+
+def _align(kind, single, As, Bs, gap_open, gap_extend, traceback, match, mismatch, alphabet, matrix, max_symbols,
+           band=None):
+    """The sequence-against-sequence kinds: ``As`` / ``Bs`` as for the batch functions, or one sequence each with
+    ``single``; ``band`` None = the entry without one.  -> the list of result dicts."""
+    if max_symbols not in (8, 32):
+        raise ValueError("max_symbols must be 8 or 32")
+    if single:
+        As, Bs = [As], [Bs]
+    elif len(As) == 0:
+        return []
+    A, B, a_off, m, b_off, n = _batch_in(As, Bs)
+    scoring = _scoring(kind, (A, B), match, mismatch, alphabet, matrix, max_symbols)
+    vals = dict(A=A, a_len=len(A), B=B, b_len=len(B), a_off=_ptr(a_off), m=_ptr(m), b_off=_ptr(b_off), n=_ptr(n),
+                gap_open=gap_open, gap_extend=gap_extend, band=band)
+    if scoring is None:
+        vals.update(match=1 if match is None else match, mismatch=0 if mismatch is None else mismatch)
+    else:
+        alpha, S = scoring
+        vals.update(alphabet=alpha, n_sym=len(alpha), sub=_ptr(S))
+    return _call(kind, single, vals, m, n, traceback, scoring is not None, max_symbols == 32,
+                 bool(kind.band) and band is not None)
+
+
+def sw_align(A, B, match=None, mismatch=None, gap_open=1, gap_extend=1, traceback=True, alphabet=None, matrix=None,
+             max_symbols=8):
+    """Smith-Waterman local alignment (build extension) -> dict(score, end, beg, cigar).
+
+    ``match`` / ``mismatch`` (None: 1 / 0) over the symbols of A and B, at most 7 (msa_sw_align).  Or ``alphabet``
+    (up to 7 distinct bytes) with ``matrix``, len(alphabet) x len(alphabet) scores in [-128, 127], ``matrix[a][b]`` =
+    alphabet[a] in A against alphabet[b] in B (msa_sw_align_scored); giving ``match`` or ``mismatch`` with it is a
+    ValueError, as for nw_align.  ``max_symbols=32`` (msa_sw_align_scored32; any value but 8 or 32 is a ValueError):
+    ``alphabet`` may hold up to 31 bytes -- proteins, IUPAC DNA --, and ``match`` / ``mismatch`` score the symbols of
+    A and B themselves, at most 31.  The matrix-scored calls run the stripe kernel whatever the pair's size."""
+    return _align(LB.KINDS["sw"], True, A, B, gap_open, gap_extend, traceback, match, mismatch, alphabet, matrix,
+                  max_symbols)[0]
 
 
 def nw_align(A, B, gap_open=3, gap_extend=1, band=-1, traceback=True, match=None, mismatch=None, alphabet=None,
@@ -377,48 +420,8 @@ def nw_align(A, B, gap_open=3, gap_extend=1, band=-1, traceback=True, match=None
     ``max_symbols=32`` (msa_nw_align_scored32; any value but 8 or 32 is a ValueError): proteins, IUPAC DNA --
     ``alphabet`` may hold up to 32 bytes, ``match`` / ``mismatch`` take up to 32 distinct symbols, and with none of
     the four given the call scores +1 / 0 over the symbols of A and B."""
-    A, B = _buf(A), _buf(B)
-    scoring = _nw_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
-    sc = C.c_int32()
-    cap = 4 * (len(A) + len(B)) + 16
-    cig = C.create_string_buffer(cap) if traceback else None
-    if scoring is None:
-        LB.check(LB.lib().msa_nw_align(A, len(A), B, len(B), gap_open, gap_extend, band, C.byref(sc), cig,
-                                       cap if traceback else 0), "msa_nw_align")
-    else:
-        alpha, S = scoring
-        name = _entry("msa_nw_align_scored", max_symbols)
-        LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p),
-                                         gap_open, gap_extend, band, C.byref(sc), cig, cap if traceback else 0), name)
-    r = dict(score=sc.value)
-    if traceback:
-        r["cigar"] = cig.value.decode()
-    return r
-
-
-def _batch_in(As, Bs):
-    """(A buffer, B buffer, a_off, m, b_off, n as int64 arrays) of a batch; ``Bs`` one bytes object = shared by
-    every pair (sent once)."""
-    As = [_buf(a) for a in As]
-    k = len(As)
-    m = np.array([len(a) for a in As], dtype=np.int64)
-    a_off = np.concatenate(([0], np.cumsum(m)[:-1])).astype(np.int64)
-    if isinstance(Bs, (bytes, bytearray, str, memoryview)):
-        B = _buf(Bs)
-        n = np.full(k, len(B), dtype=np.int64)
-        b_off = np.zeros(k, dtype=np.int64)
-    else:
-        Bs = [_buf(b) for b in Bs]
-        if len(Bs) != k:
-            raise ValueError("Bs must be as long as As, or one bytes object shared by every pair")
-        B = b"".join(Bs)
-        n = np.array([len(b) for b in Bs], dtype=np.int64)
-        b_off = np.concatenate(([0], np.cumsum(n)[:-1])).astype(np.int64)
-    return b"".join(As), B, a_off, m, b_off, n
-
-
-def _i64p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return _align(LB.KINDS["nw"], True, A, B, gap_open, gap_extend, traceback, match, mismatch, alphabet, matrix,
+                  max_symbols, band)[0]
 
 
 def sw_align_batch(As, Bs, match=None, mismatch=None, gap_open=1, gap_extend=1, traceback=True, alphabet=None,
@@ -430,39 +433,8 @@ def sw_align_batch(As, Bs, match=None, mismatch=None, gap_open=1, gap_extend=1, 
     plans (one fill and one walk launch per chunk of pairs that fits a quarter of the device budget).
     ``match`` / ``mismatch`` / ``alphabet`` / ``matrix`` / ``max_symbols`` as for sw_align (msa_sw_align_batch_scored,
     msa_sw_align_batch_scored32), over one alphabet for the whole call: up to 7 symbols, or 31."""
-    if max_symbols not in (8, 32):
-        raise ValueError("max_symbols must be 8 or 32")
-    if len(As) == 0:
-        return []
-    A, B, a_off, m, b_off, n = _batch_in(As, Bs)
-    scoring = _sw_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
-    k = len(m)
-    sc = np.zeros(k, dtype=np.int32)
-    end = np.zeros((k, 2), dtype=np.int64)
-    beg = np.zeros((k, 2), dtype=np.int64)
-    coff = np.zeros(k + 1, dtype=np.int64)
-    cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
-    cig = C.create_string_buffer(cap) if traceback else None
-    outs = (sc.ctypes.data_as(C.c_void_p), _i64p(end), _i64p(beg) if traceback else None, cig, cap,
-            _i64p(coff) if traceback else None)
-    if scoring is None:
-        LB.check(LB.lib().msa_sw_align_batch(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
-                                             1 if match is None else match, 0 if mismatch is None else mismatch,
-                                             gap_open, gap_extend, *outs), "msa_sw_align_batch")
-    else:
-        alpha, S = scoring
-        name = "msa_sw_align_batch_scored" if max_symbols == 8 else "msa_sw_align_batch_scored32"
-        LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
-                                         alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend, *outs),
-                 name)
-    out = []
-    for p in range(k):
-        r = dict(score=int(sc[p]), end=(int(end[p, 0]), int(end[p, 1])))
-        if traceback:
-            r["beg"] = (int(beg[p, 0]), int(beg[p, 1]))
-            r["cigar"] = cig.raw[coff[p]:coff[p + 1] - 1].decode()
-        out.append(r)
-    return out
+    return _align(LB.KINDS["sw"], False, As, Bs, gap_open, gap_extend, traceback, match, mismatch, alphabet, matrix,
+                  max_symbols)
 
 
 def nw_align_batch(As, Bs, gap_open=3, gap_extend=1, band=-1, traceback=True, match=None, mismatch=None,
@@ -474,41 +446,8 @@ def nw_align_batch(As, Bs, gap_open=3, gap_extend=1, band=-1, traceback=True, ma
     ``mismatch`` / ``alphabet`` / ``matrix`` as for nw_align (msa_nw_align_batch_scored); the alphabet of ``match`` /
     ``mismatch`` is the distinct symbols of all As, then all Bs, in first-seen order.  ``max_symbols=32`` as for
     nw_align (msa_nw_align_batch_scored32): up to 32 distinct symbols in the whole call."""
-    _entry("msa_nw_align_batch_scored", max_symbols)
-    if len(As) == 0:
-        return []
-    A, B, a_off, m, b_off, n = _batch_in(As, Bs)
-    scoring = _nw_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
-    k = len(m)
-    sc = np.zeros(k, dtype=np.int32)
-    coff = np.zeros(k + 1, dtype=np.int64)
-    cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
-    cig = C.create_string_buffer(cap) if traceback else None
-    if scoring is None:
-        LB.check(LB.lib().msa_nw_align_batch(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off),
-                                             _i64p(n), gap_open, gap_extend, band, sc.ctypes.data_as(C.c_void_p),
-                                             cig, cap, _i64p(coff) if traceback else None), "msa_nw_align_batch")
-    else:
-        alpha, S = scoring
-        name = _entry("msa_nw_align_batch_scored", max_symbols)
-        LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
-                                         alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend, band,
-                                         sc.ctypes.data_as(C.c_void_p), cig, cap,
-                                         _i64p(coff) if traceback else None), name)
-    out = []
-    for p in range(k):
-        r = dict(score=int(sc[p]))
-        if traceback:
-            r["cigar"] = cig.raw[coff[p]:coff[p + 1] - 1].decode()
-        out.append(r)
-    return out
-
-
-def _fit_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols=8):
-    """_nw_scoring, with +1 / 0 over the symbols of ``seqs`` when none of the four arguments is given (the fit
-    entries always take an alphabet and a matrix)."""
-    scoring = _nw_scoring(seqs, match, mismatch, alphabet, matrix, max_symbols)
-    return _nw_scoring(seqs, 1, 0, None, None, max_symbols) if scoring is None else scoring
+    return _align(LB.KINDS["nw"], False, As, Bs, gap_open, gap_extend, traceback, match, mismatch, alphabet, matrix,
+                  max_symbols, band)
 
 
 def fit_align(query, ref, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
@@ -522,20 +461,8 @@ def fit_align(query, ref, gap_open=3, gap_extend=1, traceback=True, match=None, 
     symbols; ``beg == end`` when the best alignment inserts the whole query.  ``traceback=False`` gives the score
     and ``end`` only (``beg`` is None).  Scoring as for nw_align: ``match`` / ``mismatch``, or ``alphabet`` with
     ``matrix``; with none given +1 / 0.  ``max_symbols=32`` (msa_fit_align32): up to 32 symbols, as for nw_align."""
-    A, B = _buf(query), _buf(ref)
-    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
-    name = _entry("msa_fit_align", max_symbols)
-    sc = C.c_int32()
-    bj, ej = C.c_int64(), C.c_int64()
-    cap = 4 * (len(A) + len(B)) + 16
-    cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open,
-                                     gap_extend, C.byref(sc), C.byref(bj), C.byref(ej), cig,
-                                     cap if traceback else 0), name)
-    r = dict(score=sc.value, beg=bj.value if traceback else None, end=ej.value)
-    if traceback:
-        r["cigar"] = cig.value.decode()
-    return r
+    return _align(LB.KINDS["fit"], True, query, ref, gap_open, gap_extend, traceback, match, mismatch, alphabet,
+                  matrix, max_symbols)[0]
 
 
 def fit_align_batch(queries, refs, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None,
@@ -546,36 +473,8 @@ def fit_align_batch(queries, refs, gap_open=3, gap_extend=1, traceback=True, mat
     exactly like nw_align_batch's ``Bs``; scoring as for fit_align, over one alphabet for the whole call (``match``
     / ``mismatch``: the distinct symbols of all queries, then all refs, in first-seen order).  ``max_symbols=32``
     (msa_fit_align_batch32): up to 32 symbols in the whole call."""
-    name = _entry("msa_fit_align_batch", max_symbols)
-    if len(queries) == 0:
-        return []
-    A, B, a_off, m, b_off, n = _batch_in(queries, refs)
-    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
-    k = len(m)
-    sc = np.zeros(k, dtype=np.int32)
-    be = np.zeros((k, 2), dtype=np.int64)
-    coff = np.zeros(k + 1, dtype=np.int64)
-    cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
-    cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
-                                     alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend,
-                                     sc.ctypes.data_as(C.c_void_p), _i64p(be), cig, cap,
-                                     _i64p(coff) if traceback else None), name)
-    out = []
-    for p in range(k):
-        r = dict(score=int(sc[p]), beg=int(be[p, 0]) if traceback else None, end=int(be[p, 1]))
-        if traceback:
-            r["cigar"] = cig.raw[coff[p]:coff[p + 1] - 1].decode()
-        out.append(r)
-    return out
-
-
-def _overlap_dict(score, beg, end, traceback, cigar):
-    r = dict(score=int(score), a_beg=int(beg[0]) if traceback else None, a_end=int(end[0]),
-             b_beg=int(beg[1]) if traceback else None, b_end=int(end[1]))
-    if traceback:
-        r["cigar"] = cigar
-    return r
+    return _align(LB.KINDS["fit"], False, queries, refs, gap_open, gap_extend, traceback, match, mismatch, alphabet,
+                  matrix, max_symbols)
 
 
 def overlap_align(A, B, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
@@ -590,17 +489,8 @@ def overlap_align(A, B, gap_open=3, gap_extend=1, traceback=True, match=None, mi
     ``a_beg == a_end == len(A)``, ``b_beg == b_end == 0`` and an empty CIGAR.  The CIGAR (start -> end, I consumes A,
     D consumes B) consumes exactly ``a_end - a_beg`` and ``b_end - b_beg``.  ``traceback=False`` gives the score and
     the two ends only (``a_beg`` and ``b_beg`` are None).  Scoring and ``max_symbols`` as for fit_align."""
-    A, B = _buf(A), _buf(B)
-    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
-    name = _entry("msa_overlap_align", max_symbols)
-    sc = C.c_int32()
-    beg, end = np.zeros(2, dtype=np.int64), np.zeros(2, dtype=np.int64)
-    cap = 4 * (len(A) + len(B)) + 16
-    cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open,
-                                     gap_extend, C.byref(sc), _i64p(beg), _i64p(end), cig,
-                                     cap if traceback else 0), name)
-    return _overlap_dict(sc.value, beg, end, traceback, cig.value.decode() if traceback else None)
+    return _align(LB.KINDS["overlap"], True, A, B, gap_open, gap_extend, traceback, match, mismatch, alphabet, matrix,
+                  max_symbols)[0]
 
 
 def overlap_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
@@ -611,33 +501,8 @@ def overlap_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=
     nw_align_batch's; scoring as for overlap_align, over one alphabet for the whole call (``match`` / ``mismatch``:
     the distinct symbols of all As, then all Bs, in first-seen order).  ``max_symbols=32``
     (msa_overlap_align_batch32): up to 32 symbols in the whole call."""
-    name = _entry("msa_overlap_align_batch", max_symbols)
-    if len(As) == 0:
-        return []
-    A, B, a_off, m, b_off, n = _batch_in(As, Bs)
-    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
-    k = len(m)
-    sc = np.zeros(k, dtype=np.int32)
-    beg = np.zeros((k, 2), dtype=np.int64)
-    end = np.zeros((k, 2), dtype=np.int64)
-    coff = np.zeros(k + 1, dtype=np.int64)
-    cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
-    cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
-                                     alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend,
-                                     sc.ctypes.data_as(C.c_void_p), _i64p(beg), _i64p(end), cig, cap,
-                                     _i64p(coff) if traceback else None), name)
-    return [_overlap_dict(sc[p], beg[p], end[p], traceback,
-                          cig.raw[coff[p]:coff[p + 1] - 1].decode() if traceback else None) for p in range(k)]
-
-
-def _extend_dict(score, end, gscore, traceback, cigar):
-    # (MSA_SCORE_NONE: a banded extension clipped the pair, so its fill never reached (m, n))
-    r = dict(score=int(score), a_end=int(end[0]), b_end=int(end[1]),
-             global_score=None if int(gscore) == LB.SCORE_NONE else int(gscore))
-    if traceback:
-        r["cigar"] = cigar
-    return r
+    return _align(LB.KINDS["overlap"], False, As, Bs, gap_open, gap_extend, traceback, match, mismatch, alphabet,
+                  matrix, max_symbols)
 
 
 def extend_align(A, B, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
@@ -660,18 +525,8 @@ def extend_align(A, B, gap_open=3, gap_extend=1, traceback=True, match=None, mis
     band`` hold no such cell: the call clips the longer sequence there, and ``global_score`` is then ``None`` (there
     is no end-to-end alignment inside the band); otherwise it is nw_align's under the same band.  A negative band
     other than the default -1 is an MsaError (ARG)."""
-    A, B = _buf(A), _buf(B)
-    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
-    name = _entry("msa_extend_align" if band == -1 else "msa_extend_align_banded", max_symbols)
-    bands = () if band == -1 else (int(band),)
-    sc, gs = C.c_int32(), C.c_int32()
-    end = np.zeros(2, dtype=np.int64)
-    cap = 4 * (len(A) + len(B)) + 16
-    cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open,
-                                     gap_extend, *bands, C.byref(sc), _i64p(end), C.byref(gs), cig,
-                                     cap if traceback else 0), name)
-    return _extend_dict(sc.value, end, gs.value, traceback, cig.value.decode() if traceback else None)
+    return _align(LB.KINDS["extend"], True, A, B, gap_open, gap_extend, traceback, match, mismatch, alphabet, matrix,
+                  max_symbols, None if band == -1 else int(band))[0]
 
 
 def extend_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
@@ -683,25 +538,8 @@ def extend_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=N
     the distinct symbols of all As, then all Bs, in first-seen order).  ``max_symbols=32``
     (msa_extend_align_batch32): up to 32 symbols in the whole call.  ``band`` >= 0 (msa_extend_align_batch_banded): one
     band for every pair, each clipped to it on its own, as extend_align does."""
-    name = _entry("msa_extend_align_batch" if band == -1 else "msa_extend_align_batch_banded", max_symbols)
-    bands = () if band == -1 else (int(band),)
-    if len(As) == 0:
-        return []
-    A, B, a_off, m, b_off, n = _batch_in(As, Bs)
-    alpha, S = _fit_scoring((A, B), match, mismatch, alphabet, matrix, max_symbols)
-    k = len(m)
-    sc = np.zeros(k, dtype=np.int32)
-    gs = np.zeros(k, dtype=np.int32)
-    end = np.zeros((k, 2), dtype=np.int64)
-    coff = np.zeros(k + 1, dtype=np.int64)
-    cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
-    cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(getattr(LB.lib(), name)(A, len(A), B, len(B), k, _i64p(a_off), _i64p(m), _i64p(b_off), _i64p(n),
-                                     alpha, len(alpha), S.ctypes.data_as(C.c_void_p), gap_open, gap_extend, *bands,
-                                     sc.ctypes.data_as(C.c_void_p), _i64p(end), gs.ctypes.data_as(C.c_void_p), cig, cap,
-                                     _i64p(coff) if traceback else None), name)
-    return [_extend_dict(sc[p], end[p], gs[p], traceback,
-                         cig.raw[coff[p]:coff[p + 1] - 1].decode() if traceback else None) for p in range(k)]
+    return _align(LB.KINDS["extend"], False, As, Bs, gap_open, gap_extend, traceback, match, mismatch, alphabet,
+                  matrix, max_symbols, None if band == -1 else int(band))
 
 
 _PROFILE_MODES = {"local": LB.PROFILE_LOCAL, "global": LB.PROFILE_GLOBAL, "fit": LB.PROFILE_FIT}
@@ -739,11 +577,15 @@ def _profile_in(profile, alphabet, mode):
     return _PROFILE_MODES[mode], np.ascontiguousarray(P, dtype=np.int8), alphabet
 
 
-def _profile_dict(score, beg, end, traceback, cigar):
-    r = dict(score=int(score), beg=(int(beg[0]), int(beg[1])) if traceback else None, end=(int(end[0]), int(end[1])))
-    if traceback:
-        r["cigar"] = cigar
-    return r
+def _profile_align(single, profile, seqs, alphabet, mode, gap_open, gap_extend, traceback):
+    """profile_align (``seqs`` one sequence, with ``single``) / profile_align_batch -> the list of result dicts."""
+    mo, P, alphabet = _profile_in(profile, alphabet, mode)
+    B, b_off, n = _concat([seqs] if single else seqs)
+    if len(n) == 0:
+        return []
+    vals = dict(mode=mo, prof=_ptr(P), rows=P.shape[0], B=B, b_len=len(B), b_off=_ptr(b_off), n=_ptr(n),
+                alphabet=alphabet, n_sym=len(alphabet), gap_open=gap_open, gap_extend=gap_extend)
+    return _call(LB.KINDS["profile"], single, vals, np.full(len(n), P.shape[0]), n, traceback)
 
 
 def profile_align(profile, seq, alphabet, mode="local", gap_open=3, gap_extend=1, traceback=True):
@@ -758,39 +600,10 @@ def profile_align(profile, seq, alphabet, mode="local", gap_open=3, gap_extend=1
     symbol of ``seq``.  ``traceback=False`` gives the score and ``end`` only (``beg`` is None).  A gap of L costs
     (gap_open - gap_extend) + gap_extend * L.  Building the profile from a multiple alignment is the caller's job;
     profile_from_matrix gives the one a single sequence has under a substitution matrix."""
-    mo, P, alphabet = _profile_in(profile, alphabet, mode)
-    B = _buf(seq)
-    sc = C.c_int32()
-    beg, end = np.zeros(2, dtype=np.int64), np.zeros(2, dtype=np.int64)
-    cap = 4 * (P.shape[0] + len(B)) + 16
-    cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(LB.lib().msa_profile_align(mo, P.ctypes.data_as(C.c_void_p), P.shape[0], B, len(B), alphabet,
-                                        len(alphabet), gap_open, gap_extend, C.byref(sc),
-                                        _i64p(beg) if traceback else None, _i64p(end), cig, cap if traceback else 0),
-             "msa_profile_align")
-    return _profile_dict(sc.value, beg, end, traceback, cig.value.decode() if traceback else None)
+    return _profile_align(True, profile, seq, alphabet, mode, gap_open, gap_extend, traceback)[0]
 
 
 def profile_align_batch(profile, seqs, alphabet, mode="local", gap_open=3, gap_extend=1, traceback=True):
     """One profile against many sequences (msa_profile_align_batch) -> a list of profile_align()'s dicts: the search
     case, every pair using all rows of ``profile``, which each plan of the call holds once."""
-    mo, P, alphabet = _profile_in(profile, alphabet, mode)
-    seqs = [_buf(b) for b in seqs]
-    k = len(seqs)
-    if k == 0:
-        return []
-    B = b"".join(seqs)
-    n = np.array([len(b) for b in seqs], dtype=np.int64)
-    b_off = np.concatenate(([0], np.cumsum(n)[:-1])).astype(np.int64)
-    sc = np.zeros(k, dtype=np.int32)
-    beg, end = np.zeros((k, 2), dtype=np.int64), np.zeros((k, 2), dtype=np.int64)
-    coff = np.zeros(k + 1, dtype=np.int64)
-    cap = int(4 * (k * P.shape[0] + n.sum()) + 16 * k) if traceback else 0
-    cig = C.create_string_buffer(cap) if traceback else None
-    LB.check(LB.lib().msa_profile_align_batch(mo, P.ctypes.data_as(C.c_void_p), P.shape[0], B, len(B), k, _i64p(b_off),
-                                              _i64p(n), alphabet, len(alphabet), gap_open, gap_extend,
-                                              sc.ctypes.data_as(C.c_void_p), _i64p(beg) if traceback else None,
-                                              _i64p(end), cig, cap, _i64p(coff) if traceback else None),
-             "msa_profile_align_batch")
-    return [_profile_dict(sc[p], beg[p], end[p], traceback,
-                          cig.raw[coff[p]:coff[p + 1] - 1].decode() if traceback else None) for p in range(k)]
+    return _profile_align(False, profile, seqs, alphabet, mode, gap_open, gap_extend, traceback)
