@@ -864,7 +864,8 @@ def test_sticky_error_word(dev, LB):
 
 
 def _mutated(rng, m, n):
-    """B = a mutated copy of A (substitutions + short indels), trimmed / extended to n."""
+    """B = A with a fifteenth of its symbols redrawn (substitutions only, no indels), cut to n or extended with random
+    symbols: the optimal paths are long diagonals."""
     A = rs(rng, m)
     b = bytearray(A[:n] if n <= m else A + rs(rng, n - m))
     for k in rng.choice(len(b), size=max(1, len(b) // 15), replace=False):
