@@ -37,6 +37,7 @@ NW_OVERLAP = 9
 NW_EXTEND = 10
 NW_EXTEND_BAND = 11
 SCORE_NONE = -(1 << 31)  # MSA_SCORE_NONE: no such score (a clipped banded extension's global score)
+XDROP_BAND_MAX = 640     # MSA_XDROP_BAND_MAX
 CELLS_NONE, CELLS_H, CELLS_DIR, CELLS_TAB = 0, 1, 2, 3
 # msa_profile_align's modes
 PROFILE_LOCAL, PROFILE_GLOBAL, PROFILE_FIT = 0, 1, 2
@@ -77,7 +78,7 @@ class PairResult(C.Structure):
 # api.py the call.
 _INT_SLOTS = {"mode": C.c_int, "a_len": C.c_size_t, "b_len": C.c_size_t, "rows": C.c_size_t, "n_sym": C.c_size_t,
               "cap": C.c_size_t, "k": C.c_int64, "band": C.c_int64, "match": C.c_int32, "mismatch": C.c_int32,
-              "gap_open": C.c_int32, "gap_extend": C.c_int32}
+              "gap_open": C.c_int32, "gap_extend": C.c_int32, "xdrop": C.c_int32}
 
 
 @dataclass(frozen=True)
@@ -96,20 +97,24 @@ class Kind:
     plain: Optional[Tuple[str, ...]] = None
     sentinel: bool = False                       # the highest code is kept free: one symbol fewer than max_symbols
     band: Optional[str] = None                   # None: no band; "": in every entry; else the suffix of those with one
+    # the suffix, in place of the band's, of the entries that stop by X-drop: `xdrop` follows `band`, and an int64
+    # `diagonals` per pair follows the scores
+    xdrop: Optional[str] = None
 
-    def outputs(self):
-        return ("score",) + self.pairs + (("global_score",) if self.score2 else ())
+    def outputs(self, xdrop=False):
+        return ("score",) + self.pairs + (("global_score",) if self.score2 else ()) + (("diagonals",) if xdrop else ())
 
-    def entry(self, batch, scored=True, banded=False, wide=False):
+    def entry(self, batch, scored=True, banded=False, wide=False, xdrop=False):
         """(C name, argument slots in C order) of one entry."""
+        banded = banded or xdrop
         name = (f"msa_{self.name}_align" + "_batch" * batch + "_scored" * (scored and self.plain is not None)
-                + (self.band if banded else "") + "32" * wide)
+                + (self.xdrop if xdrop else self.band if banded else "") + "32" * wide)
         slots = self.head + ("B", "b_len")
         if batch:
             slots += ("k",) + (("a_off", "m") if self.head[0] == "A" else ()) + ("b_off", "n")
         slots += self.matrix if scored else self.plain
-        slots += ("gap_open", "gap_extend") + (("band",) if banded or self.band == "" else ())
-        for o in self.outputs():
+        slots += ("gap_open", "gap_extend") + (("band",) if banded or self.band == "" else ()) + ("xdrop",) * xdrop
+        for o in self.outputs(xdrop):
             slots += (o + "_i", o + "_j") if o in self.pairs and self.split and not batch else (o,)
         return name, slots + ("cigar", "cap") + (("cigar_off",) if batch else ())
 
@@ -120,6 +125,8 @@ class Kind:
                 for banded in (False, True) if self.band else (False,):
                     for wide in (False, True) if scored and "sub" in self.matrix else (False,):
                         yield self.entry(batch, scored, banded, wide)
+                        if banded and self.xdrop:
+                            yield self.entry(batch, scored, banded, wide, xdrop=True)
 
 
 def _ij(c):
@@ -139,10 +146,13 @@ def _overlap_result(tb, score, beg, end):
                 b_beg=int(beg[1]) if tb else None, b_end=int(end[1]))
 
 
-def _extend_result(tb, score, end, gscore):
-    # (MSA_SCORE_NONE: a banded extension clipped the pair, so its fill never reached (m, n))
-    return dict(score=int(score), a_end=int(end[0]), b_end=int(end[1]),
-                global_score=None if int(gscore) == SCORE_NONE else int(gscore))
+def _extend_result(tb, score, end, gscore, diagonals=None):
+    # (MSA_SCORE_NONE: a banded extension clipped the pair, or X-drop stopped it, so its fill never reached (m, n))
+    r = dict(score=int(score), a_end=int(end[0]), b_end=int(end[1]),
+             global_score=None if int(gscore) == SCORE_NONE else int(gscore))
+    if diagonals is not None:
+        r["diagonals"] = int(diagonals)
+    return r
 
 
 def _profile_result(tb, score, beg, end):
@@ -155,7 +165,7 @@ KINDS = {kind.name: kind for kind in (
     Kind("nw", lambda tb, score: dict(score=int(score)), plain=(), band=""),
     Kind("fit", _fit_result, pairs=("beg_end",), split=True),
     Kind("overlap", _overlap_result, pairs=("beg", "end")),
-    Kind("extend", _extend_result, pairs=("end",), score2=True, band="_banded"),
+    Kind("extend", _extend_result, pairs=("end",), score2=True, band="_banded", xdrop="_xdrop"),
     # (mode, prof, rows) for A; the profile is its own scoring, so there is no matrix and no 32-symbol twin
     Kind("profile", _profile_result, pairs=("beg", "end"), withheld=("beg",), head=("mode", "prof", "rows"),
          matrix=("alphabet", "n_sym")),
@@ -227,6 +237,8 @@ def lib() -> C.CDLL:
     L.msa_plan_set_timing.argtypes = [P, i32]
     L.msa_encode_pair.argtypes = [P, sz, P, sz, P, P]
     L.msa_extend_band_clip.argtypes = [i64, i64, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.msa_xdrop_extend_run.argtypes = [P, P, i64, P, P, P, P, P, i32, i32, i32, i32, i32, i32, P, P, P, P]
+    L.msa_xdrop_extend_walk.argtypes = [i64, i32, P, P, P, P, P, P, P]
     # the alignment entries: every entry of every kind, from the kind's own argument order
     for kind in KINDS.values():
         for name, slots in kind.entries():
@@ -266,5 +278,7 @@ EXPORTED = [
     "msa_extend_align", "msa_extend_align_batch", "msa_extend_align32", "msa_extend_align_batch32",
     "msa_extend_align_banded", "msa_extend_align_batch_banded", "msa_extend_align_banded32",
     "msa_extend_align_batch_banded32", "msa_extend_band_clip",
+    "msa_extend_align_xdrop", "msa_extend_align_batch_xdrop", "msa_extend_align_xdrop32",
+    "msa_extend_align_batch_xdrop32", "msa_xdrop_extend_run", "msa_xdrop_extend_walk",
     "msa_plan_create_profile", "msa_profile_align", "msa_profile_align_batch",
 ]

@@ -338,14 +338,14 @@ def _ref(a, i):
     return C.byref(np.ctypeslib.as_ctypes_type(a.dtype).from_buffer(a.reshape(-1), i * a.itemsize))
 
 
-def _call(kind, single, vals, m, n, traceback, scored=True, wide=False, banded=False):
+def _call(kind, single, vals, m, n, traceback, scored=True, wide=False, banded=False, xdrop=False):
     """One call of ``kind``'s single-pair or batch entry over the len(m) pairs whose input slots ``vals`` holds (pair p
     is m[p] x n[p]) -> the list of their result dicts.  The outputs are arrays with one row per pair, which either
     flavour of entry fills; the argument order is the entry's slot order."""
     k = len(m)
-    name, slots = kind.entry(not single, scored, banded, wide)
-    outs = {o: np.zeros((k, 2), dtype=np.int64) if o in kind.pairs else np.zeros(k, dtype=np.int32)
-            for o in kind.outputs()}
+    name, slots = kind.entry(not single, scored, banded, wide, xdrop)
+    outs = {o: np.zeros((k, 2), dtype=np.int64) if o in kind.pairs
+            else np.zeros(k, dtype=np.int64 if o == "diagonals" else np.int32) for o in kind.outputs(xdrop)}
     coff = np.zeros(k + 1, dtype=np.int64)
     cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
     cig = C.create_string_buffer(cap) if traceback else None
@@ -367,11 +367,14 @@ def _call(kind, single, vals, m, n, traceback, scored=True, wide=False, banded=F
 
 
 def _align(kind, single, As, Bs, gap_open, gap_extend, traceback, match, mismatch, alphabet, matrix, max_symbols,
-           band=None):
+           band=None, xdrop=None):
     """The sequence-against-sequence kinds: ``As`` / ``Bs`` as for the batch functions, or one sequence each with
-    ``single``; ``band`` None = the entry without one.  -> the list of result dicts."""
+    ``single``; ``band`` None = the entry without one; ``xdrop`` None = the entry without X-drop termination.  -> the
+    list of result dicts."""
     if max_symbols not in (8, 32):
         raise ValueError("max_symbols must be 8 or 32")
+    if xdrop is not None and band is None:
+        raise ValueError("xdrop needs a band")
     if single:
         As, Bs = [As], [Bs]
     elif len(As) == 0:
@@ -379,14 +382,18 @@ def _align(kind, single, As, Bs, gap_open, gap_extend, traceback, match, mismatc
     A, B, a_off, m, b_off, n = _batch_in(As, Bs)
     scoring = _scoring(kind, (A, B), match, mismatch, alphabet, matrix, max_symbols)
     vals = dict(A=A, a_len=len(A), B=B, b_len=len(B), a_off=_ptr(a_off), m=_ptr(m), b_off=_ptr(b_off), n=_ptr(n),
-                gap_open=gap_open, gap_extend=gap_extend, band=band)
+                gap_open=gap_open, gap_extend=gap_extend, band=band, xdrop=xdrop)
     if scoring is None:
         vals.update(match=1 if match is None else match, mismatch=0 if mismatch is None else mismatch)
     else:
         alpha, S = scoring
         vals.update(alphabet=alpha, n_sym=len(alpha), sub=_ptr(S))
-    return _call(kind, single, vals, m, n, traceback, scoring is not None, max_symbols == 32,
-                 bool(kind.band) and band is not None)
+    res = _call(kind, single, vals, m, n, traceback, scoring is not None, max_symbols == 32,
+                bool(kind.band) and band is not None, xdrop is not None)
+    if xdrop is not None:  # (the fill stopped before the clipped pair's last anti-diagonal)
+        for r, mp, np_ in zip(res, m, n):
+            r["dropped"] = r["diagonals"] < min(int(mp), int(np_) + band) + min(int(np_), int(mp) + band)
+    return res
 
 
 def sw_align(A, B, match=None, mismatch=None, gap_open=1, gap_extend=1, traceback=True, alphabet=None, matrix=None,
@@ -506,7 +513,7 @@ def overlap_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=
 
 
 def extend_align(A, B, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
-                 matrix=None, max_symbols=8, band=-1):
+                 matrix=None, max_symbols=8, band=-1, xdrop=None):
     """Extension alignment (build extension, msa_extend_align): the alignment starts at the first symbols of both
     sequences and may stop anywhere -> dict(score, a_end, b_end, global_score[, cigar]): the best-scoring pair of
     prefixes, ``A[:a_end]`` against ``B[:b_end]``.
@@ -524,22 +531,31 @@ def extend_align(A, B, gap_open=3, gap_extend=1, traceback=True, match=None, mis
     one with at most ``band`` net indels at every point.  Rows past ``len(B) + band`` and columns past ``len(A) +
     band`` hold no such cell: the call clips the longer sequence there, and ``global_score`` is then ``None`` (there
     is no end-to-end alignment inside the band); otherwise it is nw_align's under the same band.  A negative band
-    other than the default -1 is an MsaError (ARG)."""
+    other than the default -1 is an MsaError (ARG).
+
+    ``xdrop`` (msa_extend_align_xdrop; needs ``band`` >= 0, else ValueError; at most ``_lib.XDROP_BAND_MAX``, else an
+    MsaError (UNSUPPORTED)): X-drop termination, BLAST's.  The fill goes anti-diagonal by anti-diagonal (``i + j``) and
+    stops after the first one at which the maxima of the last two anti-diagonals both lie more than ``xdrop`` (raw score
+    units) below the best score so far; cells on later anti-diagonals do not exist for the result.  The dict gains
+    ``diagonals`` (the last anti-diagonal filled) and ``dropped`` (the fill stopped before the clipped pair's last one;
+    ``global_score`` is then ``None``).  ``xdrop`` < 0 never stops: the banded call's result.  One wave fills one pair:
+    made for batches of short flanks, not for one long pair."""
     return _align(LB.KINDS["extend"], True, A, B, gap_open, gap_extend, traceback, match, mismatch, alphabet, matrix,
-                  max_symbols, None if band == -1 else int(band))[0]
+                  max_symbols, None if band == -1 else int(band), None if xdrop is None else int(xdrop))[0]
 
 
 def extend_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=None, mismatch=None, alphabet=None,
-                       matrix=None, max_symbols=8, band=-1):
+                       matrix=None, max_symbols=8, band=-1, xdrop=None):
     """A batch of extension alignments (msa_extend_align_batch) -> a list of extend_align()'s dicts.
 
     ``Bs``: a list as long as ``As``, or one bytes object every A is aligned against (uploaded once), exactly like
     nw_align_batch's; scoring as for extend_align, over one alphabet for the whole call (``match`` / ``mismatch``:
     the distinct symbols of all As, then all Bs, in first-seen order).  ``max_symbols=32``
     (msa_extend_align_batch32): up to 32 symbols in the whole call.  ``band`` >= 0 (msa_extend_align_batch_banded): one
-    band for every pair, each clipped to it on its own, as extend_align does."""
+    band for every pair, each clipped to it on its own, as extend_align does.  ``xdrop`` (msa_extend_align_batch_xdrop):
+    one X-drop for every pair, as for extend_align; each pair stops on its own."""
     return _align(LB.KINDS["extend"], False, As, Bs, gap_open, gap_extend, traceback, match, mismatch, alphabet,
-                  matrix, max_symbols, None if band == -1 else int(band))
+                  matrix, max_symbols, None if band == -1 else int(band), None if xdrop is None else int(xdrop))
 
 
 _PROFILE_MODES = {"local": LB.PROFILE_LOCAL, "global": LB.PROFILE_GLOBAL, "fit": LB.PROFILE_FIT}

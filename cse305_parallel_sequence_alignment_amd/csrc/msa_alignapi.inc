@@ -8,6 +8,7 @@
 //     msa_overlap_align, msa_overlap_align_batch, *32   a suffix of one sequence against a prefix of the other
 //     msa_extend_align, msa_extend_align_batch, *32     the best pair of prefixes (anchored start, free end)
 //     msa_extend_align_banded, ..._batch_banded, *32    ... inside a band, each pair clipped to it
+//     (msa_extend_align_xdrop, ..._batch_xdrop, *32     ... stopped by X-drop: msa_xdropapi.inc, through align_pairs)
 //     msa_profile_align, msa_profile_align_batch        a position-specific profile: local, global, fit
 // The host encodes the inputs, runs plans (the flow / band kernels behind msa_plan_run) and the device walks
 // (traceback_kernel, msa_plan_traceback_batch), and turns a walk's O(m + n) ops into a CIGAR.
@@ -316,13 +317,26 @@ int align_range(const AlignSpec& spec, int single, const GapBand& gb, bool want_
 
 const int64_t kPairLimit = int64_t(1) << 26;  // rows / columns of a pair (msa_sw_align has no limit of its own)
 
+// A banded extension with X-drop termination (msa_xdropapi.inc): its ranges of pairs run the one-wave-per-pair fill and
+// walk of msa_xdrop.hip, not a plan, admitted with the compact band form's bytes
+struct XDrop {
+  int32_t xdrop;
+  int64_t* diagonals;  // n_pairs, or nullptr
+};
+size_t footprint_xdrop(int64_t m, int64_t n, int band, bool dir);
+int xdrop_range(const AlignSpec& spec, const GapBand& gb, const XDrop& xd, bool want_tb, const uint8_t* ca,
+                const uint8_t* cb, const AlignIn& in, int64_t p0, int64_t p1, size_t bytes, const AlignOut& out,
+                std::string& all);
+
 // Every alignment entry: check the arguments (MSA_ERR_ARG; size_lim bounds m and n), the gap rule
 // (MSA_ERR_UNSUPPORTED), the band against the lengths (MSA_ERR_ARG; a banded extension clips instead), encode with
 // one symbol map for the call, A then B (MSA_ERR_ALPHABET), and only then ask for the device; then align_range chunk by chunk -- consecutive pairs
 // whose summed single-pair footprints fit a quarter of the device budget, at most 2^20 of them -- and hand out the
-// CIGARs.
+// CIGARs.  xd: a banded extension with X-drop termination -- the same checks in the same order, a band above
+// MSA_XDROP_BAND_MAX (after the band of the longest sequence stood in for a wider one) answered with the gap rule's
+// MSA_ERR_UNSUPPORTED, and every range through xdrop_range.
 int align_pairs(AlignSpec spec, int single, const AlignIn& in0, int64_t size_lim, int32_t gap_open,
-                int32_t gap_extend, int64_t band_in, const AlignOut& out) {
+                int32_t gap_extend, int64_t band_in, const AlignOut& out, const XDrop* xd = nullptr) {
   if (spec.status != MSA_OK) return spec.status;
   if ((!in0.A && !spec.prof) || !in0.B || !in0.a_off || !in0.m || !in0.b_off || !in0.n || in0.np < 1 ||
       (out.cigars && !out.cigar_off) || band_in < (spec.clip_to_band ? 0 : -1))
@@ -340,6 +354,7 @@ int align_pairs(AlignSpec spec, int single, const AlignIn& in0, int64_t size_lim
                                  gap_open < 0 || gap_extend < 0)
                               : (gap_extend < 0 || gap_open < gap_extend))
     return MSA_ERR_UNSUPPORTED;
+  if (xd && std::min(band_in, span_max) > MSA_XDROP_BAND_MAX) return MSA_ERR_UNSUPPORTED;
   if (!spec.banded) band_in = -1;
   std::vector<int64_t> cm, cn;  // a banded extension's sizes: every pair's in-band prefixes (offsets stay)
   if (spec.clip_to_band) {
@@ -366,6 +381,7 @@ int align_pairs(AlignSpec spec, int single, const AlignIn& in0, int64_t size_lim
   // (a profile call: every plan of it holds its pairs' rows of the profile, 32 B each)
   auto fp = [&](int64_t p) -> size_t {
     const size_t rows = spec.prof ? 32 * (size_t)in.m[p] : 0;
+    if (xd) return footprint_xdrop(in.m[p], in.n[p], gb.band, want_tb);
     if (spec.footprint == FOOT_BAND) return rows + footprint_nw(in.m[p], in.n[p], gb.band, want_tb);
     return rows + (want_tb ? footprint_dir(in.m[p], in.n[p]) : footprint_planes(in.m[p], in.n[p], 0, 1));
   };
@@ -377,8 +393,9 @@ int align_pairs(AlignSpec spec, int single, const AlignIn& in0, int64_t size_lim
     size_t bytes = fp(p0);
     p1 = p0 + 1;
     while (p1 < in.np && p1 - p0 < (int64_t(1) << 20) && bytes + fp(p1) <= quarter) bytes += fp(p1++);
-    if ((rc = align_range(spec, single, gb, want_tb, ca.data(), cb.data(), in, p0, p1, bytes, out, all)) != MSA_OK)
-      return rc;
+    rc = xd ? xdrop_range(spec, gb, *xd, want_tb, ca.data(), cb.data(), in, p0, p1, bytes, out, all)
+            : align_range(spec, single, gb, want_tb, ca.data(), cb.data(), in, p0, p1, bytes, out, all);
+    if (rc != MSA_OK) return rc;
   }
   // (a clipped pair has no H(m, n): its fill ended at (m', n'))
   for (int64_t p = 0; spec.clip_to_band && out.fin_h && p < in.np; ++p)

@@ -33,6 +33,7 @@
 #include "msa_rowsweep.hip"
 #include "msa_traceback.hip"
 #include "msa_tbatch.hip"
+#include "msa_xdrop.hip"
 
 using namespace msa;
 
@@ -923,3 +924,4 @@ int msa_plan_checksum(msa_plan* P, const int32_t* dH, int64_t pair, uint64_t* di
 #include "msa_refapi.inc"
 #include "msa_rowapi.inc"
 #include "msa_alignapi.inc"
+#include "msa_xdropapi.inc"

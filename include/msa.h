@@ -58,6 +58,11 @@
  *                        the same inside a band |i - j| <= band, the work bounded by m, n and the band alone (build
  *                        extension: MSA_NW_EXTEND_BAND plans -- the banded global kernel's cells and edge phases
  *                        under the extension's end-cell tracker; the clip rule that stands for |m - n| <= band)
+ *   msa_extend_align_xdrop, msa_extend_align_batch_xdrop, msa_extend_align_xdrop32,
+ *   msa_extend_align_batch_xdrop32, msa_xdrop_extend_run, msa_xdrop_extend_walk
+ *                        the banded extension with X-drop termination: the fill stops once the last two
+ *                        anti-diagonals fall more than xdrop below the best score (build extension: a kernel family
+ *                        of its own, one wave per pair, anti-diagonal by anti-diagonal; not a plan kind)
  *   msa_plan_create_scored32, msa_nw_align_scored32, msa_nw_align_batch_scored32, msa_fit_align32,
  *   msa_fit_align_batch32
  *                        MSA_NW_SCORED and MSA_NW_FIT over alphabets of up to 32 symbols (proteins, IUPAC DNA):
@@ -704,7 +709,8 @@ int msa_overlap_align_batch32(const char* A, size_t a_len, const char* B, size_t
  *   so a caller decides between clipping and aligning to the end without a second fill.
  *   Out of scope, each MSA_ERR_UNSUPPORTED at plan creation: any band other than -1 (the global plans' |m - n| <= band
  *   does not fit a free end), cells other than MSA_CELLS_DIR / MSA_CELLS_NONE, gap_extend < 0 or gap_open <
- *   gap_extend.  No Z-drop / X-drop termination: every cell is computed.  Such plans always run the stripe kernel
+ *   gap_extend.  No Z-drop / X-drop termination here: every cell is computed (inside a band:
+ *   msa_extend_align_xdrop below).  Such plans always run the stripe kernel
  *   (msa_plan_launch_info mode 0), one pair or a batch, never a split batch; msa_plan_format_info reports end-cell
  *   tracking 1 (compare-select: the tracked values may be negative, which the packed key cannot hold); and the
  *   value-range inequality of msa_plan_create_scored holds unchanged (the same sources, steps and -inf; the tracked
@@ -753,7 +759,8 @@ int msa_extend_align_batch32(const char* A, size_t a_len, const char* B, size_t 
  *     fin[0] is H(m', n'), as for any banded global plan.
  *   One band per call.  band = -1 is not this plan kind's: MSA_NW_EXTEND is untouched and keeps rejecting any band.
  *   Out of scope, each MSA_ERR_UNSUPPORTED at plan creation: band < 0, cells other than MSA_CELLS_DIR /
- *   MSA_CELLS_NONE, a profile (msa_plan_create_profile), gap_extend < 0 or gap_open < gap_extend.  No Z-drop; no band,
+ *   MSA_CELLS_NONE, a profile (msa_plan_create_profile), gap_extend < 0 or gap_open < gap_extend.  No termination in a plan
+ *   (msa_extend_align_xdrop below stops by X-drop, with a kernel of its own); no band,
  *   flow, chunked or split launch: every such plan runs the stripe kernel's exact launch (msa_plan_launch_info mode
  *   0), as every free-end plan does, with end-cell tracking 1.  The value-range inequality of msa_plan_create_scored
  *   holds unchanged (a banded global plan's sources and steps; the tracked maximum is a copy of an in-band cell).
@@ -782,6 +789,83 @@ int msa_extend_align_batch_banded32(const char* A, size_t a_len, const char* B, 
                                     const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
                                     int32_t gap_extend, int64_t band, int32_t* score, int64_t* end_ij,
                                     int32_t* global_score, char* cigars, size_t cigar_cap, int64_t* cigar_off);
+
+/* Banded extension alignment with X-drop termination (build extension; a kernel family of its own, msa_xdrop.hip: one
+ * wave per pair sweeps the band anti-diagonal by anti-diagonal and decides after each whether to go on -- not a plan
+ * kind: the stripe kernel's schedule is laid out before the launch and computes every cell).  This is the anti-diagonal
+ * X-drop of BLAST's gapped extension and LOGAN; ksw2's row-wise Z-drop has a diagonal-offset term, which stays out.
+ * Everything is MSA_NW_EXTEND_BAND's on the clipped pair (m', n') = msa_extend_band_clip(m, n, w): the cells, the banded
+ * borders, E / F / H, the direction byte and its tie rules, the value-range inequality.  X-drop adds a stopping rule:
+ *   d = i + j is a cell's anti-diagonal.  a(d) = the maximum of H over the in-band interior cells on d, -inf when d has
+ *   none (band 0, odd d; a(1) = -inf).  best(d) = max(0, a(2), ..., a(d)).
+ *   After anti-diagonal d, for d = 2 .. m' + n', the fill stops when   best(d) - max(a(d - 1), a(d)) > xdrop.
+ *   D is that d, or m' + n' when the rule never fires; cells with i + j > D do not exist for the result.  (Two
+ *   anti-diagonals on purpose: the main diagonal's cells lie on even d only, and a one-anti-diagonal rule would fire at
+ *   d = 3 for every xdrop below the gap-open cost.  With w >= 1 every d in [2, m' + n'] holds an in-band interior cell,
+ *   with w = 0 every even d does, so the maximum of the two is always finite.)
+ *   Result: score and end cell = the first maximum in ROW-MAJOR order over the in-band interior cells with i + j <= D
+ *   (not visit order: an equal value on a later anti-diagonal with a smaller row wins); a best <= 0 is the empty
+ *   extension exactly as for msa_extend_align_banded; the walk and the border gap are msa_extend_align_banded's (the
+ *   walk only meets cells with a smaller i + j: all of them were computed); diagonals = D, per pair; global_score is
+ *   MSA_SCORE_NONE when the pair was clipped or D < m' + n'.
+ *   xdrop is in raw score units; xdrop < 0 means never stop, and the results are then msa_extend_align_banded's in
+ *   every field.
+ * Caps: band <= MSA_XDROP_BAND_MAX (per pair three int32 anti-diagonals of 2 band + 4 in LDS, four pairs and 1 KiB of
+ * scores per workgroup: 62,656 B at the cap, inside a workgroup's 64 KiB, two workgroups per CU inside its 160 KiB);
+ * above it MSA_ERR_UNSUPPORTED.  Lengths have no cap beyond the value-range inequality: one wave fills one pair, so a
+ * long pair is simply slow.
+ * The entries: the *_banded twins' signatures with `xdrop` after `band` and `diagonals` (n_pairs entries, may be NULL)
+ * after `global_score`; the twins' order of checks -- band < 0 is MSA_ERR_ARG with the other arguments; the gap rule
+ * and a band above the cap (after the band of the call's longest sequence stood in for a wider one, which holds the
+ * same cells) are MSA_ERR_UNSUPPORTED; then the alphabet, and only then the device --; each pair clipped, one symbol
+ * map for the call, a shared B uploaded once, chunks within a quarter of the budget, admission with the compact band
+ * form's (2 band + 1)(m' + 1) bytes per pair.  Out of scope: ksw2's diagonal-offset term, per-pair bands or xdrop,
+ * X-drop for the unbanded extension and for profiles, several waves on one long pair, plan objects. */
+#define MSA_XDROP_BAND_MAX 640
+int msa_extend_align_xdrop(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                           const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band, int32_t xdrop,
+                           int32_t* score, int64_t* end_ij, int32_t* global_score, int64_t* diagonals, char* cigar,
+                           size_t cigar_cap);
+int msa_extend_align_batch_xdrop(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                                 const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                                 const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                                 int32_t gap_extend, int64_t band, int32_t xdrop, int32_t* score, int64_t* end_ij,
+                                 int32_t* global_score, int64_t* diagonals, char* cigars, size_t cigar_cap,
+                                 int64_t* cigar_off);
+int msa_extend_align_xdrop32(const char* A0, size_t m, const char* B0, size_t n, const char* alphabet, size_t n_sym,
+                             const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band, int32_t xdrop,
+                             int32_t* score, int64_t* end_ij, int32_t* global_score, int64_t* diagonals, char* cigar,
+                             size_t cigar_cap);
+int msa_extend_align_batch_xdrop32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                                   const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                                   const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                                   int32_t gap_extend, int64_t band, int32_t xdrop, int32_t* score, int64_t* end_ij,
+                                   int32_t* global_score, int64_t* diagonals, char* cigars, size_t cigar_cap,
+                                   int64_t* cigar_off);
+/* The device-resident form the entries above are built on: asynchronous on `stream`, no allocation, no host sync.
+ * dA, dB: device codes (0..31); d_m, d_n, d_a_off, d_b_off: device arrays of n_pairs int64, pair p being
+ * dA[a_off[p] .. + m[p]) against dB[b_off[p] .. + n[p]) with CLIPPED sizes, |m - n| <= band (else that pair's status is
+ * MSA_ERR_ARG; outside the value-range inequality: MSA_ERR_UNSUPPORTED; such a pair is not filled).  d_sub32: DEVICE
+ * table of 1,024 int8 at stride 32, d_sub32[32 a + b] = A's code a against B's code b, or NULL: match / mismatch (in
+ * [-128, 127]).  d_dir (may be NULL: no bytes): the direction bytes in a compact band form, cell (i, j) of pair p at
+ * d_dir[d_dir_off[p] + i (2 band + 1) + (j - i + band)], rows 0 .. m: (2 band + 1)(m + 1) bytes per pair; the format is
+ * msa_plan_traceback_nw's; bytes of cells past D, of borders and outside the band are not written.
+ * d_res: 8 int64 per pair, {score, end_i, end_j, D, H(m, n) or MSA_SCORE_NONE when D < m + n, status, in-band interior
+ * cells computed (those with i + j <= D), 0}.
+ * Host-side errors: a NULL array, n_pairs < 1 or band < 0: MSA_ERR_ARG; gap_extend < 0, gap_open < gap_extend or band >
+ * MSA_XDROP_BAND_MAX: MSA_ERR_UNSUPPORTED; then the device.
+ * msa_xdrop_extend_walk, after it on the same stream: every pair's walk from its end cell (d_res) over those bytes,
+ * one wave per pair; d_ops / d_ops_off / d_info[8 per pair] are msa_plan_traceback_batch's contract (ops end -> start,
+ * {n_ops, i + 1, j + 1, status, 0, 0, 0, 0}, (i, j) the border cell where the walk stopped; the caller appends the global
+ * border gap; the empty extension is no walk).  Every walk ends within 2 (end_i + end_j) + 4 steps whatever bytes
+ * d_dir holds (MSA_ERR_TIMEOUT; a step out of the band or a byte without a predecessor: MSA_ERR_NOMATCH). */
+int msa_xdrop_extend_run(const uint8_t* dA, const uint8_t* dB, int64_t n_pairs, const int64_t* d_m,
+                         const int64_t* d_n, const int64_t* d_a_off, const int64_t* d_b_off, const int8_t* d_sub32,
+                         int32_t match, int32_t mismatch, int32_t gap_open, int32_t gap_extend, int32_t band,
+                         int32_t xdrop, uint8_t* d_dir, const int64_t* d_dir_off, int64_t* d_res, void* stream);
+int msa_xdrop_extend_walk(int64_t n_pairs, int32_t band, const uint8_t* d_dir, const int64_t* d_dir_off,
+                          const int64_t* d_res, uint8_t* d_ops, const int64_t* d_ops_off, int64_t* d_info,
+                          void* stream);
 
 /* The four matrix-scored entries above for alphabets of up to 32 symbols (proteins with B Z X *, IUPAC DNA): the
  * signatures of their 8-symbol twins, 1 <= n_sym <= 32, sub = n_sym x n_sym.  With n_sym <= 8 a call builds exactly
