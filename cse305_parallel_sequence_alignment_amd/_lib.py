@@ -78,7 +78,8 @@ class PairResult(C.Structure):
 # api.py the call.
 _INT_SLOTS = {"mode": C.c_int, "a_len": C.c_size_t, "b_len": C.c_size_t, "rows": C.c_size_t, "n_sym": C.c_size_t,
               "cap": C.c_size_t, "k": C.c_int64, "band": C.c_int64, "match": C.c_int32, "mismatch": C.c_int32,
-              "gap_open": C.c_int32, "gap_extend": C.c_int32, "xdrop": C.c_int32}
+              "gap_open": C.c_int32, "gap_extend": C.c_int32, "xdrop": C.c_int32,
+              "seed_a0": C.c_int64, "seed_b0": C.c_int64, "seed_len0": C.c_int64}
 
 
 @dataclass(frozen=True)
@@ -98,20 +99,29 @@ class Kind:
     sentinel: bool = False                       # the highest code is kept free: one symbol fewer than max_symbols
     band: Optional[str] = None                   # None: no band; "": in every entry; else the suffix of those with one
     # the suffix, in place of the band's, of the entries that stop by X-drop: `xdrop` follows `band`, and an int64
-    # `diagonals` per pair follows the scores
+    # `diagonals` per pair follows the scores; "": every entry stops by X-drop
     xdrop: Optional[str] = None
+    # int64 inputs after the sequences, one per pair: arrays in a batch entry (after `n`), values in a single-pair
+    # entry (slot name + "0")
+    extra: Tuple[str, ...] = ()
+    # both flanks of a seed: an int32 `flank_score` follows the {i, j} outputs, and it and `diagonals` hold two
+    # entries per pair, {left, right}
+    flanks: bool = False
 
     def outputs(self, xdrop=False):
-        return ("score",) + self.pairs + (("global_score",) if self.score2 else ()) + (("diagonals",) if xdrop else ())
+        return (("score",) + self.pairs + (("global_score",) if self.score2 else ())
+                + (("flank_score",) if self.flanks else ()) + (("diagonals",) if xdrop or self.xdrop == "" else ()))
 
     def entry(self, batch, scored=True, banded=False, wide=False, xdrop=False):
         """(C name, argument slots in C order) of one entry."""
+        xdrop = xdrop or self.xdrop == ""
         banded = banded or xdrop
         name = (f"msa_{self.name}_align" + "_batch" * batch + "_scored" * (scored and self.plain is not None)
                 + (self.xdrop if xdrop else self.band if banded else "") + "32" * wide)
         slots = self.head + ("B", "b_len")
         if batch:
             slots += ("k",) + (("a_off", "m") if self.head[0] == "A" else ()) + ("b_off", "n")
+        slots += self.extra if batch else tuple(x + "0" for x in self.extra)
         slots += self.matrix if scored else self.plain
         slots += ("gap_open", "gap_extend") + (("band",) if banded or self.band == "" else ()) + ("xdrop",) * xdrop
         for o in self.outputs(xdrop):
@@ -155,6 +165,13 @@ def _extend_result(tb, score, end, gscore, diagonals=None):
     return r
 
 
+def _seed_result(tb, score, beg, end, flank, diagonals):
+    # (api.seed_align adds each flank's end cell and `dropped`, which need the seed's coordinates)
+    left, right = (dict(score=int(flank[f]), diagonals=int(diagonals[f])) for f in (0, 1))
+    return dict(score=int(score), a_beg=int(beg[0]), b_beg=int(beg[1]), a_end=int(end[0]), b_end=int(end[1]),
+                seed_score=int(score) - int(flank[0]) - int(flank[1]), left=left, right=right)
+
+
 def _profile_result(tb, score, beg, end):
     return dict(score=int(score), beg=_ij(beg) if tb else None, end=_ij(end))
 
@@ -166,6 +183,9 @@ KINDS = {kind.name: kind for kind in (
     Kind("fit", _fit_result, pairs=("beg_end",), split=True),
     Kind("overlap", _overlap_result, pairs=("beg", "end")),
     Kind("extend", _extend_result, pairs=("end",), score2=True, band="_banded", xdrop="_xdrop"),
+    # one seed per pair and both of its flanks: a band and an xdrop in every entry
+    Kind("seed", _seed_result, pairs=("beg", "end"), band="", xdrop="", extra=("seed_a", "seed_b", "seed_len"),
+         flanks=True),
     # (mode, prof, rows) for A; the profile is its own scoring, so there is no matrix and no 32-symbol twin
     Kind("profile", _profile_result, pairs=("beg", "end"), withheld=("beg",), head=("mode", "prof", "rows"),
          matrix=("alphabet", "n_sym")),
@@ -239,6 +259,7 @@ def lib() -> C.CDLL:
     L.msa_extend_band_clip.argtypes = [i64, i64, i64, C.POINTER(i64), C.POINTER(i64)]
     L.msa_xdrop_extend_run.argtypes = [P, P, i64, P, P, P, P, P, i32, i32, i32, i32, i32, i32, P, P, P, P]
     L.msa_xdrop_extend_walk.argtypes = [i64, i32, P, P, P, P, P, P, P]
+    L.msa_xdrop_flank_run.argtypes = [P, P, i64, P, P, P, P, P, P, i32, i32, i32, i32, i32, i32, P, P, P, P]
     # the alignment entries: every entry of every kind, from the kind's own argument order
     for kind in KINDS.values():
         for name, slots in kind.entries():
@@ -281,4 +302,5 @@ EXPORTED = [
     "msa_extend_align_xdrop", "msa_extend_align_batch_xdrop", "msa_extend_align_xdrop32",
     "msa_extend_align_batch_xdrop32", "msa_xdrop_extend_run", "msa_xdrop_extend_walk",
     "msa_plan_create_profile", "msa_profile_align", "msa_profile_align_batch",
+    "msa_xdrop_flank_run", "msa_seed_align", "msa_seed_align_batch", "msa_seed_align32", "msa_seed_align_batch32",
 ]

@@ -345,7 +345,8 @@ def _call(kind, single, vals, m, n, traceback, scored=True, wide=False, banded=F
     k = len(m)
     name, slots = kind.entry(not single, scored, banded, wide, xdrop)
     outs = {o: np.zeros((k, 2), dtype=np.int64) if o in kind.pairs
-            else np.zeros(k, dtype=np.int64 if o == "diagonals" else np.int32) for o in kind.outputs(xdrop)}
+            else np.zeros((k, 2) if kind.flanks and o in ("flank_score", "diagonals") else k,
+                          dtype=np.int64 if o == "diagonals" else np.int32) for o in kind.outputs(xdrop)}
     coff = np.zeros(k + 1, dtype=np.int64)
     cap = int(4 * (m.sum() + n.sum()) + 16 * k) if traceback else 0
     cig = C.create_string_buffer(cap) if traceback else None
@@ -367,10 +368,11 @@ def _call(kind, single, vals, m, n, traceback, scored=True, wide=False, banded=F
 
 
 def _align(kind, single, As, Bs, gap_open, gap_extend, traceback, match, mismatch, alphabet, matrix, max_symbols,
-           band=None, xdrop=None):
+           band=None, xdrop=None, extra=None):
     """The sequence-against-sequence kinds: ``As`` / ``Bs`` as for the batch functions, or one sequence each with
-    ``single``; ``band`` None = the entry without one; ``xdrop`` None = the entry without X-drop termination.  -> the
-    list of result dicts."""
+    ``single``; ``band`` None = the entry without one; ``xdrop`` None = the entry without X-drop termination;
+    ``extra``: the kind's int64 inputs per pair, name -> array (a single entry takes element 0).  -> the list of
+    result dicts."""
     if max_symbols not in (8, 32):
         raise ValueError("max_symbols must be 8 or 32")
     if xdrop is not None and band is None:
@@ -383,6 +385,10 @@ def _align(kind, single, As, Bs, gap_open, gap_extend, traceback, match, mismatc
     scoring = _scoring(kind, (A, B), match, mismatch, alphabet, matrix, max_symbols)
     vals = dict(A=A, a_len=len(A), B=B, b_len=len(B), a_off=_ptr(a_off), m=_ptr(m), b_off=_ptr(b_off), n=_ptr(n),
                 gap_open=gap_open, gap_extend=gap_extend, band=band, xdrop=xdrop)
+    for name, x in (extra or {}).items():
+        if len(x) != len(m):
+            raise ValueError(f"{name} must hold one entry per pair")
+        vals[name], vals[name + "0"] = _ptr(x), int(x[0])
     if scoring is None:
         vals.update(match=1 if match is None else match, mismatch=0 if mismatch is None else mismatch)
     else:
@@ -390,10 +396,15 @@ def _align(kind, single, As, Bs, gap_open, gap_extend, traceback, match, mismatc
         vals.update(alphabet=alpha, n_sym=len(alpha), sub=_ptr(S))
     res = _call(kind, single, vals, m, n, traceback, scoring is not None, max_symbols == 32,
                 bool(kind.band) and band is not None, xdrop is not None)
-    if xdrop is not None:  # (the fill stopped before the clipped pair's last anti-diagonal)
+    if xdrop is not None and not kind.flanks:  # (the fill stopped before the clipped pair's last anti-diagonal)
         for r, mp, np_ in zip(res, m, n):
-            r["dropped"] = r["diagonals"] < min(int(mp), int(np_) + band) + min(int(np_), int(mp) + band)
+            r["dropped"] = _dropped(r["diagonals"], int(mp), int(np_), band)
     return res
+
+
+def _dropped(diagonals, m, n, band):
+    """The fill of an m x n extension stopped before its clipped pair's last anti-diagonal."""
+    return diagonals < min(m, n + band) + min(n, m + band)
 
 
 def sw_align(A, B, match=None, mismatch=None, gap_open=1, gap_extend=1, traceback=True, alphabet=None, matrix=None,
@@ -556,6 +567,58 @@ def extend_align_batch(As, Bs, gap_open=3, gap_extend=1, traceback=True, match=N
     one X-drop for every pair, as for extend_align; each pair stops on its own."""
     return _align(LB.KINDS["extend"], False, As, Bs, gap_open, gap_extend, traceback, match, mismatch, alphabet,
                   matrix, max_symbols, None if band == -1 else int(band), None if xdrop is None else int(xdrop))
+
+
+def _seed(single, As, Bs, seed_a, seed_b, seed_len, band, xdrop, gap_open, gap_extend, traceback, match, mismatch,
+          alphabet, matrix, max_symbols):
+    """seed_align / seed_align_batch: the call through _align, then each flank's end cell and ``dropped`` from the
+    seed's coordinates (an empty flank is never dropped)."""
+    sa, sb, sl = (np.atleast_1d(np.asarray(x, dtype=np.int64)) for x in (seed_a, seed_b, seed_len))
+    band = -1 if band is None else int(band)  # (no band: the entries' MSA_ERR_ARG)
+    res = _align(LB.KINDS["seed"], single, As, Bs, gap_open, gap_extend, traceback, match, mismatch, alphabet, matrix,
+                 max_symbols, band, int(xdrop), extra=dict(seed_a=sa, seed_b=sb, seed_len=sl))
+    lens = [(len(_buf(As)), len(_buf(Bs)))] if single else \
+        [(len(_buf(a)), len(_buf(Bs if isinstance(Bs, (bytes, bytearray, str, memoryview)) else Bs[p])))
+         for p, a in enumerate(As)]
+    for r, (m, n), a, b, k in zip(res, lens, sa.tolist(), sb.tolist(), sl.tolist()):
+        r["left"].update(a_end=a - r["a_beg"], b_end=b - r["b_beg"])
+        r["right"].update(a_end=r["a_end"] - a - k, b_end=r["b_end"] - b - k)
+        for f, fm, fn in ((r["left"], a, b), (r["right"], m - a - k, n - b - k)):
+            f["dropped"] = fm > 0 and fn > 0 and _dropped(f["diagonals"], fm, fn, band)
+    return res
+
+
+def seed_align(A, B, seed_a, seed_b, seed_len, band, xdrop=-1, gap_open=3, gap_extend=1, traceback=True, match=None,
+               mismatch=None, alphabet=None, matrix=None, max_symbols=8):
+    """Seed extension (build extension, msa_seed_align): the alignment through the seed ``A[seed_a:seed_a+seed_len]``
+    against ``B[seed_b:seed_b+seed_len]``, extended on both flanks in one call -> dict(score, a_beg, b_beg, a_end,
+    b_end, seed_score, left, right[, cigar]): ``A[a_beg:a_end]`` against ``B[b_beg:b_end]``.
+
+    Each flank is exactly ``extend_align(..., band=band, xdrop=xdrop)`` of its two byte strings -- the right flank
+    ``A[seed_a+seed_len:]`` against ``B[seed_b+seed_len:]``, the left flank ``A[:seed_a][::-1]`` against
+    ``B[:seed_b][::-1]``, which the kernel reads backwards in place: nothing is reversed or copied.  ``left`` and
+    ``right`` are dict(score, a_end, b_end, diagonals, dropped) in the flank's own coordinates (``a_end`` symbols of A
+    away from the seed); a flank with no symbols on one side is not launched and is the empty extension (score 0,
+    ``a_end == b_end == diagonals == 0``, not dropped).  ``seed_score`` is the sum of the seed's column scores (it may
+    hold mismatches; ``seed_len=0`` is a bare anchor) and ``score = left + seed_score + right``.  The CIGAR (start ->
+    end, I consumes A, D consumes B) consumes exactly ``a_end - a_beg`` and ``b_end - b_beg``: the left flank's
+    alignment, ``seed_len`` M, the right flank's.  ``band`` is required (None or a negative one: an MsaError (ARG);
+    above ``_lib.XDROP_BAND_MAX``: UNSUPPORTED); ``xdrop`` < 0 never stops.  ``traceback=False`` gives everything but
+    the CIGAR and runs no walk.  Scoring and ``max_symbols`` as for extend_align."""
+    return _seed(True, A, B, seed_a, seed_b, seed_len, band, xdrop, gap_open, gap_extend, traceback, match, mismatch,
+                 alphabet, matrix, max_symbols)[0]
+
+
+def seed_align_batch(As, Bs, seed_a, seed_b, seed_len, band, xdrop=-1, gap_open=3, gap_extend=1, traceback=True,
+                     match=None, mismatch=None, alphabet=None, matrix=None, max_symbols=8):
+    """A batch of seed extensions (msa_seed_align_batch) -> a list of seed_align()'s dicts.
+
+    One seed per pair: ``seed_a`` / ``seed_b`` / ``seed_len`` hold one entry per pair, relative to it.  ``Bs``: a list
+    as long as ``As``, or one bytes object every A is aligned against (uploaded once): many seeds against one reference.
+    Several seeds on one pair are pairs whose sequences coincide.  One band, one xdrop and one alphabet for the whole
+    call; every launched flank is one wave's task, the two flanks of a seed next to each other."""
+    return _seed(False, As, Bs, seed_a, seed_b, seed_len, band, xdrop, gap_open, gap_extend, traceback, match, mismatch,
+                 alphabet, matrix, max_symbols)
 
 
 _PROFILE_MODES = {"local": LB.PROFILE_LOCAL, "global": LB.PROFILE_GLOBAL, "fit": LB.PROFILE_FIT}

@@ -925,3 +925,4 @@ int msa_plan_checksum(msa_plan* P, const int32_t* dH, int64_t pair, uint64_t* di
 #include "msa_rowapi.inc"
 #include "msa_alignapi.inc"
 #include "msa_xdropapi.inc"
+#include "msa_seedapi.inc"

@@ -1,5 +1,5 @@
-// msa_xdrop.hip -- banded extension alignment with X-drop termination (msa_xdrop_extend_run, msa_xdrop_extend_walk;
-// the contract is include/msa.h's at msa_extend_align_xdrop).
+// msa_xdrop.hip -- banded extension alignment with X-drop termination (msa_xdrop_extend_run, msa_xdrop_flank_run,
+// msa_xdrop_extend_walk; the contract is include/msa.h's at msa_extend_align_xdrop).
 //
 // The stripe kernel lays its phases, barriers and hand-offs out from m, n and the band before the launch, so it
 // computes every cell of its schedule.  A data-dependent stop needs a schedule without cross-wave dependencies:
@@ -63,14 +63,20 @@ __device__ __forceinline__ void xd_wave_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
-// Wave v of block b fills pair b * XD_WPB + v: A[pa .. + m) against B[pb .. + n), |m - n| <= w.  sub32: 1,024 int8
-// scores at stride 32 (row: A's code), or nullptr: match / mismatch.  g = gap_extend, op = gap_open.  xdrop < 0:
-// never stop.  dir may be nullptr (no bytes).  res[8 p ..] = {score, end_i, end_j, D, H(m, n) or XD_NONE, status,
-// cells computed, 0}.
+// Wave v of block b fills pair b * XD_WPB + v: A[pa .. + m) against B[pb .. + n), |m - n| <= w.  step (nullptr: every
+// pair +1): the pair's reading direction s, +1 or -1 (anything else: status MSA_ERR_ARG) -- row i's code is
+// A[pa + s (i - 1)], column j's is B[pb + s (j - 1)], so with s = -1 the pair is the sequences that END at pa and pb,
+// read backwards in place (a seed's left flank); s is wave-uniform and only the two code loads know of it: the cells,
+// the tracker, the bytes and the result are in the pair's own (flank) coordinates, and the table is never transposed.
+// STEP = (step != nullptr), the launcher's choice: a launch without steps runs the instantiation that has none in it.
+// sub32: 1,024 int8 scores at stride 32 (row: A's code), or nullptr: match / mismatch.  g = gap_extend, op = gap_open.
+// xdrop < 0: never stop.  dir may be nullptr (no bytes).  res[8 p ..] = {score, end_i, end_j, D, H(m, n) or XD_NONE,
+// status, cells computed, 0}.
+template <bool STEP>
 __global__ __launch_bounds__(64 * XD_WPB) void xdrop_fill_kernel(
     const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, int n_pairs, const long long* __restrict__ pm,
     const long long* __restrict__ pn, const long long* __restrict__ pa, const long long* __restrict__ pb,
-    const int8_t* __restrict__ sub32, int match, int mismatch, int g, int op, int w, int xdrop,
+    const int8_t* __restrict__ step, const int8_t* __restrict__ sub32, int match, int mismatch, int g, int op, int w, int xdrop,
     uint8_t* __restrict__ dir, const long long* __restrict__ dir_off, long long* __restrict__ res) {
   extern __shared__ __attribute__((aligned(16))) int xd_lds[];
   int8_t* stab = (int8_t*)xd_lds;
@@ -93,8 +99,9 @@ __global__ __launch_bounds__(64 * XD_WPB) void xdrop_fill_kernel(
     smax = max(smax, v < 0 ? -v : v);
   }
   smax = xd_wave_max(smax);
+  const int s = STEP ? __builtin_amdgcn_readfirstlane((int)step[pair]) : 1;
   int status = 0;
-  if (m64 < 1 || n64 < 1 || m64 > (1 << 26) || n64 > (1 << 26) || m64 - n64 > w || n64 - m64 > w)
+  if (m64 < 1 || n64 < 1 || m64 > (1 << 26) || n64 > (1 << 26) || m64 - n64 > w || n64 - m64 > w || (s != 1 && s != -1))
     status = MSA_ERR_ARG;
   else if (((long long)smax + 2ll * op + 2ll * g) * (m64 + n64 + 256) + ((long long)op - g) >= (1ll << 28))
     status = MSA_ERR_UNSUPPORTED;
@@ -114,8 +121,22 @@ __global__ __launch_bounds__(64 * XD_WPB) void xdrop_fill_kernel(
   }
   xd_wave_sync();
 
+  // Code t (0-based) of a side is at s t from its first symbol.  A lane's rows ascend and its columns descend with
+  // the lane, so with steps each lane keeps its own two bases -- row (i0 + lane)'s code is al[s (i0 - 1)], column
+  // (j0 - lane)'s is bl[s (j0 - 1)] -- and the offsets are wave-uniform: scalar arithmetic, one 64-bit add per load
   const uint8_t* a = A + pa[pair];
   const uint8_t* b = B + pb[pair];
+  const long long sl = (long long)(s * lane);
+  const uint8_t* al = a + sl;
+  const uint8_t* bl = b - sl;
+  auto code_a = [&](int i0) -> int {  // of row i0 + lane
+    if constexpr (STEP) return al[(long long)(s * (i0 - 1))];
+    else return a[(i0 + lane) - 1];
+  };
+  auto code_b = [&](int j0) -> int {  // of column j0 - lane
+    if constexpr (STEP) return bl[(long long)(s * (j0 - 1))];
+    else return b[(j0 - lane) - 1];
+  };
   const int RS = 2 * w + 1;
   uint8_t* dp = dir ? dir + dir_off[pair] : nullptr;
   // rows of anti-diagonal d: 1 <= i <= m, 1 <= d - i <= n, |2 i - d| <= w
@@ -127,8 +148,8 @@ __global__ __launch_bounds__(64 * XD_WPB) void xdrop_fill_kernel(
   // the codes of the next anti-diagonal's first chunk are loaded one anti-diagonal ahead
   int nlo = lo_of(2), nhi = hi_of(2), na = 0, nb = 0;
   if (nlo + lane <= nhi) {
-    na = a[nlo + lane - 1];
-    nb = b[2 - (nlo + lane) - 1];
+    na = code_a(nlo);
+    nb = code_b(2 - nlo);
   }
   for (int d = 2; d <= d_end; ++d) {
     const int ilo = nlo, ihi = nhi, ca0 = na, cb0 = nb;
@@ -137,8 +158,8 @@ __global__ __launch_bounds__(64 * XD_WPB) void xdrop_fill_kernel(
       nhi = hi_of(d + 1);
       const int i = nlo + lane;
       if (i <= nhi) {
-        na = a[i - 1];
-        nb = b[d + 1 - i - 1];
+        na = code_a(nlo);
+        nb = code_b(d + 1 - nlo);
       }
     }
     int ad = XD_NEG;
@@ -146,7 +167,7 @@ __global__ __launch_bounds__(64 * XD_WPB) void xdrop_fill_kernel(
       const int i = i0 + lane, j = d - i;
       if (i <= ihi) {
         const int k1 = j - i + w + 1;
-        const int ca = i0 == ilo ? ca0 : (int)a[i - 1], cb = i0 == ilo ? cb0 : (int)b[j - 1];
+        const int ca = i0 == ilo ? ca0 : code_a(i0), cb = i0 == ilo ? cb0 : code_b(d - i0);
         const int hd = Hs[k1], hl = Hs[k1 - 1], hu = Hs[k1 + 1], el = Es[k1 - 1], fu = Fs[k1 + 1];
         int e = max(hl - op, el - g), f = max(hu - op, fu - g);
         e = e < XD_NEG / 2 ? XD_NEG : e;

@@ -63,6 +63,10 @@
  *                        the banded extension with X-drop termination: the fill stops once the last two
  *                        anti-diagonals fall more than xdrop below the best score (build extension: a kernel family
  *                        of its own, one wave per pair, anti-diagonal by anti-diagonal; not a plan kind)
+ *   msa_xdrop_flank_run, msa_seed_align, msa_seed_align_batch, msa_seed_align32, msa_seed_align_batch32
+ *                        seed extension: both flanks of a seed in one call, the alignment through the seed (build
+ *                        extension: the X-drop fill with a reading direction per pair, so a left flank is read
+ *                        backwards in place from the uploaded buffers)
  *   msa_plan_create_scored32, msa_nw_align_scored32, msa_nw_align_batch_scored32, msa_fit_align32,
  *   msa_fit_align_batch32
  *                        MSA_NW_SCORED and MSA_NW_FIT over alphabets of up to 32 symbols (proteins, IUPAC DNA):
@@ -866,6 +870,70 @@ int msa_xdrop_extend_run(const uint8_t* dA, const uint8_t* dB, int64_t n_pairs, 
 int msa_xdrop_extend_walk(int64_t n_pairs, int32_t band, const uint8_t* d_dir, const int64_t* d_dir_off,
                           const int64_t* d_res, uint8_t* d_ops, const int64_t* d_ops_off, int64_t* d_info,
                           void* stream);
+/* msa_xdrop_extend_run with a reading direction per pair: d_step, DEVICE array of n_pairs int8, +1 or -1 (any other
+ * value: that pair's status is MSA_ERR_ARG, the other pairs are not affected), or NULL: every pair +1, which is
+ * msa_xdrop_extend_run itself.  A pair with step s takes row i's code from dA[a_off + s (i - 1)] and column j's from
+ * dB[b_off + s (j - 1)]: with s = -1, a_off and b_off name the bytes nearest the seed, and the pair is the two
+ * sequences that end there, read backwards in place -- dA[a_off - m + 1 .. a_off] and dB[b_off - n + 1 .. b_off] must
+ * lie inside the buffers.  Everything else is in the pair's own coordinates and as for msa_xdrop_extend_run: the cells,
+ * the stopping rule, the tie rules, d_res, the bytes msa_xdrop_extend_walk walks; d_sub32[32 a + b] stays A's code a
+ * against B's code b whatever the direction.  Checks and errors: msa_xdrop_extend_run's. */
+int msa_xdrop_flank_run(const uint8_t* dA, const uint8_t* dB, int64_t n_pairs, const int64_t* d_m,
+                        const int64_t* d_n, const int64_t* d_a_off, const int64_t* d_b_off, const int8_t* d_step,
+                        const int8_t* d_sub32, int32_t match, int32_t mismatch, int32_t gap_open, int32_t gap_extend,
+                        int32_t band, int32_t xdrop, uint8_t* d_dir, const int64_t* d_dir_off, int64_t* d_res,
+                        void* stream);
+
+/* Seed extension (build extension): the alignment through a seed -- A[seed_a .. + seed_len) against
+ * B[seed_b .. + seed_len), which the caller found -- extended on both flanks by the X-drop family above, in one call.
+ * The left flank is read backwards in place (msa_xdrop_flank_run's step -1): nothing is reversed or copied on the host,
+ * and in a batch coinciding ranges (several seeds on one pair, many seeds against one reference) are uploaded once.
+ * Contract.  With L = A[:seed_a][::-1] against B[:seed_b][::-1] and R = A[seed_a+seed_len:] against
+ * B[seed_b+seed_len:], each flank's result is FIELD FOR FIELD what msa_extend_align_xdrop returns for that pair of byte
+ * strings under the same band and xdrop: the band clip, the row-major tie rule in flank coordinates (so for the left
+ * flank the end nearest the seed in A, then in B), and the walk's tie order.  Then:
+ *   score = flank_score[0] + sum over t of S[A[seed_a+t]][B[seed_b+t]] + flank_score[1]  (the seed may hold mismatches;
+ *           seed_len = 0 is a bare anchor);
+ *   beg = (seed_a - L.a_end, seed_b - L.b_end);  end = (seed_a + seed_len + R.a_end, seed_b + seed_len + R.b_end);
+ *   the CIGAR runs start -> end and consumes exactly end - beg on each side: the left flank's ops IN WALK ORDER (its
+ *   walk goes from the far end to the seed, which is left -> right already; its border gap comes after them), then
+ *   seed_len x M, then the right flank's ops reversed, run-length encoded once over the whole.  cigar == NULL: no bytes
+ *   and no walks.
+ *   flank_score (may be NULL) and diagonals (may be NULL): {left, right}.
+ * Empty flanks.  A flank with no symbols on either side (seed_a == 0 or seed_b == 0; the seed ending at m or at n) is
+ * not launched: its result is the empty extension, score 0, end (0, 0), diagonals 0.  A call whose flanks are all empty
+ * makes no device call.
+ * Batch: one seed per pair, seed_a / seed_b / seed_len (n_pairs each) relative to the pair; beg_ij, end_ij, flank_score
+ * and diagonals hold 2 entries per pair; the other arguments are the batch twins'.
+ * Checks, in this order and before any device call.  MSA_ERR_ARG: the alphabet and matrix (as for the twins), a NULL
+ * input, a missing score, beg_ij or end_ij, n_pairs < 1, m or n < 1, a range outside the buffers, seed_len < 0,
+ * seed_a < 0 or seed_b < 0, seed_a + seed_len > m or seed_b + seed_len > n, band < 0.  MSA_ERR_UNSUPPORTED: band >
+ * MSA_XDROP_BAND_MAX (after the band of the call's longest sequence stood in for a wider one), the gap rule, the
+ * value-range inequality taken with the whole m + n.  MSA_ERR_ALPHABET: as for the twins.  Then the device: admission
+ * with the launched flanks' footprints, ranges of seeds within a quarter of the budget; the two flanks of a seed are
+ * neighbouring tasks of one launch.
+ * Out of scope: global_score per flank, per-seed bands or xdrop, chaining several seeds, seeds on the reverse-complement
+ * strand (the caller complements), an unbanded seed extension. */
+int msa_seed_align(const char* A0, size_t m, const char* B0, size_t n, int64_t seed_a, int64_t seed_b,
+                   int64_t seed_len, const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                   int32_t gap_extend, int64_t band, int32_t xdrop, int32_t* score, int64_t* beg_ij, int64_t* end_ij,
+                   int32_t* flank_score, int64_t* diagonals, char* cigar, size_t cigar_cap);
+int msa_seed_align_batch(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                         const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                         const int64_t* seed_a, const int64_t* seed_b, const int64_t* seed_len, const char* alphabet,
+                         size_t n_sym, const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band,
+                         int32_t xdrop, int32_t* score, int64_t* beg_ij, int64_t* end_ij, int32_t* flank_score,
+                         int64_t* diagonals, char* cigars, size_t cigar_cap, int64_t* cigar_off);
+int msa_seed_align32(const char* A0, size_t m, const char* B0, size_t n, int64_t seed_a, int64_t seed_b,
+                     int64_t seed_len, const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
+                     int32_t gap_extend, int64_t band, int32_t xdrop, int32_t* score, int64_t* beg_ij,
+                     int64_t* end_ij, int32_t* flank_score, int64_t* diagonals, char* cigar, size_t cigar_cap);
+int msa_seed_align_batch32(const char* A, size_t a_len, const char* B, size_t b_len, int64_t n_pairs,
+                           const int64_t* a_off, const int64_t* m, const int64_t* b_off, const int64_t* n,
+                           const int64_t* seed_a, const int64_t* seed_b, const int64_t* seed_len, const char* alphabet,
+                           size_t n_sym, const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band,
+                           int32_t xdrop, int32_t* score, int64_t* beg_ij, int64_t* end_ij, int32_t* flank_score,
+                           int64_t* diagonals, char* cigars, size_t cigar_cap, int64_t* cigar_off);
 
 /* The four matrix-scored entries above for alphabets of up to 32 symbols (proteins with B Z X *, IUPAC DNA): the
  * signatures of their 8-symbol twins, 1 <= n_sym <= 32, sub = n_sym x n_sym.  With n_sym <= 8 a call builds exactly
