@@ -38,6 +38,7 @@ NW_EXTEND = 10
 NW_EXTEND_BAND = 11
 SCORE_NONE = -(1 << 31)  # MSA_SCORE_NONE: no such score (a clipped banded extension's global score)
 XDROP_BAND_MAX = 640     # MSA_XDROP_BAND_MAX
+CHAIN_LOOKBACK_MAX = 1024  # MSA_CHAIN_LOOKBACK_MAX
 CELLS_NONE, CELLS_H, CELLS_DIR, CELLS_TAB = 0, 1, 2, 3
 # msa_profile_align's modes
 PROFILE_LOCAL, PROFILE_GLOBAL, PROFILE_FIT = 0, 1, 2
@@ -260,6 +261,11 @@ def lib() -> C.CDLL:
     L.msa_xdrop_extend_run.argtypes = [P, P, i64, P, P, P, P, P, i32, i32, i32, i32, i32, i32, P, P, P, P]
     L.msa_xdrop_extend_walk.argtypes = [i64, i32, P, P, P, P, P, P, P]
     L.msa_xdrop_flank_run.argtypes = [P, P, i64, P, P, P, P, P, P, i32, i32, i32, i32, i32, i32, P, P, P, P]
+    # seed chaining: no alignment kind (no sequences, no CIGAR), bound by hand
+    chain = [i32, i32, i32, i64, i64, i32]  # match, gap_open, gap_extend, band, max_dist, lookback
+    L.msa_chain_run.argtypes = [P, P, P, i64, P] + chain + [P, P, P, P]
+    L.msa_chain_seeds.argtypes = [P, P, P, i64] + chain + [i32, P, P, P, P, P]
+    L.msa_chain_seeds_batch.argtypes = [P, P, P, i64, P] + chain + [i32, P, P, P, P, P]
     # the alignment entries: every entry of every kind, from the kind's own argument order
     for kind in KINDS.values():
         for name, slots in kind.entries():
@@ -303,4 +309,5 @@ EXPORTED = [
     "msa_extend_align_batch_xdrop32", "msa_xdrop_extend_run", "msa_xdrop_extend_walk",
     "msa_plan_create_profile", "msa_profile_align", "msa_profile_align_batch",
     "msa_xdrop_flank_run", "msa_seed_align", "msa_seed_align_batch", "msa_seed_align32", "msa_seed_align_batch32",
+    "msa_chain_run", "msa_chain_seeds", "msa_chain_seeds_batch",
 ]

@@ -621,6 +621,263 @@ def seed_align_batch(As, Bs, seed_a, seed_b, seed_len, band, xdrop=-1, gap_open=
                  alphabet, matrix, max_symbols)
 
 
+def _chain(single, seed_a, seed_b, seed_len, band, match, gap_open, gap_extend, max_dist, lookback, min_score):
+    """chain_seeds / chain_seeds_batch: every problem sorted by (be, ae, the caller's index), the library's call over the
+    sorted anchors, and its results mapped back -> per problem (chains, f, pred), f and pred in the caller's indexing."""
+    probs = []
+    for x in zip(seed_a, seed_b, seed_len):
+        a, b, ln = (np.asarray(v, dtype=np.int64).reshape(-1) for v in x)
+        if not len(a) == len(b) == len(ln):
+            raise ValueError("seed_a, seed_b and seed_len must hold one entry per anchor")
+        # (lexsort is stable: equal (be, ae) stay in the caller's order)
+        probs.append((a, b, ln, np.lexsort((a + ln, b + ln))))
+    off = np.concatenate(([0], np.cumsum([len(p[0]) for p in probs]))).astype(np.int64)
+    total = int(off[-1])
+    a, b, ln = (np.ascontiguousarray(np.concatenate([p[k][p[3]] for p in probs]), dtype=np.int64) for k in range(3))
+    f, pred, chain_of, score = (np.zeros(max(total, 1), dtype=np.int32) for _ in range(4))
+    n_chains = np.zeros(len(probs), dtype=np.int32)
+    params = (int(match), int(gap_open), int(gap_extend), -1 if band is None else int(band), int(max_dist),
+              int(lookback), int(min_score))
+    outs = (_ptr(f), _ptr(pred), _ptr(chain_of), _ptr(n_chains), _ptr(score))
+    if single:
+        name = "msa_chain_seeds"
+        rc = LB.lib().msa_chain_seeds(_ptr(a), _ptr(b), _ptr(ln), total, *params, *outs)
+    else:
+        name = "msa_chain_seeds_batch"
+        rc = LB.lib().msa_chain_seeds_batch(_ptr(a), _ptr(b), _ptr(ln), len(probs), _ptr(off), *params, *outs)
+    LB.check(rc, name)
+    res = []
+    for p, (pa, pb, pl, order) in enumerate(probs):
+        lo, hi = int(off[p]), int(off[p + 1])
+        co = chain_of[lo:hi]
+        # the anchors of every kept chain, by rank, each in ascending sorted position: chain order
+        kept = np.flatnonzero(co >= 0)
+        kept = kept[np.argsort(co[kept], kind="stable")]
+        ends = np.cumsum(np.bincount(co[kept], minlength=int(n_chains[p])))
+        chains = []
+        for r in range(int(n_chains[p])):
+            members = order[kept[ends[r - 1] if r else 0:ends[r]]]
+            first, last = int(members[0]), int(members[-1])
+            chains.append(dict(score=int(score[lo + r]), anchors=[int(t) for t in members], a_beg=int(pa[first]),
+                               b_beg=int(pb[first]), a_end=int(pa[last] + pl[last]), b_end=int(pb[last] + pl[last])))
+        fc, pc = np.zeros(hi - lo, dtype=np.int32), np.full(hi - lo, -1, dtype=np.int32)
+        fc[order] = f[lo:hi]
+        has = pred[lo:hi] >= 0
+        pc[order[has]] = order[pred[lo:hi][has]]
+        res.append((chains, fc, pc))
+    return res
+
+
+def chain_seeds(seed_a, seed_b, seed_len, band, match=1, gap_open=3, gap_extend=1, max_dist=5000, lookback=64,
+                min_score=0):
+    """Seed chaining (build extension, msa_chain_seeds): the chains of one pair's anchors, rank 0 (the best) first ->
+    a list of dict(score, anchors, a_beg, b_beg, a_end, b_end).
+
+    Anchor t is ``A[seed_a[t] : seed_a[t] + seed_len[t]]`` seeded against ``B[seed_b[t] : ...]`` (seed_align's
+    coordinates), in any order: the call sorts them by (b end, a end, index), and ``anchors`` holds the CALLER's
+    indices in chain order; the chain spans ``A[a_beg:a_end]`` and ``B[b_beg:b_end]``.  With ``ae = a + len``,
+    ``be = b + len``, ``da = ae_i - ae_j`` and ``db = be_i - be_j``, anchor j (earlier in the sorted order) may precede
+    i iff it is at most ``lookback`` places before it, ``0 < da, db <= max_dist`` and ``|da - db| <= band``; then
+    ``f(i) = max(match len_i, max_j f(j) + match min(da, db, len_i) - gc(|da - db|))``, ``gc(L) = (gap_open -
+    gap_extend) + gap_extend L``, ``gc(0) = 0``, the predecessor being the latest j that gives the maximum.  Chains are
+    cut from the anchors in order of ``f`` descending: follow the predecessors until there is none or one is taken by an
+    earlier chain (the chain then scores the difference); chains below ``min_score`` are dropped, their anchors stay
+    taken.  All integers: the result is exact.  ``band`` is required (None or negative: an MsaError (UNSUPPORTED), as
+    for every parameter outside its bounds: ``match`` 1..15, ``gap_open >= gap_extend >= 0``, ``max_dist >= 1``,
+    ``lookback`` 1.. ``_lib.CHAIN_LOOKBACK_MAX``); a negative coordinate, ``len < 1`` or an end above 2**26: ARG.  The
+    recurrence runs on the device, one wave per problem; a problem of at most one anchor needs none."""
+    return _chain(True, [seed_a], [seed_b], [seed_len], band, match, gap_open, gap_extend, max_dist, lookback,
+                  min_score)[0][0]
+
+
+def chain_seeds_batch(seed_a, seed_b, seed_len, band, match=1, gap_open=3, gap_extend=1, max_dist=5000, lookback=64,
+                      min_score=0, full=False):
+    """A batch of chaining problems (msa_chain_seeds_batch) -> a list of chain_seeds()'s lists.
+
+    ``seed_a`` / ``seed_b`` / ``seed_len``: lists holding one array per problem; one set of parameters for the call.
+    ``full=True`` -> (that list, f, pred): per problem the int32 arrays ``f`` and ``pred`` in the caller's indexing
+    (``pred[t]`` = the caller's index of t's predecessor, or -1)."""
+    if not (len(seed_a) == len(seed_b) == len(seed_len)):
+        raise ValueError("seed_a, seed_b and seed_len must hold one array per problem")
+    res = _chain(False, seed_a, seed_b, seed_len, band, match, gap_open, gap_extend, max_dist, lookback,
+                 min_score) if len(seed_a) else []
+    chains = [r[0] for r in res]
+    return (chains, [r[1] for r in res], [r[2] for r in res]) if full else chains
+
+
+def _runs(cigar):
+    """[[run, op]] of a CIGAR string."""
+    out, run = [], 0
+    for c in cigar:
+        if c.isdigit():
+            run = 10 * run + int(c)
+        else:
+            out.append([run, c])
+            run = 0
+    return out
+
+
+def _split_runs(runs, ca, cb):
+    """(head, tail) of a run list: head consumes exactly ``ca`` symbols of A (M, I) and ``cb`` of B (M, D)."""
+    head, runs = [], [list(r) for r in runs]
+    while ca or cb:
+        run, op = runs[0]
+        take = min(run, ca if op == "I" else cb if op == "D" else min(ca, cb))
+        if take == 0:
+            raise LB.MsaError(-9, "chain_align")  # (cannot happen: the flanks' ends are the walk's own)
+        head.append([take, op])
+        ca, cb = ca - take * (op != "D"), cb - take * (op != "I")
+        if take == run:
+            runs.pop(0)
+        else:
+            runs[0][0] -= take
+    return head, runs
+
+
+def _chain_align(single, As, Bs, seed_a, seed_b, seed_len, band, xdrop, chain_match, chain_gap_open, chain_gap_extend,
+                 max_dist, lookback, min_score, gap_open, gap_extend, traceback, match, mismatch, alphabet, matrix,
+                 max_symbols):
+    """chain_align / chain_align_batch: three device calls per batch -- chain_seeds_batch, ONE nw_align_batch over the
+    gaps between the anchors of every pair's best chain, ONE seed_align_batch for the two outer flanks (a bare anchor
+    between ``A[:a_beg]`` and ``A[a_end:]`` joined, and the same of B: its left and right flank are the chain's) -- and
+    the sum of the parts."""
+    if max_symbols not in (8, 32):
+        raise ValueError("max_symbols must be 8 or 32")
+    As = [_buf(x) for x in As]
+    Bs = [_buf(Bs)] * len(As) if isinstance(Bs, (bytes, bytearray, str, memoryview)) else [_buf(x) for x in Bs]
+    if not (len(As) == len(Bs) == len(seed_a) == len(seed_b) == len(seed_len)):
+        raise ValueError("Bs, seed_a, seed_b and seed_len must hold one entry per pair")
+    if not As:
+        return []
+    go, ge = int(gap_open), int(gap_extend)
+    skw = dict(gap_open=go, gap_extend=ge, traceback=traceback, match=match, mismatch=mismatch, alphabet=alphabet,
+               matrix=matrix, max_symbols=max_symbols)
+    _scoring(LB.KINDS["seed"], (), match, mismatch, alphabet, matrix, max_symbols)  # (the argument rules, before work)
+    chains = _chain(single, seed_a, seed_b, seed_len, band,
+                    chain_match, go if chain_gap_open is None else chain_gap_open,
+                    ge if chain_gap_extend is None else chain_gap_extend, max_dist, lookback, min_score)
+    if matrix is not None:
+        S, lut = np.asarray(matrix, dtype=np.int64), np.full(256, -1, dtype=np.int64)
+        lut[np.frombuffer(_buf(alphabet), dtype=np.uint8)] = np.arange(len(_buf(alphabet)))
+    ma, mi = (1 if match is None else int(match)), (0 if mismatch is None else int(mismatch))
+
+    def columns(x, y):  # the score of the columns x[t] against y[t]
+        x, y = np.frombuffer(x, dtype=np.uint8), np.frombuffer(y, dtype=np.uint8)
+        if matrix is None:
+            return int(np.where(x == y, ma, mi).sum())
+        if (lut[x] < 0).any() or (lut[y] < 0).any():
+            raise LB.MsaError(-2, "chain_align")
+        return int(S[lut[x], lut[y]].sum())
+
+    # per pair with a chain: its parts in order, ("M", k, score) | ("I" / "D", L, score) | ("gap", index into the nw
+    # batch); the gaps of all pairs are one batch, the flanks of all pairs another
+    plans, gap_a, gap_b, fl_a, fl_b, fl_sa, fl_sb = [], [], [], [], [], [], []
+    for A, B, sa, sb, sl, (found, _, _) in zip(As, Bs, seed_a, seed_b, seed_len, chains):
+        if not found:
+            plans.append(None)
+            continue
+        sa, sb, sl = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (sa, sb, sl))
+        ch = found[0]
+        t0 = ch["anchors"][0]
+        pae, pbe = int(sa[t0] + sl[t0]), int(sb[t0] + sl[t0])
+        if pae > len(A) or pbe > len(B):
+            raise LB.MsaError(-1, "chain_align")
+        parts = [("M", int(sl[t0]), columns(A[ch["a_beg"]:pae], B[ch["b_beg"]:pbe]))]
+        for t in ch["anchors"][1:]:
+            ae, be = int(sa[t] + sl[t]), int(sb[t] + sl[t])
+            if ae > len(A) or be > len(B):
+                raise LB.MsaError(-1, "chain_align")
+            k = min(ae - pae, be - pbe, int(sl[t]))  # the anchor keeps its last k columns
+            ga, gb = ae - k - pae, be - k - pbe
+            if ga and gb:
+                parts.append(("gap", len(gap_a)))
+                gap_a.append(A[pae:ae - k])
+                gap_b.append(B[pbe:be - k])
+            elif ga or gb:
+                parts.append(("I" if ga else "D", ga + gb, -((go - ge) + ge * (ga + gb))))
+            parts.append(("M", k, columns(A[ae - k:ae], B[be - k:be])))
+            pae, pbe = ae, be
+        fa, fb = A[:ch["a_beg"]] + A[pae:], B[:ch["b_beg"]] + B[pbe:]
+        plans.append((ch, parts, len(fl_a) if fa and fb else None))
+        if fa and fb:
+            fl_a.append(fa), fl_b.append(fb), fl_sa.append(ch["a_beg"]), fl_sb.append(ch["b_beg"])
+    gaps = nw_align_batch(gap_a, gap_b, band=-1 if band is None else int(band), **skw) if gap_a else []
+    flanks = seed_align_batch(fl_a, fl_b, fl_sa, fl_sb, [0] * len(fl_a), band, xdrop=xdrop, **skw) if fl_a else []
+    empty = dict(score=0, a_end=0, b_end=0, diagonals=0, dropped=False)
+    res = []
+    for plan in plans:
+        if plan is None:
+            res.append(None)
+            continue
+        ch, parts, fl = plan
+        left, right = (flanks[fl]["left"], flanks[fl]["right"]) if fl is not None else (dict(empty), dict(empty))
+        score, runs = left["score"] + right["score"], []
+        if traceback:
+            runs, tail = _split_runs(_runs(flanks[fl]["cigar"]), left["a_end"], left["b_end"]) if fl is not None \
+                else ([], [])
+        for part in parts:
+            if part[0] == "gap":
+                g = gaps[part[1]]
+                score += g["score"]
+                more = _runs(g["cigar"]) if traceback else []
+            else:
+                score += part[2]
+                more = [[part[1], part[0]]] if part[1] else []
+            runs += more
+        r = dict(score=score, a_beg=ch["a_beg"] - left["a_end"], b_beg=ch["b_beg"] - left["b_end"],
+                 a_end=ch["a_end"] + right["a_end"], b_end=ch["b_end"] + right["b_end"], chain_score=ch["score"],
+                 anchors=ch["anchors"], left=left, right=right)
+        if traceback:
+            merged = []
+            for run, op in runs + tail:
+                if merged and merged[-1][1] == op:
+                    merged[-1][0] += run
+                else:
+                    merged.append([run, op])
+            r["cigar"] = "".join(f"{run}{op}" for run, op in merged)
+        res.append(r)
+    return res
+
+
+def chain_align(A, B, seed_a, seed_b, seed_len, band, xdrop=-1, chain_match=1, chain_gap_open=None,
+                chain_gap_extend=None, max_dist=5000, lookback=64, min_score=0, gap_open=3, gap_extend=1,
+                traceback=True, match=None, mismatch=None, alphabet=None, matrix=None, max_symbols=8):
+    """The alignment of a pair through the best chain of its anchors -> dict(score, a_beg, b_beg, a_end, b_end,
+    chain_score, anchors, left, right[, cigar]), or None for a pair without a chain (no anchors, or none reaching
+    ``min_score``): ``A[a_beg:a_end]`` against ``B[b_beg:b_end]``.
+
+    A Python composition of three device calls, not an alignment kind of the library: chain_seeds picks the rank-0 chain
+    (``chain_match``, ``chain_gap_open`` / ``chain_gap_extend`` -- None: the alignment's ``gap_open`` / ``gap_extend``
+    --, ``max_dist``, ``lookback``, ``min_score``; ``anchors`` are the caller's indices in chain order, ``chain_score``
+    the chain's); then every part is a call the library already has, and ``score`` is their sum:
+      * overlapping anchors are trimmed: after anchor j, anchor i keeps its last ``k = min(da, db, len_i)`` columns;
+        each kept column scores under the call's scoring (mismatches allowed, as seed_align's ``seed_score``);
+      * between them ``ga = da - k`` symbols of A and ``gb = db - k`` of B remain: nothing; or, one side empty, one I
+        (A's) or D (B's) run costing ``(gap_open - gap_extend) + gap_extend L``; or ``nw_align(..., band=band)`` of the
+        two substrings, which exists because the chain keeps ``|ga - gb| <= band`` -- all gaps of a call are one
+        nw_align_batch call;
+      * ``left`` and ``right`` are seed_align's dictionaries of the flank left of the first anchor and right of the
+        last: ``extend_align(..., band=band, xdrop=xdrop)`` of those byte strings, the left ones reversed -- all
+        flanks of a call are one seed_align_batch call.
+    The CIGAR is the parts in order, neighbouring runs of one op merged, and consumes exactly ``a_end - a_beg`` and
+    ``b_end - b_beg``.  ``traceback=False`` runs no walks.  Scoring and ``max_symbols`` as for seed_align."""
+    return _chain_align(True, [A], [B], [seed_a], [seed_b], [seed_len], band, xdrop, chain_match, chain_gap_open,
+                        chain_gap_extend, max_dist, lookback, min_score, gap_open, gap_extend, traceback, match,
+                        mismatch, alphabet, matrix, max_symbols)[0]
+
+
+def chain_align_batch(As, Bs, seed_a, seed_b, seed_len, band, xdrop=-1, chain_match=1, chain_gap_open=None,
+                      chain_gap_extend=None, max_dist=5000, lookback=64, min_score=0, gap_open=3, gap_extend=1,
+                      traceback=True, match=None, mismatch=None, alphabet=None, matrix=None, max_symbols=8):
+    """A batch of chain_align() -> a list of its results (None for a pair without a chain).
+
+    ``seed_a`` / ``seed_b`` / ``seed_len``: one array of anchors per pair; ``Bs``: a list as long as ``As``, or one bytes
+    object every A is aligned against.  Three device calls for the whole batch: the chains, the gaps, the flanks."""
+    return _chain_align(False, As, Bs, seed_a, seed_b, seed_len, band, xdrop, chain_match, chain_gap_open,
+                        chain_gap_extend, max_dist, lookback, min_score, gap_open, gap_extend, traceback, match,
+                        mismatch, alphabet, matrix, max_symbols)
+
+
 _PROFILE_MODES = {"local": LB.PROFILE_LOCAL, "global": LB.PROFILE_GLOBAL, "fit": LB.PROFILE_FIT}
 
 

@@ -34,6 +34,7 @@
 #include "msa_traceback.hip"
 #include "msa_tbatch.hip"
 #include "msa_xdrop.hip"
+#include "msa_chain.hip"
 
 using namespace msa;
 
@@ -926,3 +927,4 @@ int msa_plan_checksum(msa_plan* P, const int32_t* dH, int64_t pair, uint64_t* di
 #include "msa_alignapi.inc"
 #include "msa_xdropapi.inc"
 #include "msa_seedapi.inc"
+#include "msa_chainapi.inc"

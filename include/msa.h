@@ -912,8 +912,8 @@ int msa_xdrop_flank_run(const uint8_t* dA, const uint8_t* dB, int64_t n_pairs, c
  * value-range inequality taken with the whole m + n.  MSA_ERR_ALPHABET: as for the twins.  Then the device: admission
  * with the launched flanks' footprints, ranges of seeds within a quarter of the budget; the two flanks of a seed are
  * neighbouring tasks of one launch.
- * Out of scope: global_score per flank, per-seed bands or xdrop, chaining several seeds, seeds on the reverse-complement
- * strand (the caller complements), an unbanded seed extension. */
+ * Out of scope: global_score per flank, per-seed bands or xdrop, seeds on the reverse-complement strand (the caller
+ * complements), an unbanded seed extension.  (Choosing among several seeds of a pair: msa_chain_seeds, below.) */
 int msa_seed_align(const char* A0, size_t m, const char* B0, size_t n, int64_t seed_a, int64_t seed_b,
                    int64_t seed_len, const char* alphabet, size_t n_sym, const int8_t* sub, int32_t gap_open,
                    int32_t gap_extend, int64_t band, int32_t xdrop, int32_t* score, int64_t* beg_ij, int64_t* end_ij,
@@ -934,6 +934,57 @@ int msa_seed_align_batch32(const char* A, size_t a_len, const char* B, size_t b_
                            size_t n_sym, const int8_t* sub, int32_t gap_open, int32_t gap_extend, int64_t band,
                            int32_t xdrop, int32_t* score, int64_t* beg_ij, int64_t* end_ij, int32_t* flank_score,
                            int64_t* diagonals, char* cigars, size_t cigar_cap, int64_t* cigar_off);
+
+/* Seed chaining (build extension; a kernel family of its own, msa_chain.hip: one wave per problem): the colinear
+ * subsets of a pair's anchors with the best scores -- the step between seeding and extension.  All integers, exact.
+ * A problem is the list of the N anchors of one pair; anchor t = (a, b, len): A[a .. a + len) seeded against
+ * B[b .. b + len), msa_seed_align's coordinates; ae = a + len, be = b + len.  Anchors come in nondecreasing (be, ae)
+ * lexicographic order; duplicates are allowed.  One set of parameters per call: match >= 1; gap_open >= gap_extend >= 0,
+ * a length difference of L costing gc(L) = (gap_open - gap_extend) + gap_extend L, gc(0) = 0; band >= 0, the largest
+ * diagonal skew between neighbours of a chain; max_dist >= 1; lookback in 1 .. MSA_CHAIN_LOOKBACK_MAX.
+ *   For j < i, da = ae_i - ae_j and db = be_i - be_j; j may precede i iff i - j <= lookback, da > 0, db > 0,
+ *   da <= max_dist, db <= max_dist and |da - db| <= band.
+ *     cand(j, i) = f(j) + match min(da, db, len_i) - gc(|da - db|)
+ *     f(i)       = max(match len_i, max over admissible j of cand(j, i))
+ *     pred(i)    = the LARGEST admissible j with cand(j, i) == f(i) if f(i) > match len_i, else -1
+ *   (a candidate that merely equals match len_i is no predecessor, minimap2's `sc > max_f`).  f(i) <= match ae_i, so
+ *   int32 holds everything once coordinates are >= 0, len >= 1, ae and be <= 2^26, match 2^26 < 2^30 and
+ *   gc(min(band, 2^26)) < 2^30.  band and max_dist above 2^26 act as 2^26.
+ * Chains (on the host, O(N log N)): the anchors in order of f descending, ties to the smaller index; from an anchor
+ * not yet in a chain follow pred until it is -1 or reaches an anchor u already taken; the chain scores f(end), or
+ * f(end) - f(u).  A chain scoring below min_score is dropped, its anchors stay taken.  The kept chains are ranked in
+ * that order, rank 0 first.
+ * msa_chain_seeds_batch: a, b, len (int64) hold the anchors of all problems back to back, problem p's being
+ * off[p] .. off[p + 1] (off: n_problems + 1, off[0] >= 0, ascending, at most 2^26 anchors per problem).  Out, per
+ * anchor: f and pred (either may be NULL; pred is an index within the problem), chain_of = the rank of the anchor's
+ * chain in its problem, or -1; per problem n_chains; and chain_score (may be NULL): problem p's chains, by rank, at
+ * chain_score[off[p] .. off[p] + n_chains[p]).  msa_chain_seeds: one problem of n >= 0 anchors.
+ * Errors, in this order.  MSA_ERR_ARG: a NULL a, b, len (with any anchor), off, chain_of or n_chains, n_problems < 1,
+ * n < 0, off not as above, a negative coordinate, len < 1, ae or be above 2^26, anchors out of order.
+ * MSA_ERR_UNSUPPORTED: a parameter outside its bounds above.  Then the device -- unless no problem holds more than one
+ * anchor: such a call is answered on the host (f = match len, pred = -1) and succeeds with or without a GPU.
+ * Otherwise: admission against the device budget, ranges of problems within a quarter of it, one launch per range.
+ * Out of scope: float / log gap costs as minimap2's, per-problem parameters, a lookback above the cap, minimap2's skip
+ * heuristics, reverse-strand anchors (the caller flips them), re-chaining after alignment. */
+#define MSA_CHAIN_LOOKBACK_MAX 1024
+int msa_chain_seeds(const int64_t* a, const int64_t* b, const int64_t* len, int64_t n, int32_t match,
+                    int32_t gap_open, int32_t gap_extend, int64_t band, int64_t max_dist, int32_t lookback,
+                    int32_t min_score, int32_t* f, int32_t* pred, int32_t* chain_of, int32_t* n_chains,
+                    int32_t* chain_score);
+int msa_chain_seeds_batch(const int64_t* a, const int64_t* b, const int64_t* len, int64_t n_problems,
+                          const int64_t* off, int32_t match, int32_t gap_open, int32_t gap_extend, int64_t band,
+                          int64_t max_dist, int32_t lookback, int32_t min_score, int32_t* f, int32_t* pred,
+                          int32_t* chain_of, int32_t* n_chains, int32_t* chain_score);
+/* The device-resident form: asynchronous on `stream`, no allocation, no host sync.  d_a, d_b, d_len, d_off: DEVICE
+ * arrays as above; d_f, d_pred (per anchor) and d_status (per problem): DEVICE int32.  The kernel checks each problem's
+ * anchors and offsets itself: a problem that breaks a rule gets status MSA_ERR_ARG and nothing else is written for it,
+ * its neighbours are not affected; N = 0 is status 0 and writes nothing.  Dynamic LDS: four problems x three int32
+ * rings of 64 ceil(lookback / 64) + 64 entries per workgroup, 52,224 B at the cap.
+ * Host-side errors: a NULL array, n_problems < 1 or > 2^26: MSA_ERR_ARG; a parameter outside its bounds:
+ * MSA_ERR_UNSUPPORTED; then the device. */
+int msa_chain_run(const int64_t* d_a, const int64_t* d_b, const int64_t* d_len, int64_t n_problems,
+                  const int64_t* d_off, int32_t match, int32_t gap_open, int32_t gap_extend, int64_t band,
+                  int64_t max_dist, int32_t lookback, int32_t* d_f, int32_t* d_pred, int32_t* d_status, void* stream);
 
 /* The four matrix-scored entries above for alphabets of up to 32 symbols (proteins with B Z X *, IUPAC DNA): the
  * signatures of their 8-symbol twins, 1 <= n_sym <= 32, sub = n_sym x n_sym.  With n_sym <= 8 a call builds exactly
